@@ -30,7 +30,12 @@ parsed).  The FULL object described below goes to bench_detail.json beside this 
 --config 5 is not a BASELINE configuration: a 128x128-chunk world whose trees do not fit the 256 MiB Infinity Cache, checked
 against rows the CPU oracle renders in the same run (how the design degrades beyond the caches).
 
-The full result object carries:
+A plain run does only what the headline needs: set-up, the warm-up steps, the timed steps, --dump-outputs DIR (the image the
+last timed step read back into host memory, see dump_outputs) and the line.  Its roofline carries the kernel and the launch
+time of the timed region, not `achieved` / `frac` (those take an oracle run of their own).  Everything below that is measured
+or checked beyond the timed steps runs only with --full (--no-cpu, --no-roofline, --no-extras, --no-other-configs trim it).
+
+With --full the result object also carries:
   roofline     — the contract figure: achieved = ALGORITHMIC bytes per sample of the reference's
                  access stream (counted by the CPU oracle on a row-sample of this same view) x samples per launch /
                  mean launch duration from HIP events on the launch stream, against the 8 TB/s HBM peak.  It is a
@@ -290,6 +295,25 @@ def compare_golden(image, gold, width, against="tests/golden/timed_rows.npz (row
     return {"rows": [int(y) for y in rows], "pixels": int(same.size), "pixels_differing": int((~same).sum()),
             "bit_identical": bool(same.all()), "max_rel_err": float(np.nanmax(rel)) if rel.size else 0.0,
             "passes": int(len(gold[0])), "against": against}
+
+
+DUMP_LIMIT = 64 << 20    # bytes --dump-outputs may write in all
+DUMP_SAMPLE = 1 << 21    # pixels of the fixed sample written instead when the whole image would not fit (40 MiB with its indices)
+
+
+def dump_outputs(out_dir, image, width, height):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step, the image read back into host memory
+    (float32, the running mean since the last read-back), as DIR/image.npy [height, width, 3].  A view whose image is larger
+    than DUMP_LIMIT (3840x2160) writes a fixed sample instead: DIR/image_sample.npy [DUMP_SAMPLE, 3] float32, the pixels at
+    DIR/image_sample_index.npy (float64, ascending pixel indices drawn by numpy's default_rng(0), the same in every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.asarray(image, np.float32).reshape(height, width, 3)
+    if img.nbytes <= DUMP_LIMIT:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+        return
+    idx = np.sort(np.random.default_rng(0).choice(width * height, DUMP_SAMPLE, replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), img.reshape(-1, 3)[idx])
+    np.save(os.path.join(out_dir, "image_sample_index.npy"), idx.astype(np.float64))
 
 
 def live_golden(sc, n_rows=12, n_passes=4):
@@ -576,12 +600,16 @@ def main():
     ap.add_argument("--chunks", type=int, default=32)
     ap.add_argument("--kernel", type=int, default=0, help="kernel variant (CHUNKY_OPT_KERNEL)")
     ap.add_argument("--tile", type=int, default=0, help="shard tiles: 0 = 16x16-pixel blocks (default), n > 0 = runs of n pixel indices")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: roofline, cpu_baseline, image checks, extensions, "
+                                                         "end_to_end, group_check, other_configs (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes what the last timed step read back (the image, "
+                                                                       "float32) as DIR/*.npy; see dump_outputs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--no-roofline", action="store_true",
-                    help="skip the oracle row-sample too: nothing under oracle/ is loaded, built or spawned (profiler runs)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the end_to_end / image_check / group_check legs (profiler runs)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short legs of BASELINE configs[1], [3], [4] in the default line")
+                    help="with --full: skip the oracle row-sample too: nothing under oracle/ is loaded, built or spawned (profiler runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the end_to_end / image_check / group_check legs (profiler runs)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short legs of BASELINE configs[1], [3], [4] in the default line")
     ap.add_argument("--group", type=int, default=0, help="N > 0: ONE process, N GPUs behind one context (chunky_group_create); "
                                                          "members share GPU 0 when the box has fewer than N")
     ap.add_argument("--detail", default="", help="where the FULL result object goes (default: bench_detail.json beside this script); stdout "
@@ -603,6 +631,8 @@ def main():
         seeds = native.java_random_ints(max(passes, MERGE_INTERVAL))
         print(json.dumps(group_leg(devices, sc, seeds, passes, golden_rows(golden_name), args.kernel)), flush=True)
         return
+    if not args.full:  # a plain run: the headline alone, none of the legs beyond the timed steps
+        args.no_cpu = args.no_roofline = args.no_extras = args.no_other_configs = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -638,7 +668,7 @@ def main():
     if args.passes > 0:
         passes = args.passes
     n_pix = sc.width * sc.height
-    gold = golden_rows(golden_name)
+    gold = golden_rows(golden_name) if not args.no_extras else None   # (only the image checks read it)
     if gold is None and args.config == 5 and not args.no_extras and not args.no_roofline:
         gold = live_golden(sc)   # (before the GPU is busy: a few seconds of the host's cores)
     group_devices = None
@@ -781,6 +811,8 @@ def main():
                             "read-back (copy + RCCL reduce) incl. waiting for the slowest rank"}
     if rank == 0 and args.dump:
         np.save(args.dump, (r.read() if group_devices else image.cpu().numpy()))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, host_image.numpy(), sc.width, sc.height)
 
     # ---- image check: 4 passes of the same view through the same shards and the same collective, against the reference's rows ----
     image_check = None
@@ -879,9 +911,10 @@ def main():
         if not args.no_roofline:
             roof, cal, rows = roofline_object(sc, args.config, info, launch_ms, launches, samples_per_launch, passes_per_launch, seeds, threads, 36,
                                               args.kernel, attach_pmc=not group_devices, build_oracle=not args.no_cpu)
-        else:
-            roof = {"bound": "hbm", "achieved": 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": 0.0, "traffic": None,
-                    "kernel": kernel_label(info), "launches": launches, "launch_ms": round(launch_ms, 4), "samples_per_launch": samples_per_launch}
+        else:  # --no-roofline, or a plain run (achieved / frac are not computed: None, left out of the line)
+            roof = {"bound": "hbm", "achieved": 0.0 if args.full else None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": 0.0 if args.full else None,
+                    "traffic": None, "kernel": kernel_label(info), "launches": launches, "launch_ms": round(launch_ms, 4),
+                    "samples_per_launch": samples_per_launch}
         group_transport = inst.transport() if group_devices else None
         how = (f"{len(group_devices)} GPU(s) behind one context in one process (chunky_group_create), 16x16-pixel blocks round-robin, "
                f"one exchange per read-back inside the library ({group_transport['name']})"

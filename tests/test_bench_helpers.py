@@ -119,3 +119,25 @@ def test_emit_writes_the_full_object_beside_the_line(tmp_path, capsys):
     d = json.load(open(p))
     assert d["roofline"]["limits"] and d["other_configs"][0]["roofline"]["limits"] and json.loads(lines[0])["detail"] == "d.json"
     assert "full result object" in so.err
+
+
+def test_dump_outputs_writes_the_image_or_a_fixed_sample_of_it(tmp_path):
+    """--dump-outputs: the whole read-back image as float32 [H, W, 3]; an image above the 64 MB budget (3840x2160) gives the same
+    seeded sample of its pixels in every run, with their indices."""
+    small = np.random.default_rng(5).random(3 * 64 * 36, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), small, 64, 36)
+    assert os.listdir(tmp_path / "a") == ["image.npy"]
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and got.shape == (36, 64, 3) and (got.reshape(-1) == small).all()
+    big = np.random.default_rng(6).random(3 * 3840 * 2160, dtype=np.float32)
+    assert big.nbytes > bench.DUMP_LIMIT
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, 3840, 2160)
+    files = ["image_sample.npy", "image_sample_index.npy"]
+    assert sorted(os.listdir(tmp_path / "b")) == files
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= bench.DUMP_LIMIT
+    s, i = (np.load(tmp_path / "b" / f) for f in files)
+    assert s.dtype == np.float32 and s.shape == (bench.DUMP_SAMPLE, 3) and i.dtype == np.float64 and (np.diff(i) > 0).all()
+    assert (s == big.reshape(-1, 3)[i.astype(np.int64)]).all()
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "c" / f), np.load(tmp_path / "b" / f))

@@ -116,6 +116,21 @@ def test_single_rank_through_the_spawn_path(tmp_path, single_rank_image):
     np.testing.assert_array_equal(np.load(dump).view(np.uint32), want.view(np.uint32))
 
 
+def test_plain_run_times_the_steps_and_dumps_what_they_read_back(tmp_path, single_rank_image):
+    """A plain `bench.py --gpus 1` (no --full) times the steps and prints the line: no image check, no end-to-end or other legs,
+    no roofline figure that takes an oracle run.  --dump-outputs writes the image its last timed step read back into host memory."""
+    _sc, want = single_rank_image
+    out = tmp_path / "outputs"
+    line = _run_bench(1, str(tmp_path / "fb_plain.npy"), extra=("--dump-outputs", str(out)), launcher=False)
+    for k in ("image_check", "end_to_end", "other_configs", "cpu_baseline", "group_check", "extension_behind_cull", "extension_emitter_nee"):
+        assert k not in line, k
+    assert line["roofline"]["achieved"] is None and line["roofline"]["frac"] is None and line["roofline"]["launch_ms"] > 0
+    assert sorted(os.listdir(out)) == ["image.npy"]
+    got = np.load(out / "image.npy")
+    assert got.dtype == np.float32 and got.shape == (H, W, 3)
+    np.testing.assert_array_equal(got.reshape(-1).view(np.uint32), want.view(np.uint32))
+
+
 def test_read_back_every_merge_interval(tmp_path, gpu_instance):
     """The reference reads the buffer back every 1024 spp and starts the running mean again (OpenClPathTracingRenderer.java:158-178):
     three steps of 600 passes on two ranks cross the interval once — two read-back reduces in the timed region, and the final
@@ -139,7 +154,7 @@ def test_headline_line_checks_its_own_image(tmp_path):
     """The driver's run, shortened: the headline workload at full size on two ranks (sharing the one GPU), one step.  After the
     timed region bench.py renders 4 passes through the same shards and the same collective and compares whole rows with the
     reference build's (tests/golden/timed_rows.npz): the line carries the verdict."""
-    line = _run_bench(2, str(tmp_path / "fb_full.npy"), small=False)
+    line = _run_bench(2, str(tmp_path / "fb_full.npy"), extra=("--full",), small=False)
     assert line["config"]["baseline_config"] == 2 and line["config"]["passes_per_step"] == 256
     chk = line["image_check"]
     assert chk["bit_identical"] and chk["pixels"] == 16 * 1920 and chk["passes"] == 8 and chk["pixels_differing"] == 0, chk
@@ -154,7 +169,7 @@ def _run_single(args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     with tempfile.TemporaryDirectory() as td:
         detail = os.path.join(td, "detail.json")
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-cpu", "--detail", detail, *args],
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--full", "--no-cpu", "--detail", detail, *args],
                            capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
         assert p.returncode == 0, p.stderr[-3000:]
         return _line_and_detail(p.stdout, detail)

@@ -26,7 +26,7 @@ def test_widetree_under_asan_ubsan(tmp_path):
 def test_capi_host_parsers_under_asan_ubsan(tmp_path):
     """derive_records / build_quad_aux / build_bvh_records / bvh_leaves_sound / list_emitters of capi.hip, compiled for the host only"""
     exe = str(tmp_path / "capi_host_fuzz")
-    cmd = ["hipcc", "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+    cmd = ["hipcc", "-x", "hip", "--offload-host-only", "-fno-gpu-sanitize", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-ffp-contract=off", os.path.join(ROOT, "tests", "sanitize", "capi_host_fuzz.cpp"), os.path.join(native.CSRC, "widetree.cpp"), "-o", exe]
     proc = subprocess.run(cmd, capture_output=True, text=True)
     assert proc.returncode == 0, proc.stderr[-3000:]

@@ -8,10 +8,10 @@ TAG=${1:-prof}
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 python3 -c 'from chunkyclplugin_amd import native; native.build(); native.lib(); from oracle import binding; binding.port()' || exit 1
 export CHUNKY_ORACLE_NO_BUILD=1   # everything is built: nothing below compiles or spawns make (profiled processes must not)
-timeout 400 python3 bench.py --detail $O/bench_detail.json > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c1-200
+timeout 400 python3 bench.py --full --detail $O/bench_detail.json > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c1-200
 timeout 200 python3 tools/phase_stats.py 4 16 > $O/phase_stats_outdoor.json 2>/dev/null
 if [ -z "${ONLY_BENCH:-}" ]; then
-for c in 1 3 4 5; do timeout 600 python3 bench.py --config $c --detail $O/bench_config${c}_detail.json > $O/bench_config$c.json 2> $O/bench_config$c.err; tail -1 $O/bench_config$c.json | cut -c1-200; done
+for c in 1 3 4 5; do timeout 600 python3 bench.py --full --config $c --detail $O/bench_config${c}_detail.json > $O/bench_config$c.json 2> $O/bench_config$c.err; tail -1 $O/bench_config$c.json | cut -c1-200; done
 CHUNKY_STATS_SCENE=entities timeout 300 python3 tools/phase_stats.py 4 8 > $O/phase_stats_entities.json 2>/dev/null
 timeout 1500 python3 tools/config_bench.py benchmark benchmark_entities indoor indoor_nee entities entities4k entities1m > $O/config_bench.jsonl 2> $O/config_bench.err; cut -c1-200 $O/config_bench.jsonl
 fi
