@@ -687,11 +687,13 @@ def add_entities(scene: PackedScene, n_tris: int, seed: int = 11, actor_tris: in
 
 
 def tiny_scene(seed: int = 3, size: int = 16, width: int = 48, height: int = 32,
-               entities: int = 40, sun_flag: bool = True) -> PackedScene:
-    """A small world for unit tests: the outdoor generator at 1 chunk, plus a few entities."""
+               entities: int = 40, sun_flag: bool = True, water: bool = False,
+               atlas_tiles: Tuple[int, int] = (8, 8)) -> PackedScene:
+    """A small world for unit tests: the outdoor generator at 1 chunk, plus a few entities
+    (`water` and `atlas_tiles` as in outdoor_world)."""
     sc = outdoor_world(chunks=max(size // 16, 1), height=size * 2, seed=seed, width=width,
                        img_height=height, sun_flag=sun_flag, aabb_frac=0.10, quad_frac=0.06,
-                       emitters=0.02)
+                       emitters=0.02, atlas_tiles=atlas_tiles, water=water)
     if entities:
         S = float(1 << sc.octree_depth)
         sc = add_entities(sc, entities, seed=seed + 1, actor_tris=entities // 2,

@@ -163,7 +163,9 @@ int chunky_render_set_camera(chunky_render* r, int projector_type, const float* 
 
 typedef enum chunky_option {
     CHUNKY_OPT_DRAW_DEPTH = 0,      /* int, default 256  (K/rayTracer.cl:94) */
-    CHUNKY_OPT_MAX_DEPTH = 1,       /* int >= 1, default 5 (K/rayTracer.cl:107) */
+    CHUNKY_OPT_MAX_DEPTH = 1,       /* int >= 1, default 5 (K/rayTracer.cl:107); above 254 the fallback kernels run (render_pool marks a
+                                     * fresh path with depth 255), which have none of the extensions below: with any of them set,
+                                     * chunky_render_passes then returns CHUNKY_E_STATE before it launches or writes anything */
     CHUNKY_OPT_EMITTER_SCALE = 2,   /* float bits, default 13.0f (K/rayTracer.cl:99) */
     CHUNKY_OPT_KERNEL = 3,          /* int: kernel variant, 0 = default (the pool kernel); bit 0 reference octree layout, bit 1
                                      * one lane per path (render_lanes), bit 2 phase profile (pool kernel), bit 3 the

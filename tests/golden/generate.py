@@ -11,6 +11,7 @@ filter.npz (`python tests/golden/generate.py filter` writes only this one) holds
 kernel (tonemap/include/post_processing_filter.cl, compiled in place the same way): sample values,
 exposures, and the ARGB words for every filter type, plus pow known answers.
 timed_rows.npz (`... generate.py timed`): rows of the five BASELINE views at their timed sizes (write_timed).
+timed_camera_rows.npz (`... generate.py cameras`): rows of the camera / tint / atlas views at the timed sizes (write_cameras).
 helpers.npz (`... generate.py helpers`): known answers of the reference's exported helper functions (write_helpers).
 libm_platform.npz (`... generate.py libm`): images of the reference object on a second platform layer (glibc libm): write_libm.
 """
@@ -73,6 +74,38 @@ def write_timed(ref):
     np.savez_compressed(os.path.join(HERE, "timed_rows.npz"), **out)
 
 
+def write_cameras(ref):
+    """timed_camera_rows.npz: the same as timed_rows.npz for golden_scenes.CAMERA_VIEWS — depth of field, pre-generated rays (a
+    ragged 1917 x 1075 view among them), a camera outside the world, the biome-water tint, textures over four atlas layers, sun
+    draws in the room, the city with depth of field, and pre-generated rays into the entity world — eight rows each
+    (golden_scenes.camera_rows), TIMED_PASSES passes of the java.util.Random(0) seed stream."""
+    seeds = scenes.java_random_ints(gs.TIMED_PASSES)
+    out = {"seeds": seeds}
+    for name in gs.CAMERA_VIEWS:
+        sc = gs.camera_view(name)
+        h = binding.SceneHandle(sc)
+        rows = gs.camera_rows(sc)
+        res = np.zeros((len(rows), sc.width, 3), np.float32)
+        for k, y in enumerate(rows):
+            full = ref.render_passes(h, seeds, gid_range=(y * sc.width, (y + 1) * sc.width), threads=binding.usable_threads())
+            res[k] = full.reshape(-1, 3)[y * sc.width:(y + 1) * sc.width]
+        out[name + "_digest"] = gs.input_digest(sc)
+        out[name + "_rows"] = np.array(rows, np.int32)
+        out[name + "_res"] = res
+        print(name, sc.width, sc.height, "rows", rows, "mean", float(res.mean()), flush=True)
+    savez_lzma(os.path.join(HERE, "timed_camera_rows.npz"), **out)
+
+
+def savez_lzma(path, **arrays):
+    """np.savez_compressed with LZMA instead of deflate (np.load reads either): radiance rows compress about 9 % better, which
+    keeps eight rows of eight 1080p views under the 1 MiB a committed file may take."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for k, v in arrays.items():
+            with z.open(k + ".npy", "w") as f:
+                np.lib.format.write_array(f, np.asanyarray(v), allow_pickle=False)
+
+
 def write_helpers(ref):
     """helpers.npz: answers of the reference object's own exported helpers (oracle/ref_shim.cpp ref_helpers drives them) on the
     input rows of golden_scenes.helper_rows, for the golden scene "entities" (models, textures, sun disc, both BVHs)."""
@@ -132,6 +165,8 @@ def main():
         return write_timed(ref)
     if "helpers" in sys.argv[1:]:
         return write_helpers(ref)
+    if "cameras" in sys.argv[1:]:
+        return write_cameras(ref)
     if "libm" in sys.argv[1:]:
         return write_libm()
     seeds = scenes.java_random_ints(gs.N_PASSES)
@@ -167,6 +202,7 @@ def main():
     print("kats written")
     write_filter(ref)
     write_timed(ref)
+    write_cameras(ref)
     write_helpers(ref)
     write_libm()
 

@@ -11,26 +11,27 @@ W, H = 64, 48
 N_PASSES = 3
 
 
-def _outdoor():
-    return scenes.outdoor_world(chunks=2, height=48, seed=101, width=W, img_height=H, aabb_frac=0.08,
+def _outdoor(chunks=2):
+    return scenes.outdoor_world(chunks=chunks, height=48, seed=101, width=W, img_height=H, aabb_frac=0.08,
                                 quad_frac=0.05, emitters=0.02)
 
 
-def make(name: str) -> scenes.PackedScene:
+def make(name: str, chunks: int = 2) -> scenes.PackedScene:
+    """The golden scene `name`; `chunks` > 2 builds the outdoor ones on a wider world (8 chunks: octree depth 7, DEEP_NAMES)."""
     if name == "outdoor":
-        return _outdoor()
+        return _outdoor(chunks)
     if name == "outdoor_nosun":
-        return dataclasses.replace(_outdoor(), sun=scenes.pack_sun(0.6, 1.2, 1.25, False))
+        return dataclasses.replace(_outdoor(chunks), sun=scenes.pack_sun(0.6, 1.2, 1.25, False))
     if name == "entities":
         sc = _outdoor()
         return scenes.add_entities(sc, 600, seed=5, actor_tris=120, region=((2, 20, 2), (30, 44, 30)))
     if name == "dof":
-        sc = _outdoor()
+        sc = _outdoor(chunks)
         cam = sc.camera.copy()
         cam[12], cam[13] = 0.08, 18.0
         return dataclasses.replace(sc, camera=cam)
     if name == "pregen":
-        sc = _outdoor()
+        sc = _outdoor(chunks)
         rng = np.random.default_rng(9)
         rays = np.zeros((W * H, 6), np.float32)
         rays[:, :3] = sc.camera[:3]
@@ -39,13 +40,13 @@ def make(name: str) -> scenes.PackedScene:
         rays[:, 3:] = d
         return dataclasses.replace(sc, camera=rays.reshape(-1), projector_type=-1)
     if name == "inside":
-        sc = _outdoor()
+        sc = _outdoor(chunks)
         return dataclasses.replace(sc, camera=scenes.look_at_camera((10.3, 9.2, 12.1), (20, 14, 20), 90.0))
     if name == "atlas_layers":   # thirteen textures over four 32x32 atlas layers (quirk B#7: the 19-bit layer mask)
-        return scenes.outdoor_world(chunks=2, height=48, seed=101, width=W, img_height=H, aabb_frac=0.08, quad_frac=0.05,
+        return scenes.outdoor_world(chunks=chunks, height=48, seed=101, width=W, img_height=H, aabb_frac=0.08, quad_frac=0.05,
                                     emitters=0.02, atlas_tiles=(2, 2))
     if name == "water":          # tint type 3 (biome water, K/material.h:61-72) beside types 1, 2 and 0xFF
-        return scenes.outdoor_world(chunks=2, height=48, seed=101, width=W, img_height=H, aabb_frac=0.08, quad_frac=0.05,
+        return scenes.outdoor_world(chunks=chunks, height=48, seed=101, width=W, img_height=H, aabb_frac=0.08, quad_frac=0.05,
                                     emitters=0.02, water=True)
     if name == "indoor":
         return scenes.indoor_room(size=24, seed=7, width=W, img_height=H, emitter_frac=0.03)
@@ -56,6 +57,10 @@ def make(name: str) -> scenes.PackedScene:
 
 
 NAMES = ["outdoor", "outdoor_nosun", "entities", "dof", "pregen", "inside", "indoor", "indoor_sun", "atlas_layers", "water"]
+# every golden world has octree depth 6 (the one-level wide tree, render_pool<16, ...>); make(name, DEEP_CHUNKS) builds these on an
+# 8-chunk world instead — depth 7, a 4-bit dense top over one 3-bit level: render_pool<17, ...>, the form the timed views run
+DEEP_NAMES = ["outdoor_nosun", "dof", "pregen", "inside", "water", "atlas_layers"]
+DEEP_CHUNKS = 8
 RECORD_GIDS = np.arange(0, W * H, 37, dtype=np.int32)
 
 
@@ -97,6 +102,85 @@ def timed_rows(sc: scenes.PackedScene):
     """Sixteen whole rows per view, evenly spread from sky to foreground (30 720 pixels of a 1920-wide view, 61 440 at 3840)."""
     h = sc.height
     return [((2 * k + 1) * h) // 32 for k in range(16)]
+
+
+# ---- other camera kinds, tints and atlas layers at the timed sizes (tests/golden/timed_camera_rows.npz: the reference build's rows) ----
+CAMERA_VIEWS = ["outdoor_dof", "outdoor_pregen", "outdoor_outside", "water", "atlas_layers", "indoor_sun", "city_dof", "entities_pregen"]
+# (tree form, entity-BVH phases, sorted block tests) of the render_pool instantiation launch_pool picks for each view: depth 9 (the
+# outdoor worlds: 6 + 3), 7 (the room: 4 + 3) and 10 (the city: 7 + 3) are all the one-level form; the city's model blocks make it sorted
+CAMERA_KERNEL = {"outdoor_dof": (17, False, False), "outdoor_pregen": (17, False, False), "outdoor_outside": (17, False, False),
+                 "water": (17, False, False), "atlas_layers": (17, False, False), "indoor_sun": (17, False, False),
+                 "city_dof": (17, False, True), "entities_pregen": (17, True, False)}
+ENTITY_REGION = ((40, 90, 40), (470, 170, 470))
+
+
+def with_dof(sc: scenes.PackedScene, aperture: float, subject_distance: float) -> scenes.PackedScene:
+    cam = sc.camera.copy()
+    cam[12], cam[13] = aperture, subject_distance
+    return dataclasses.replace(sc, camera=cam)
+
+
+def pregen_rays(sc: scenes.PackedScene, width: int, height: int, seed: int, aim=None) -> np.ndarray:
+    """width*height*6 floats of a pre-generated camera (projector_type -1, ClCamera.java:72-105) round sc's pinhole camera: origins
+    jittered about its position, one in 16 above the octree (y > 2^depth) and one in 16 at x < 0; directions the pinhole fan plus
+    noise, unnormalised with lengths from 0.05 to 20, some components exactly +0.0 or -0.0.  With `aim` = (lo, hi), two thirds
+    of the rays are aimed at points of that box."""
+    rng = np.random.default_rng(seed)
+    n = width * height
+    cam = np.asarray(sc.camera[:15], np.float64)
+    side = float(1 << int(sc.octree_depth))
+    o = cam[:3] + rng.normal(scale=1.5, size=(n, 3))
+    o[::16, 1] = side + rng.uniform(0.5, 40.0, len(o[::16]))
+    o[5::16, 0] = -rng.uniform(0.5, 30.0, len(o[5::16]))
+    px = np.arange(n) % width
+    py = np.arange(n) // width
+    fov = cam[14]
+    local = np.stack([(px / width - 0.5) * fov * width / height, (py / height - 0.5) * fov, np.ones(n)], axis=1)
+    d = local @ cam[3:12].reshape(3, 3).T + rng.normal(scale=0.05, size=(n, 3))
+    if aim is not None:
+        k = 2 * n // 3
+        idx = rng.permutation(n)[:k]
+        d[idx] = rng.uniform(aim[0], aim[1], (k, 3)) - o[idx]
+    d *= 10.0 ** rng.uniform(-1.3, 1.3, (n, 1))
+    d[::23, 0] = 0.0
+    d[7::29, 2] = -0.0
+    d[11::31, 1] = 0.0
+    d[13::37, 1] = -0.0
+    rays = np.concatenate([o, d], axis=1).astype(np.float32)
+    return rays.reshape(-1)
+
+
+def camera_view(name: str) -> scenes.PackedScene:
+    """The camera kinds (depth of field, pre-generated rays, a camera outside the world), the biome-water tint, textures over
+    several atlas layers and sun draws indoors, on the timed worlds at the timed sizes — the scenes of timed_view with one thing
+    changed, so that they run the instantiations bench.py times (CAMERA_KERNEL)."""
+    if name == "outdoor_dof":
+        return with_dof(timed_view("outdoor"), 0.4, 60.0)
+    if name == "outdoor_pregen":   # ragged: 1917 x 1075 pads the last 16 x 16 tile column and row
+        sc = timed_view("outdoor")
+        return sc.with_view(1917, 1075, camera=pregen_rays(sc, 1917, 1075, seed=31), projector_type=-1)
+    if name == "outdoor_outside":  # outside the 512^3 octree, looking in: the lookups with inside = false
+        sc = timed_view("outdoor")
+        return sc.with_view(sc.width, sc.height, camera=scenes.look_at_camera((-70.0, 560.0, -40.0), (256.0, 90.0, 300.0), 60.0))
+    if name == "water":
+        return scenes.cached_outdoor_world(chunks=32, height=256, water=True)
+    if name == "atlas_layers":
+        return scenes.cached_outdoor_world(chunks=32, height=256, atlas_tiles=(2, 2))
+    if name == "indoor_sun":
+        return dataclasses.replace(timed_view("indoor"), sun=scenes.pack_sun(0.6, 1.2, 1.25, True))
+    if name == "city_dof":
+        return with_dof(timed_view("city"), 0.5, 40.0)
+    if name == "entities_pregen":
+        sc = timed_view("entities")
+        return sc.with_view(sc.width, sc.height, camera=pregen_rays(sc, sc.width, sc.height, seed=37, aim=ENTITY_REGION), projector_type=-1)
+    raise KeyError(name)
+
+
+def camera_rows(sc: scenes.PackedScene):
+    """Eight whole rows, evenly spread from sky to foreground, the last one the image's last (a padded tile row where the height is
+    not a multiple of 16)."""
+    h = sc.height
+    return [((2 * k + 1) * h) // 16 for k in range(7)] + [h - 1]
 
 
 # ---- helper-level known answers (tests/golden/helpers.npz: the reference object's own helpers on these rows) ----

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""tools/fuzz_parity.py [iterations] [first seed] — randomised parity sweep on the GPU box: random small worlds, views, pass
-counts, kernel variants, shards, render-loop constants and (a third of the time) the experimental light-transport options,
+"""tools/fuzz_parity.py [iterations] [first seed] — randomised parity sweep on the GPU box: random small worlds (octree depth 5
+to 7, with or without biome water, textures over one or four atlas layers), views and camera kinds (pinhole, depth of field,
+pre-generated rays), pass counts, kernel variants, shards, render-loop constants and (a third of the time) the experimental light-transport options,
 each rendered through the C ABI and compared with the oracle bit for bit.  Not part of the test suite (it is a search, not a
 check): prints one line per failure and a summary; exit code 1 if anything differed."""
 import dataclasses
@@ -38,16 +39,33 @@ def main():
     bad = 0
     for it in range(n_iter):
         rng = np.random.default_rng(seed0 + it)
-        size = int(rng.choice([16, 32, 48]))
+        size = int(rng.choice([16, 32, 48, 64]))   # octree depth 5, 6, 7, 7: the one-level wide tree (render_pool<16 | 17, ...>) and the generic form
         ents = int(rng.choice([0, 0, 24, 120]))
         w, h = int(rng.integers(5, 90)), int(rng.integers(3, 60))
         if rng.random() < 0.15:  # a few hundred tiles: every XCD range of render_pool's sample queue has work
             w, h = int(rng.integers(150, 400)), int(rng.integers(100, 260))
-        sc = scenes.tiny_scene(seed=int(rng.integers(1, 10 ** 6)), size=size, width=w, height=h, entities=ents, sun_flag=bool(rng.random() < 0.7))
+        water = bool(rng.random() < 0.25)                              # tint type 3
+        atlas = (2, 2) if rng.random() < 0.25 else (8, 8)              # thirteen textures over four atlas layers
+        sc = scenes.tiny_scene(seed=int(rng.integers(1, 10 ** 6)), size=size, width=w, height=h, entities=ents, sun_flag=bool(rng.random() < 0.7),
+                               water=water, atlas_tiles=atlas)
+        S = float(1 << sc.octree_depth)
         if rng.random() < 0.3:   # look from inside / from far outside the world
-            S = float(1 << sc.octree_depth)
             eye = rng.uniform(-0.5 * S, 1.5 * S, 3)
             sc = dataclasses.replace(sc, camera=scenes.look_at_camera(tuple(eye), tuple(rng.uniform(0.2 * S, 0.8 * S, 3)), float(rng.uniform(30, 110))))
+        cam_kind = str(rng.choice(["pinhole", "pinhole", "dof", "pregen"]))
+        if cam_kind == "dof":
+            cam = sc.camera.copy()
+            cam[12], cam[13] = rng.uniform(0.01, 1.5), rng.uniform(0.5, 2 * S)
+            sc = dataclasses.replace(sc, camera=cam)
+        elif cam_kind == "pregen":   # origins about the eye (some outside the world), unnormalised directions with zero components
+            o = sc.camera[:3] + rng.normal(scale=0.1 * S, size=(w * h, 3))
+            o[rng.random(w * h) < 0.1] = rng.uniform(-0.5 * S, 1.5 * S, 3)
+            d = rng.normal(size=(w * h, 3)) * 10.0 ** rng.uniform(-1.5, 1.5, (w * h, 1))
+            d[:, 1] -= np.abs(d[:, 1]) * rng.uniform(0, 1)
+            d[rng.random((w * h, 3)) < 0.05] = 0.0
+            d[rng.random((w * h, 3)) < 0.05] = -0.0
+            d[~d.any(axis=1), 1] = -1.0
+            sc = dataclasses.replace(sc, camera=np.concatenate([o, d], axis=1).astype(np.float32).reshape(-1), projector_type=-1)
         ext = {}
         if rng.random() < 0.33:
             m = np.asarray(sc.material_palette).copy().reshape(-1, 6)
@@ -84,7 +102,7 @@ def main():
         cull = int(ents > 0 and rng.random() < 0.3)
         if os.environ.get("FUZZ_VERBOSE"):
             import time
-            print(f"it={it} view={w}x{h} ents={ents} variant={variant} passes={passes} first={first} draw={draw} depth={depth} shard={rank}/{world}/{tile} "
+            print(f"it={it} view={w}x{h} camera={cam_kind} water={water} atlas={atlas} octree={sc.octree_depth} ents={ents} variant={variant} passes={passes} first={first} draw={draw} depth={depth} shard={rank}/{world}/{tile} "
                   f"group={on_group} ext={ext} layout={layout} cull={cull} t={time.time():.2f}", flush=True)
         loader = HipSceneLoader(groups[on_group] if on_group else inst)
         loader.load_packed(sc)
@@ -111,7 +129,7 @@ def main():
         if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
             bad += 1
             diff = np.nonzero(got.view(np.uint32) != want.view(np.uint32))[0]
-            print(f"FAIL it={it} seed={seed0 + it} size={size} ents={ents} view={w}x{h} variant={variant} passes={passes} first={first} "
+            print(f"FAIL it={it} seed={seed0 + it} size={size} camera={cam_kind} water={water} atlas={atlas} ents={ents} view={w}x{h} variant={variant} passes={passes} first={first} "
                   f"draw={draw} depth={depth} scale={scale} shard={rank}/{world}/{tile} group={on_group} ext={ext} layout={layout} cull={cull} kernel={r.kernel_info()} ndiff={diff.size} first_diff={diff[:4]}", flush=True)
         r.close()
         loader.close()
