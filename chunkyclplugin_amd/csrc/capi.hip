@@ -160,8 +160,21 @@ struct chunky_render {
     std::vector<chunky_render*> parts;
     ShardView outer{0, 1, 0, 0};
     std::vector<DevBuf> gather_send, gather_recv;
+    // the denoiser's auxiliary images (chunky_render_aov_passes): albedo then normal, 3 * width * height floats each, then the
+    // kernel's claim counter; allocated (and zeroed) by the first AOV call.  Timing and the last instantiation are kept apart from
+    // the render kernels' (chunky_render_kernel_time / _kernel_info do not see AOV launches)
+    DevBuf aov;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> aov_pending;
+    float aov_ms = 0;
+    int aov_launches = 0;
+    AovChoice aov_choice{0, 0, 0};
+    int aov_last_launches = 0;  // launches of the most recent chunky_render_aov_passes
     ~chunky_render() {
         for (auto& p : pending) {
+            (void)hipEventDestroy(p.first);
+            (void)hipEventDestroy(p.second);
+        }
+        for (auto& p : aov_pending) {
             (void)hipEventDestroy(p.first);
             (void)hipEventDestroy(p.second);
         }
@@ -201,11 +214,15 @@ static int n_local_slots(int width, int height, const ShardView& t) {
     return mine > 0 ? mine * t.tile : 0;
 }
 
+// bytes of one AOV image (3 floats per pixel)
+static size_t aov_image_bytes(const chunky_render* r) { return (size_t)r->width * r->height * 3 * sizeof(float); }
+
 // ------------------------------------------------------------------------------------ device
 extern "C" const char* chunky_last_error(void) { return tls_error.c_str(); }
 // 0.4: chunky_run_callbacks carries its size (an ABI change), chunky_group_peer_status, CHUNKY_OPT_BVH_CULL_BEHIND
 // 0.5: chunky_group_transport / chunky_group_set_transport (the group's read-back exchange through RCCL, bound at run time)
-extern "C" const char* chunky_version(void) { return "chunky-hip 0.5 gfx950"; }
+// 0.6: albedo and normal images for denoisers: chunky_render_aov_passes / _read / _reset / _kernel_time / _kernel_info
+extern "C" const char* chunky_version(void) { return "chunky-hip 0.6 gfx950"; }
 
 extern "C" int chunky_device_count(void) {
     int n = 0;
@@ -2018,6 +2035,121 @@ extern "C" int chunky_render_trace_records(chunky_render* r, int32_t seed, const
     HIP_TRY(hipMemcpyAsync(counts, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(radiance, dq.p, (size_t)n * 12, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return CHUNKY_OK;
+}
+
+// ------------------------------------------------------------------------------------ AOV (albedo / normal for denoisers)
+// On a group's render target member 0 renders the caller's whole share (as chunky_render_preview does): the images are then the
+// one-context images without an exchange, and every AOV entry point below forwards to member 0.
+static int aov_ensure(chunky_render* r) {
+    if (r->aov.p) return CHUNKY_OK;
+    const size_t bytes = aov_image_bytes(r) * 2 + 256;  // albedo, normal, the claim counter
+    HIP_TRY(hipMalloc(&r->aov.p, bytes));
+    r->aov.bytes = bytes;
+    HIP_TRY(hipMemsetAsync(r->aov.p, 0, bytes, r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+static int collect_aov_timing(chunky_render* r) {
+    for (auto& p : r->aov_pending) {
+        float ms = 0;
+        HIP_TRY(hipEventSynchronize(p.second));
+        HIP_TRY(hipEventElapsedTime(&ms, p.first, p.second));
+        r->aov_ms += ms;
+        r->aov_launches += 1;
+        r->free_events.push_back(p.first);
+        r->free_events.push_back(p.second);
+    }
+    r->aov_pending.clear();
+    return CHUNKY_OK;
+}
+
+// n passes over the pixel slots of shard T (a single-device target: its own share; member 0 of a group: the caller's share)
+static int aov_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n, int first_buffer_spp) {
+    LOCK_RENDER(r);
+    if (!r->have_camera) return fail(CHUNKY_E_STATE, "aov_passes before set_camera");
+    if (!launch_aov) return fail(CHUNKY_E_STATE, "aov_passes: this build has no AOV kernels (aov.hip)");
+    if (int rc = aov_ensure(r)) return rc;
+    r->aov_last_launches = 0;
+    if (n == 0 || T.n_local <= 0) return CHUNKY_OK;
+    SceneView S;
+    if (int rc = scene_view(r->scene, &S)) return rc;
+    S.bvh_cull = r->opts.bvh_cull;
+    if (r->aov_pending.size() > 4096)
+        if (int rc = collect_aov_timing(r)) return rc;
+    float* albedo = (float*)r->aov.p;
+    float* normal = (float*)((char*)r->aov.p + aov_image_bytes(r));
+    int* counter = (int*)((char*)r->aov.p + 2 * aov_image_bytes(r));
+    for (int done = 0; done < n;) {  // launches of at most kMaxPassesPerLaunch: each continues the running mean where the last left it
+        PassSeeds ps;
+        ps.n = (n - done) < kMaxPassesPerLaunch ? (n - done) : kMaxPassesPerLaunch;
+        ps.first_spp = first_buffer_spp + done;
+        memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
+        hipEvent_t e0, e1;
+        HIP_TRY(get_event(r, &e0));
+        HIP_TRY(get_event(r, &e1));
+        HIP_TRY(hipEventRecord(e0, r->ctx->stream));
+        HIP_TRY(launch_aov(r->kernel_variant, S, r->cam, r->opts, T, ps, albedo, normal, counter, r->ctx->stream, &r->aov_choice));
+        HIP_TRY(hipEventRecord(e1, r->ctx->stream));
+        r->aov_pending.emplace_back(e0, e1);
+        r->aov_last_launches += 1;
+        done += ps.n;
+    }
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_aov_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp) {
+    if (n < 0 || (n > 0 && !seeds) || first_buffer_spp < 0) return fail(CHUNKY_E_INVALID, "aov_passes: bad arguments");
+    if (r && !r->parts.empty()) {
+        std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
+        ShardView t = r->outer;  // the caller's share of the image, all of it on member 0
+        t.n_local = n_local_slots(r->width, r->height, t);
+        return aov_passes(r->parts[0], t, seeds, n, first_buffer_spp);
+    }
+    if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
+    std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
+    return aov_passes(r, r->shard, seeds, n, first_buffer_spp);
+}
+
+extern "C" int chunky_render_aov_read(chunky_render* r, int which, float* out, int64_t n) {
+    if (r && !r->parts.empty()) return chunky_render_aov_read(r->parts[0], which, out, n);
+    LOCK_RENDER(r);
+    if (which != CHUNKY_AOV_ALBEDO && which != CHUNKY_AOV_NORMAL) return fail(CHUNKY_E_INVALID, "aov_read: unknown image %d", which);
+    const int64_t need = (int64_t)r->width * r->height * 3;
+    if (!out || n != need) return fail(CHUNKY_E_INVALID, "aov_read: need %lld floats, got %lld", (long long)need, (long long)n);
+    if (!r->aov.p) return fail(CHUNKY_E_STATE, "aov_read before any AOV pass");
+    const char* src = (const char*)r->aov.p + (which == CHUNKY_AOV_NORMAL ? aov_image_bytes(r) : 0);
+    HIP_TRY(hipMemcpyAsync(out, src, (size_t)n * 4, hipMemcpyDeviceToHost, r->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_aov_reset(chunky_render* r) {
+    if (r && !r->parts.empty()) return chunky_render_aov_reset(r->parts[0]);
+    LOCK_RENDER(r);
+    if (r->aov.p) HIP_TRY(hipMemsetAsync(r->aov.p, 0, 2 * aov_image_bytes(r), r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_aov_kernel_time(chunky_render* r, float* total_ms, int* launches) {
+    if (r && !r->parts.empty()) return chunky_render_aov_kernel_time(r->parts[0], total_ms, launches);
+    LOCK_RENDER(r);
+    if (int rc = collect_aov_timing(r)) return rc;
+    if (total_ms) *total_ms = r->aov_ms;
+    if (launches) *launches = r->aov_launches;
+    r->aov_ms = 0;
+    r->aov_launches = 0;
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_aov_kernel_info(chunky_render* r, int32_t out4[4]) {
+    if (r && !r->parts.empty()) return chunky_render_aov_kernel_info(r->parts[0], out4);
+    LOCK_RENDER(r);
+    if (!out4) return fail(CHUNKY_E_INVALID, "aov_kernel_info: NULL output");
+    out4[0] = r->aov_choice.tree;
+    out4[1] = r->aov_choice.bvh;
+    out4[2] = r->aov_choice.blocks;
+    out4[3] = r->aov_last_launches;
     return CHUNKY_OK;
 }
 

@@ -1,5 +1,5 @@
 // kernels.hpp — host-visible launch interface of the kernel translation units (render_pool.hip, render_fallback.hip,
-// aux_kernels.hip, filter.hip).
+// aux_kernels.hip, filter.hip, aov.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -107,6 +107,18 @@ hipError_t launch_trace_records(int variant, const SceneView& S, const CameraVie
                                 hipStream_t stream);
 hipError_t launch_preview(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, int* argb,
                           hipStream_t stream);
+// What launch_aov picked for a launch (chunky_render_aov_kernel_info)
+struct AovChoice {
+    int tree;    // leaf-lookup form, as KernelChoice::tree
+    int bvh;     // entity-BVH walk compiled in
+    int blocks;  // workgroups launched
+};
+// AOV passes (aov.hip): P.n <= kMaxPassesPerLaunch; albedo / normal are 3 * width * height floats each, folded in place over the
+// pixel slots of shard T; `counter` is one int of device memory the launch claims its work from.  Declared weak so that a host-only
+// build of capi.hip without the kernel translation units (tests/sanitize/capi_host_fuzz.cpp) still links; where aov.hip is not
+// linked in, chunky_render_aov_passes fails with CHUNKY_E_STATE instead of calling it.
+__attribute__((weak)) hipError_t launch_aov(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
+                      float* albedo, float* normal, int* counter, hipStream_t stream, AovChoice* chosen);
 // thresholds: 256 floats on the device (capi.hip gamma_thresholds) or null = evaluate pow per channel
 hipError_t launch_filter(long long n_pixels, float exposure, const double* in, unsigned* out, int type, hipStream_t stream,
                          const float* thresholds = nullptr);

@@ -18,7 +18,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("CHUNKY_HIP_LIB") or os.path.join(PKG_DIR, "libchunky_hip.so")  # override: tuning builds (tools/variants.sh)
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
-SOURCES = ["render_pool.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "capi.hip", "widetree.cpp"]
+SOURCES = ["render_pool.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "capi.hip", "widetree.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
 
 MAX_TRACES = 10
@@ -31,6 +31,7 @@ OPT_DRAW_DEPTH, OPT_MAX_DEPTH, OPT_EMITTER_SCALE, OPT_KERNEL, OPT_SUN_SAMPLING, 
 PEER_LOCAL, PEER_DIRECT, PEER_STAGED = 0, 1, 2
 TRANSPORT_PEER_COPY, TRANSPORT_RCCL_SENDRECV, TRANSPORT_RCCL_REDUCE = 0, 1, 2
 E_INVALID, E_NO_DEVICE, E_HIP, E_STATE, E_ABORTED = -1, -2, -3, -4, -5
+AOV_ALBEDO, AOV_NORMAL = 0, 1  # chunky_render_aov_read
 
 
 class ChunkyHipError(RuntimeError):
@@ -176,6 +177,11 @@ def lib() -> C.CDLL:
             "chunky_render_phase_stats": [vp, vp, C.c_int],
             "chunky_render_kernel_info": [vp, vp],
             "chunky_render_trace_records": [vp, i32, vp, C.c_int, vp, vp, vp],
+            "chunky_render_aov_passes": [vp, vp, C.c_int, C.c_int],
+            "chunky_render_aov_read": [vp, C.c_int, vp, i64],
+            "chunky_render_aov_reset": [vp],
+            "chunky_render_aov_kernel_time": [vp, C.POINTER(f32), C.POINTER(C.c_int)],
+            "chunky_render_aov_kernel_info": [vp, vp],
             "chunky_render_run": [vp, vp, C.POINTER(i32), i32, i32, POST_RENDER_FN, vp],
             "chunky_render_run_ex": [vp, vp, C.POINTER(i32), i32, i32, C.POINTER(RunCallbacks)],
             "chunky_java_random_ints": [i64, vp, C.c_int],

@@ -288,6 +288,36 @@ class HipPathTracingRenderer:
         check(native.lib().chunky_render_trace_records(self._h, int(seed), ptr(g), g.size, ptr(rec), ptr(cnt), ptr(rad)))
         return rec, cnt, rad
 
+    # --- auxiliary images for a denoiser (chunky_render_aov_*) ---------------------------------------
+    def render_aov(self, seeds, first_buffer_spp: int = 0, sync: bool = True) -> None:
+        """Albedo and normal passes: pass k uses seeds[k] and bufferSpp first_buffer_spp + k, like render_passes, and traces the
+        first ray of that render pass only."""
+        s = np.ascontiguousarray(seeds, np.int32)
+        check(native.lib().chunky_render_aov_passes(self._h, ptr(s), s.size, first_buffer_spp))
+        if sync:
+            self.sync()
+
+    def read_aov(self, which: int) -> np.ndarray:
+        """One AOV image (native.AOV_ALBEDO or native.AOV_NORMAL) as a (height, width, 3) float32 array."""
+        out = np.empty((self.height, self.width, 3), np.float32)
+        check(native.lib().chunky_render_aov_read(self._h, int(which), ptr(out), out.size))
+        return out
+
+    def reset_aov(self) -> None:
+        check(native.lib().chunky_render_aov_reset(self._h))
+
+    def aov_kernel_time(self):
+        """(milliseconds, launches) of the AOV kernel since the last call."""
+        ms, n = C.c_float(), C.c_int()
+        check(native.lib().chunky_render_aov_kernel_time(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def aov_info(self) -> dict:
+        """The AOV instantiation the last AOV launch ran: tree form, entity-BVH walk, workgroups, launches of the last call."""
+        out = np.zeros(4, np.int32)
+        check(native.lib().chunky_render_aov_kernel_info(self._h, ptr(out)))
+        return {"tree": int(out[0]), "bvh": bool(out[1]), "blocks": int(out[2]), "launches": int(out[3])}
+
     def render(self, sample_buffer: np.ndarray, scene_spp: int, target_spp: int, merge_interval: int = 1024) -> int:
         """The pass loop of OpenClPathTracingRenderer.render (:95-184) run natively; merges into the
         caller's double sample buffer and returns the new scene.spp."""

@@ -268,6 +268,38 @@ int chunky_render_trace_records(chunky_render* r, int32_t seed, const int32_t* g
                                 chunky_hit_record* records /* n*CHUNKY_MAX_TRACES */, int32_t* counts /* n */,
                                 float* radiance /* 3n */);
 
+/* ---- auxiliary images for an external denoiser (no reference counterpart: Chunky's denoiser plugin traces them again on the
+ * CPU for Open Image Denoise).  The albedo and the normal of the first surface each camera ray hits, averaged over passes.
+ * Pass k of a call uses seeds[k] and bufferSpp first_buffer_spp + k exactly like chunky_render_passes; its sample at pixel gid
+ * is the FIRST trace of that reference pass: RNG state seed + gid, Random_nextState, the camera ray (K/rayTracer.cl:55-91), one
+ * closestIntersect with the target's draw depth and CHUNKY_OPT_BVH_CULL_BEHIND (K/kernel.h:14-24).  A hit gives albedo =
+ * record.color.xyz before applyRayColor and normal = record.normal; a miss gives albedo = the sky colour of intersectSky with
+ * record.emittance = 1 (the radiance of a reference sample whose first trace misses, K/rayTracer.cl:94-97) and normal = (0, 0, 0).
+ * Each channel is folded in float, in pass order, with the running mean of K/rayTracer.cl:109-112.  So AOV pass k sees the camera
+ * ray render pass k sees with the same seed: a host that passes the seeds of its first N render passes gets images that line up
+ * with its beauty samples.  The other light-transport options and CHUNKY_OPT_MAX_DEPTH do not touch the first trace and are ignored.
+ * The two images are allocated, zeroed, by the first AOV call on a target; chunky_render_reset / _read / _kernel_time /
+ * _kernel_info never see them, nor AOV launches.  A set shard (chunky_render_set_shard) limits the passes to the rank's pixels; the
+ * others stay 0.  On a group's render target member 0 renders the caller's whole share (as chunky_render_preview does): the
+ * images are the one-context images, with no exchange. */
+#define CHUNKY_AOV_ALBEDO 0
+#define CHUNKY_AOV_NORMAL 1
+/* Enqueue n AOV passes (asynchronous, like chunky_render_passes; longer requests are cut into launches of at most 256 passes,
+ * which changes no bit).  CHUNKY_E_STATE before chunky_render_set_camera. */
+int chunky_render_aov_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp);
+/* Blocking read-back of one image (which = CHUNKY_AOV_ALBEDO or CHUNKY_AOV_NORMAL), 3*width*height floats, like
+ * chunky_render_read.  CHUNKY_E_STATE before any AOV pass. */
+int chunky_render_aov_read(chunky_render* r, int which, float* out, int64_t n_floats);
+/* Zero both images (chunky_render_reset for the AOV). */
+int chunky_render_aov_reset(chunky_render* r);
+/* Device time of the AOV launches enqueued since the last call, from HIP events on the stream they run on (as
+ * chunky_render_kernel_time). */
+int chunky_render_aov_kernel_time(chunky_render* r, float* total_ms, int* launches);
+/* The AOV instantiation the most recent launch ran (as chunky_render_kernel_info): out4 = {tree form (0 reference octree layout,
+ * -1 generic wide tree, 16 + n dense top node over n levels: the form render_pool runs for the scene), entity-BVH walk present,
+ * workgroups launched, launches made by the most recent chunky_render_aov_passes}. */
+int chunky_render_aov_kernel_info(chunky_render* r, int32_t out4[4]);
+
 /* ---- host pass loop (replaces OpenClPathTracingRenderer.render, J/opencl/OpenClPathTracingRenderer.java:54-191):
  * seeds from java.util.Random(0).nextInt(), bufferSpp restarting at 0 after each read-back, merge
  * sample = (sample*sampSpp + pass*passSpp) / (sampSpp+passSpp) in double (:167-173).
