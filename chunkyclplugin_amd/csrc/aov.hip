@@ -56,8 +56,9 @@ DEV AovArgPtr aov_args() {
     return a;
 }
 
-// Five waves per SIMD (at most 96 VGPRs) without the BVH walk; with it, four (at five it would spill to scratch).
-template <int TREE, bool BVH>
+// Five waves per SIMD (at most 96 VGPRs) without the BVH walk; with it, four (at five it would spill to scratch).  PROJ: a projected
+// camera (projector types 1-5, rt_device.hpp projected_ray), instantiated apart so that the other cameras keep their code.
+template <int TREE, bool BVH, bool PROJ = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BVH ? 4 : 5))) aov_kernel(AovArgs) {
     extern __shared__ int lds[];
     LdsStack stack{lds + threadIdx.x, (int)blockDim.x};
@@ -79,9 +80,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BVH ? 
             const int n_passes = a->P.n, first_spp = a->P.first_spp;
             for (int k = 0; k < n_passes; k++) {
                 AovArgPtr b = aov_args();
-                unsigned rng = (unsigned)b->P.seed[k] + (unsigned)gid;  // K/rayTracer.cl:54-56
+                const unsigned seed = (unsigned)b->P.seed[k];
+                unsigned rng = seed + (unsigned)gid;  // K/rayTracer.cl:54-56
                 rt_pcg_next(&rng);
-                const RayOD r = primary_ray(arg_copy(&b->C), gid, rng, false, px, py);
+                const RayOD r = primary_ray<PROJ>(arg_copy(&b->C), seed, gid, rng, false, px, py);
                 Hit h;
                 h.distance = rt_inf();
                 h.material = 0;
@@ -123,31 +125,35 @@ static int aov_tree(int variant, const SceneView& S, bool bvh) {
     return (tree >= 16 && tree <= 19) ? tree : -1;
 }
 
+// the instantiation for the tree form and the camera
+template <bool PROJ>
+static void (*aov_instance(int tree, bool bvh))(AovArgs) {
+    if (bvh) {
+        switch (tree) {
+            case 0: return aov_kernel<0, true, PROJ>;
+            case 17: return aov_kernel<17, true, PROJ>;
+            case 18: return aov_kernel<18, true, PROJ>;
+            default: return aov_kernel<-1, true, PROJ>;
+        }
+    } else {
+        switch (tree) {
+            case 0: return aov_kernel<0, false, PROJ>;
+            case 16: return aov_kernel<16, false, PROJ>;
+            case 17: return aov_kernel<17, false, PROJ>;
+            case 18: return aov_kernel<18, false, PROJ>;
+            case 19: return aov_kernel<19, false, PROJ>;
+            default: return aov_kernel<-1, false, PROJ>;
+        }
+    }
+}
+
 hipError_t launch_aov(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
                       float* albedo, float* normal, int* counter, hipStream_t stream, AovChoice* chosen) {
     if (P.n <= 0 || T.n_local <= 0) return hipSuccess;
     if (P.n > kMaxPassesPerLaunch) return hipErrorInvalidValue;
     const bool bvh = !S.world_bvh_empty || !S.actor_bvh_empty;
     const int tree = aov_tree(variant, S, bvh);
-    typedef void (*Kernel)(AovArgs);
-    Kernel k;
-    if (bvh) {
-        switch (tree) {
-            case 0: k = aov_kernel<0, true>; break;
-            case 17: k = aov_kernel<17, true>; break;
-            case 18: k = aov_kernel<18, true>; break;
-            default: k = aov_kernel<-1, true>; break;
-        }
-    } else {
-        switch (tree) {
-            case 0: k = aov_kernel<0, false>; break;
-            case 16: k = aov_kernel<16, false>; break;
-            case 17: k = aov_kernel<17, false>; break;
-            case 18: k = aov_kernel<18, false>; break;
-            case 19: k = aov_kernel<19, false>; break;
-            default: k = aov_kernel<-1, false>; break;
-        }
-    }
+    void (*k)(AovArgs) = C.projector_type > 0 ? aov_instance<true>(tree, bvh) : aov_instance<false>(tree, bvh);
     const int block = 256;
     const size_t lds = stack_lds_bytes(S, block);
     int n_cu = 0, occ = 0;

@@ -43,7 +43,7 @@ __global__ void __launch_bounds__(256) preview_lanes(SceneView S, CameraView C, 
     }
     unsigned rng = 0;
     rt_pcg_next(&rng);
-    const RayOD pr = primary_ray(C, gid, rng, true);
+    const RayOD pr = primary_ray_any(C, 0u, gid, rng, true);  // a projected camera: the rays of seed 0
     const f3 o = pr.o, d = pr.d;
     Hit h;
     h.distance = rt_inf();
@@ -255,6 +255,23 @@ hipError_t launch_preview(int variant, const SceneView& S, const CameraView& C, 
         hipLaunchKernelGGL(preview_lanes<-1>, dim3(grid), dim3(block), stack_lds_bytes(S, block), stream, S, C, O, argb);
     else
         hipLaunchKernelGGL(preview_lanes<0>, dim3(grid), dim3(block), stack_lds_bytes(S, block), stream, S, C, O, argb);
+    return hipGetLastError();
+}
+
+// chunky_selftest_camera_rays: the projected camera's ray of every pixel for one seed, as the render kernels compute it, in the
+// layout of the pre-generated table (origin, direction; K/camera.h:8-11)
+__global__ void __launch_bounds__(256) camera_rays_kernel(CameraView C, unsigned seed, float* __restrict__ out) {
+    const int gid = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (gid >= C.width * C.height) return;
+    const RayOD r = projected_ray(C, seed, gid, gid % C.width, gid / C.width);
+    float* o = out + 6 * (size_t)gid;
+    o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z;
+    o[3] = r.d.x; o[4] = r.d.y; o[5] = r.d.z;
+}
+hipError_t launch_camera_rays_selftest(const CameraView& C, int seed, float* out, hipStream_t stream) {
+    const long long n = (long long)C.width * C.height;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(camera_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, C, (unsigned)seed, out);
     return hipGetLastError();
 }
 

@@ -222,6 +222,8 @@ extern "C" const char* chunky_last_error(void) { return tls_error.c_str(); }
 // 0.4: chunky_run_callbacks carries its size (an ABI change), chunky_group_peer_status, CHUNKY_OPT_BVH_CULL_BEHIND
 // 0.5: chunky_group_transport / chunky_group_set_transport (the group's read-back exchange through RCCL, bound at run time)
 // 0.6: albedo and normal images for denoisers: chunky_render_aov_passes / _read / _reset / _kernel_time / _kernel_info
+//      also: projected cameras (CHUNKY_PROJ_PARALLEL .. CHUNKY_PROJ_STEREOGRAPHIC), chunky_camera_rays, chunky_selftest_camera_rays
+//      (additions only, so the version string stays "0.6": hosts that check it for the AOV calls keep working)
 extern "C" const char* chunky_version(void) { return "chunky-hip 0.6 gfx950"; }
 
 extern "C" int chunky_device_count(void) {
@@ -1474,6 +1476,40 @@ extern "C" int chunky_render_destroy(chunky_render* r) {
     return CHUNKY_OK;
 }
 
+// projected cameras (types 1-5, camera_proj.h): 15 floats laid out as the pinhole camera's, all finite, no aperture (depth of field
+// stays pinhole-only), settings[14] > 0, and settings[13] = 0 where the type has no use for it
+static_assert(RT_PROJ_PARALLEL == CHUNKY_PROJ_PARALLEL && RT_PROJ_FISHEYE == CHUNKY_PROJ_FISHEYE && RT_PROJ_PANORAMIC == CHUNKY_PROJ_PANORAMIC &&
+                  RT_PROJ_PANORAMIC_SLOT == CHUNKY_PROJ_PANORAMIC_SLOT && RT_PROJ_STEREOGRAPHIC == CHUNKY_PROJ_STEREOGRAPHIC, "camera_proj.h");
+static int check_projected(const char* who, int type, const float* s, int64_t n) {
+    if (type < CHUNKY_PROJ_PARALLEL || type > CHUNKY_PROJ_STEREOGRAPHIC)
+        return fail(CHUNKY_E_INVALID, "%s: projector type %d is not a projected camera (1-5)", who, type);
+    if (!s) return fail(CHUNKY_E_INVALID, "%s: NULL settings", who);
+    if (n != 15) return fail(CHUNKY_E_INVALID, "%s: projector type %d needs 15 floats, got %lld", who, type, (long long)n);
+    for (int i = 0; i < 15; i++)
+        if (!std::isfinite(s[i])) return fail(CHUNKY_E_INVALID, "%s: settings[%d] is not finite", who, i);
+    if (s[12] != 0.0f) return fail(CHUNKY_E_INVALID, "%s: projector type %d takes no aperture (depth of field is pinhole-only)", who, type);
+    if (!(s[14] > 0.0f)) return fail(CHUNKY_E_INVALID, "%s: settings[14] must be > 0, got %g", who, (double)s[14]);
+    if (s[13] != 0.0f && (type == CHUNKY_PROJ_FISHEYE || type == CHUNKY_PROJ_PANORAMIC || type == CHUNKY_PROJ_STEREOGRAPHIC))
+        return fail(CHUNKY_E_INVALID, "%s: settings[13] must be 0 for projector type %d", who, type);
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_camera_rays(int projector_type, const float* settings, int64_t n_floats, int width, int height, int32_t seed, float* out) {
+    if (int rc = check_projected("camera_rays", projector_type, settings, n_floats)) return rc;
+    if (width <= 0 || height <= 0 || (int64_t)width * height > INT32_MAX / 6)
+        return fail(CHUNKY_E_INVALID, "camera_rays: bad size %dx%d", width, height);
+    if (!out) return fail(CHUNKY_E_INVALID, "camera_rays: NULL output");
+    const float half_width = (float)(width / (2.0 * height)), inv_height = (float)(1.0 / height);  // as set_camera
+    for (int gid = 0; gid < width * height; gid++) {
+        const RtRay r = rt_projected_ray(projector_type, settings, settings + 3, settings[13], settings[14], half_width, inv_height,
+                                         gid % width, gid / width, (unsigned)seed, gid);
+        float* o = out + 6 * (size_t)gid;
+        o[0] = r.ox; o[1] = r.oy; o[2] = r.oz;
+        o[3] = r.dx; o[4] = r.dy; o[5] = r.dz;
+    }
+    return CHUNKY_OK;
+}
+
 extern "C" int chunky_render_set_camera(chunky_render* r, int projector_type, const float* settings, int64_t n) {
     FAN_RENDER(r, chunky_render_set_camera(m_, projector_type, settings, n));
     LOCK_RENDER(r);
@@ -1497,8 +1533,16 @@ extern "C" int chunky_render_set_camera(chunky_render* r, int projector_type, co
         HIP_TRY(hipStreamSynchronize(r->ctx->stream));  // rays may still be read by queued passes
         HIP_TRY(r->rays.upload(settings, (size_t)n * 4, r->ctx->stream));
         c.rays = (const float*)r->rays.p;
+    } else if (projector_type >= CHUNKY_PROJ_PARALLEL && projector_type <= CHUNKY_PROJ_STEREOGRAPHIC) {
+        if (int rc = check_projected("set_camera", projector_type, settings, n)) return rc;
+        memcpy(c.pos, settings, 12);
+        memcpy(c.m, settings + 3, 36);
+        c.aperture = 0.0f;
+        c.subject_distance = settings[13];  // (CameraView: settings[13] / [14] of a projected camera)
+        c.fov_tan = settings[14];
+        c.rays = nullptr;
     } else {
-        return fail(CHUNKY_E_INVALID, "set_camera: projector type %d is not supported (0 or -1)", projector_type);
+        return fail(CHUNKY_E_INVALID, "set_camera: projector type %d is not supported (-1 to 5)", projector_type);
     }
     c.projector_type = projector_type;
     r->have_camera = true;
@@ -2432,6 +2476,21 @@ extern "C" int chunky_selftest_math(chunky_ctx* ctx, int which, int n, const flo
     HIP_TRY(launch_math_selftest(which, n, (const float*)da.p, (const float*)db.p, (float*)dout.p, ctx->stream));
     HIP_TRY(hipMemcpyAsync(out, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_selftest_camera_rays(chunky_render* r, int32_t seed, float* out, int64_t n_floats) {
+    if (r && !r->parts.empty()) return chunky_selftest_camera_rays(r->parts[0], seed, out, n_floats);
+    LOCK_RENDER(r);
+    if (!r->have_camera || r->cam.projector_type <= 0) return fail(CHUNKY_E_STATE, "selftest_camera_rays: the target has no projected camera");
+    const int64_t need = (int64_t)r->width * r->height * 6;
+    if (!out || n_floats != need) return fail(CHUNKY_E_INVALID, "selftest_camera_rays: need %lld floats, got %lld", (long long)need, (long long)n_floats);
+    if (!launch_camera_rays_selftest) return fail(CHUNKY_E_STATE, "selftest_camera_rays: this build has no camera kernel (aux_kernels.hip)");
+    DevBuf dout;
+    HIP_TRY(hipMalloc(&dout.p, (size_t)need * 4));
+    HIP_TRY(launch_camera_rays_selftest(r->cam, seed, (float*)dout.p, r->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, dout.p, (size_t)need * 4, hipMemcpyDeviceToHost, r->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
     return CHUNKY_OK;
 }
 

@@ -129,5 +129,8 @@ hipError_t launch_gamma_scan(unsigned first, unsigned long long count, int curve
 // helper-level known answers (aux_kernels.hip helpers_selftest_kernel): rows of 32 floats in, 12 out
 hipError_t launch_helpers_selftest(const SceneView& S, int which, int tree, int n, const float* in, float* out, int* tree_used, hipStream_t stream);
 hipError_t launch_math_selftest(int which, int n, const float* a, const float* b, float* out, hipStream_t stream);
+// projected camera self test (aux_kernels.hip camera_rays_kernel): width * height * 6 floats, origin then direction per pixel.
+// Weak for the same reason as launch_aov: where it is not linked in, chunky_selftest_camera_rays fails with CHUNKY_E_STATE.
+__attribute__((weak)) hipError_t launch_camera_rays_selftest(const CameraView& C, int seed, float* out, hipStream_t stream);
 
 }  // namespace chunky

@@ -154,7 +154,7 @@ DEV f3 sample_path(const SceneView& S, const CameraView& C, const RenderOpts& O,
                    HitRecord* rec_out, int* rec_n) {
     unsigned rng = (unsigned)seed + (unsigned)gid;
     rt_pcg_next(&rng);
-    const RayOD pr = primary_ray(C, gid, rng, false);
+    const RayOD pr = primary_ray_any(C, (unsigned)seed, gid, rng, false);
     f3 o = pr.o, d = pr.d;
     f3 radiance = mk3(0, 0, 0), throughput = mk3(1, 1, 1);
     Hit h;

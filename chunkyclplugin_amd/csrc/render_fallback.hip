@@ -228,9 +228,10 @@ DEV int next_sample_single(const SceneView& S, const CameraView& C, const ShardV
     // ---- new sample (K/rayTracer.cl:55-91) ----
     {
         // locals, not struct members, as out-parameters: keeps LaneState promotable to registers
-        unsigned rng = (unsigned)A->P.seed[L.pass] + (unsigned)L.gid;  // per-lane index: a vector load from the argument segment
+        const unsigned seed = (unsigned)A->P.seed[L.pass];  // per-lane index: a vector load from the argument segment
+        unsigned rng = seed + (unsigned)L.gid;
         rt_pcg_next(&rng);
-        const RayOD pr = primary_ray(C, L.gid, rng, false);
+        const RayOD pr = primary_ray_any(C, seed, L.gid, rng, false);
         L.rng = rng;
         L.o = pr.o;
         L.d = pr.d;
@@ -366,9 +367,10 @@ DEV int next_sample(const SceneView& S, const CameraView& C, const ShardView& T,
     // ---- new sample (K/rayTracer.cl:55-91) ----
     {
         // locals, not struct members, as out-parameters: keeps LaneState promotable to registers
-        unsigned rng = (unsigned)A->P.seed[L.pass] + (unsigned)gid;  // per-lane index: a vector load from the argument segment
+        const unsigned seed = (unsigned)A->P.seed[L.pass];  // per-lane index: a vector load from the argument segment
+        unsigned rng = seed + (unsigned)gid;
         rt_pcg_next(&rng);
-        const RayOD pr = primary_ray(C, gid, rng, false);
+        const RayOD pr = primary_ray_any(C, seed, gid, rng, false);
         L.rng = rng;
         L.o = pr.o;
         L.d = pr.d;

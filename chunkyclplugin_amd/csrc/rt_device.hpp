@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "rt_math.h"
+#include "camera_proj.h"
 
 namespace chunky {
 
@@ -107,9 +108,9 @@ struct SceneView {
 
 struct CameraView {
     const float* __restrict__ rays;  // projector -1: W*H*6 floats (K/camera.h:8-11)
-    int projector_type;
+    int projector_type;              // 0 pinhole, -1 pre-generated, 1-5 projected (camera_proj.h)
     float pos[3], m[9];              // ClCamera.java:42-52
-    float aperture, subject_distance, fov_tan;
+    float aperture, subject_distance, fov_tan;  // settings[12..14] (projected types: 0, settings[13], settings[14])
     int width, height;
     float half_width, inv_height;    // K/rayTracer.cl:66-67 (double sites, rounded once on the host)
 };
@@ -726,8 +727,27 @@ DEV RayOD primary_ray(const CameraView& C, int gid, unsigned& rng, bool unit_dir
     }
     return RayOD{mk3(ox, oy, oz), mk3(dx, dy, dz)};
 }
-DEV RayOD primary_ray(const CameraView& C, int gid, unsigned& rng, bool unit_dir) {
-    return primary_ray(C, gid, rng, unit_dir, gid % C.width, gid / C.width);
+
+// Projected cameras (projector types 1-5, camera_proj.h): the ray from the pass seed's own jitter stream.
+// It draws nothing from the path's state and does not take the preview's extra normalize (the projection normalises already,
+// and the reference preview does not normalise pre-generated rays).  settings[13] / [14] travel in subject_distance / fov_tan.
+DEV RayOD projected_ray(const CameraView& C, unsigned seed, int gid, int px, int py) {
+    const RtRay r = rt_projected_ray(C.projector_type, C.pos, C.m, C.subject_distance, C.fov_tan, C.half_width, C.inv_height, px, py,
+                                     seed, gid);
+    return RayOD{mk3(r.ox, r.oy, r.oz), mk3(r.dx, r.dy, r.dz)};
+}
+// PROJ: a compile-time choice of the kernels whose registers are budgeted (render_pool, aov_kernel): their pinhole / pre-generated
+// instantiations compile exactly the code above
+template <bool PROJ>
+DEV RayOD primary_ray(const CameraView& C, unsigned seed, int gid, unsigned& rng, bool unit_dir, int px, int py) {
+    if (PROJ) return projected_ray(C, seed, gid, px, py);
+    return primary_ray(C, gid, rng, unit_dir, px, py);
+}
+// the other kernels (fallbacks, preview, trace records): a uniform branch on the projector type
+DEV RayOD primary_ray_any(const CameraView& C, unsigned seed, int gid, unsigned& rng, bool unit_dir) {
+    const int px = gid % C.width, py = gid / C.width;
+    if (C.projector_type > 0) return projected_ray(C, seed, gid, px, py);
+    return primary_ray(C, gid, rng, unit_dir, px, py);
 }
 
 }  // namespace chunky

@@ -32,6 +32,8 @@ PEER_LOCAL, PEER_DIRECT, PEER_STAGED = 0, 1, 2
 TRANSPORT_PEER_COPY, TRANSPORT_RCCL_SENDRECV, TRANSPORT_RCCL_REDUCE = 0, 1, 2
 E_INVALID, E_NO_DEVICE, E_HIP, E_STATE, E_ABORTED = -1, -2, -3, -4, -5
 AOV_ALBEDO, AOV_NORMAL = 0, 1  # chunky_render_aov_read
+PROJ_PREGENERATED, PROJ_PINHOLE = -1, 0  # chunky_render_set_camera: the reference's two projector types
+PROJ_PARALLEL, PROJ_FISHEYE, PROJ_PANORAMIC, PROJ_PANORAMIC_SLOT, PROJ_STEREOGRAPHIC = 1, 2, 3, 4, 5  # CHUNKY_PROJ_* (projected cameras)
 
 
 class ChunkyHipError(RuntimeError):
@@ -188,6 +190,8 @@ def lib() -> C.CDLL:
             "chunky_selftest_math": [vp, C.c_int, C.c_int, vp, vp, vp],
             "chunky_selftest_helpers": [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(i32)],
             "chunky_selftest_gamma_scan": [vp, C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(f32)],
+            "chunky_selftest_camera_rays": [vp, i32, vp, i64],
+            "chunky_camera_rays": [C.c_int, vp, i64, C.c_int, C.c_int, i32, vp],
             "chunky_filter_frame": [vp, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int],
             "chunky_filter_gamma_thresholds": [vp],
             "chunky_filter_frame_device": [vp, i64, f32, vp, vp, C.c_int, C.c_int, C.POINTER(f32)],
@@ -213,6 +217,15 @@ def ptr(a: np.ndarray) -> int:
 def java_random_ints(n: int, seed: int = 0) -> np.ndarray:
     out = np.zeros(n, np.int32)
     check(lib().chunky_java_random_ints(seed, ptr(out), n))
+    return out
+
+
+def camera_rays(projector_type: int, settings, width: int, height: int, seed: int) -> np.ndarray:
+    """chunky_camera_rays: the width*height*6-float table (projector type -1) of a projected camera for the pass of `seed`,
+    computed on the host with the kernels' arithmetic (no device needed)."""
+    s = np.ascontiguousarray(settings, np.float32)
+    out = np.zeros(int(width) * int(height) * 6, np.float32)
+    check(lib().chunky_camera_rays(int(projector_type), ptr(s), s.size, int(width), int(height), int(np.int32(np.uint32(seed & 0xFFFFFFFF))), ptr(out)))
     return out
 
 

@@ -335,6 +335,41 @@ def camera_from_json(cam: dict, origin=(0.0, 0.0, 0.0)) -> np.ndarray:
     return np.concatenate([p, M.reshape(-1), [aperture, subject, fov_tan]]).astype(np.float32)
 
 
+# Chunky's ProjectionMode (scene JSON camera.projectionMode) -> the projected camera types of chunky_render_set_camera
+PROJECTION_TYPES = {"PARALLEL": 1, "FISHEYE": 2, "PANORAMIC": 3, "PANORAMIC_SLOT": 4, "STEREOGRAPHIC": 5}
+
+
+def camera_settings(cam: dict, origin=(0.0, 0.0, 0.0), world_width: float = 0.0):
+    """(projector_type, settings) for chunky_render_set_camera from Chunky's scene JSON camera block.  PINHOLE (or no
+    projectionMode) is type 0 with camera_from_json's 15 floats; PARALLEL, FISHEYE, PANORAMIC, PANORAMIC_SLOT and STEREOGRAPHIC
+    are the projected types 1-5 (include/chunky_hip.h), which the kernels generate from the pass seed.  Anything else — the ODS
+    modes, or depth of field on a non-pinhole mode — is (-1, None): the host builds a ray table for it as before.  How Chunky's
+    fov maps to settings[13] / [14] is this project's reading of its projectors: the parallel view is `fov` world units per unit
+    of y, backed off by `world_width`; the fisheye and both panoramas take the fov in degrees; the stereographic scale is
+    2 tan(fov / 4), so that the image's top and bottom edges lie fov / 2 off the axis."""
+    mode = str(cam.get("projectionMode", "PINHOLE")).upper()
+    base = camera_from_json(cam, origin)
+    if mode == "PINHOLE":
+        return 0, base
+    kind = PROJECTION_TYPES.get(mode)
+    if kind is None or float(base[12]) != 0.0:
+        return -1, None
+    fov = float(cam.get("fov", 70.0))
+    if kind == 1:
+        s13, s14 = float(world_width), fov
+    elif kind == 4:
+        s13, s14 = float(base[14]), fov
+    elif kind == 5:
+        s13, s14 = 0.0, 2.0 * math.tan(math.radians(fov) / 4.0)
+    else:
+        s13, s14 = 0.0, fov
+    if not (math.isfinite(s14) and s14 > 0.0):
+        return -1, None
+    settings = base.copy()
+    settings[12], settings[13], settings[14] = 0.0, s13, s14
+    return kind, settings
+
+
 def load_scene(octree2_path: str, json_path: str = None, width: int = 1920, height: int = 1080,
                emitters: bool = False) -> scenes.PackedScene:
     """`.octree2` (+ scene JSON for camera / sun) -> PackedScene through the procedural asset pack (`asset_pack`: model classes

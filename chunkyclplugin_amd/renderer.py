@@ -27,6 +27,12 @@ from . import native
 from .native import check, ptr
 
 
+def camera_rays(projector_type: int, settings, width: int, height: int, seed: int) -> np.ndarray:
+    """The projector type -1 table equivalent to a projected camera (types 1-5) in the pass of `seed`: feeding it to
+    set_camera(-1, ...) renders that pass bit for bit (include/chunky_hip.h chunky_camera_rays).  Host only."""
+    return native.camera_rays(projector_type, settings, width, height, seed)
+
+
 class RendererInstance:
     """One GPU context per device index (the reference keeps a singleton for its one cl_device,
     RendererInstance.java:23-28; `clDevice` index from PersistentSettings :33)."""
@@ -207,6 +213,13 @@ class HipPathTracingRenderer:
     def set_camera(self, projector_type: int, settings) -> None:
         s = np.ascontiguousarray(settings, np.float32)
         check(native.lib().chunky_render_set_camera(self._h, int(projector_type), ptr(s), s.size))
+
+    def camera_rays(self, seed: int) -> np.ndarray:
+        """Self test of a projected camera (types 1-5): the rays the render kernels compute for the pass of `seed`, every pixel,
+        width*height*6 floats as camera_rays() lays them out."""
+        out = np.zeros(self.width * self.height * 6, np.float32)
+        check(native.lib().chunky_selftest_camera_rays(self._h, int(np.int32(np.uint32(int(seed) & 0xFFFFFFFF))), ptr(out), out.size))
+        return out
 
     def set_option(self, option: int, value) -> None:
         if option == native.OPT_EMITTER_SCALE:
