@@ -1678,6 +1678,8 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
         const bool bvh = !S.world_bvh_empty || !S.actor_bvh_empty;
         if ((r->kernel_variant & (1 | 2 | 4 | 8)) || (bvh && !(S.bvh_rec && S.tri_rec && S.mat8)))
             return fail(CHUNKY_E_STATE, "the extended light-transport options need the default kernel (CHUNKY_OPT_KERNEL 0)");
+        if (!S.wide)  // their instantiations walk the re-laid-out tree only (an octree deeper than 15 levels has none)
+            return fail(CHUNKY_E_STATE, "the extended light-transport options need an octree the wide re-layout takes (depth <= 15)");
         // the fallback kernels never read these options: a set render_pool refuses (max depth 255) would render the reference's transport
         if (!pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr))
             return fail(CHUNKY_E_STATE, "the extended light-transport options need max depth <= 254 (CHUNKY_OPT_MAX_DEPTH)");

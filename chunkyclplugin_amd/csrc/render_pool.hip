@@ -633,7 +633,11 @@ bool pool_kernel_applies(int variant, const SceneView& S, const RenderOpts& O, b
     // render_pool: always without entity BVHs; with them when they could be re-laid out (rt_device.hpp bvh_rec / tri_rec)
     // (its 6-word parked record counts march steps in 16 bits: a larger draw depth runs render_waves)
     const bool steps_fit = (any_bvh || opts_extended(O) || O.draw_depth <= 65535) && O.max_depth <= 254;  // (path depth 255 marks a fresh path)
-    return !(variant & 2) && !(variant & 8) && have_queue_and_staging && steps_fit &&
+    // a scene without a wide tree (an octree deeper than 15 levels, a block pointer beyond 25 bits: widetree.cpp) runs render_pool's
+    // reference-layout walk, which only the plain instantiations have (pool_kernel<0, 0 | 32 | 64>): with entity BVHs, the extended
+    // options or phase statistics launch_pool would pick a wide-tree instantiation, so those go to the fallback kernels
+    const bool form0_fits = S.wide != nullptr || (!any_bvh && !opts_extended(O) && !(variant & 4));
+    return !(variant & 2) && !(variant & 8) && have_queue_and_staging && steps_fit && form0_fits &&
            (!any_bvh || (S.bvh_rec && S.tri_rec && S.mat8 && !(variant & 1)));
 }
 hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,

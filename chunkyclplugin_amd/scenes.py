@@ -686,6 +686,61 @@ def add_entities(scene: PackedScene, n_tris: int, seed: int = 11, actor_tris: in
                                name=scene.name + f"+{n_tris}tri")
 
 
+def embed_offset(depth: int, slots: Sequence[int]) -> np.ndarray:
+    """(x, y, z) of the corner of the cube reached from the root of a depth-`depth` octree through child slots `slots`
+    (slot = (x << 2) | (y << 1) | z of one address bit, top level first)."""
+    off = np.zeros(3, np.int64)
+    for i, s in enumerate(slots):
+        level = depth - 1 - i
+        off += np.array([(s >> 2) & 1, (s >> 1) & 1, s & 1], np.int64) << level
+    return off
+
+
+def embed_deeper(scene: PackedScene, depth: int, slots: Optional[Sequence[int]] = None, siblings=None) -> PackedScene:
+    """The same world inside a deeper octree: `depth` - d new 8-int groups in front of the array (d = scene.octree_depth), the old
+    tree under child slot slots[i] of new level i (default all 0: the world stays at the origin), its branch values shifted by
+    8 (depth - d), the seven siblings of every new level leaves: air, or what `siblings` says — {(i, slot): block-palette index or
+    ANY_TYPE} makes that child of new level i (a cube of edge 2^(depth - 1 - i)) one leaf of that block, so rays that leave the
+    small world hit, or walk through, leaves of levels d ... depth - 1.  The array grows by 8 ints per level: a depth-20 world is as
+    small as the one it holds.  With slots that are not all 0 the camera moves with the world (a pinhole or projected camera's
+    position, every origin of pre-generated rays; in float, so large offsets cost the view its low bits); entity BVHs are not
+    moved — add_entities(..., region=...) afterwards, in the new coordinates."""
+    d = int(scene.octree_depth)
+    k = int(depth) - d
+    if k <= 0:
+        raise ValueError(f"target depth {depth} is not deeper than the scene's {d}")
+    slots = [0] * k if slots is None else [int(s) for s in slots]
+    if len(slots) != k or any(s < 0 or s > 7 for s in slots):
+        raise ValueError(f"{k} new levels need {k} child slots in 0..7")
+    siblings = dict(siblings or {})
+    for (i, s) in siblings:
+        if not (0 <= i < k and 0 <= s <= 7) or s == slots[i]:
+            raise ValueError(f"sibling {(i, s)} is not a sibling of the embedded world")
+    old = np.asarray(scene.octree, np.int64)
+    body = old[1:].copy()
+    body[body > 0] += 8 * k
+    head = np.zeros(1 + 8 * k, np.int64)
+    head[0] = 1
+    for i in range(k):
+        for s in range(8):
+            t = siblings.get((i, s), 0)
+            head[1 + 8 * i + s] = -ANY_TYPE if t == ANY_TYPE else -2 * int(t)
+        below = 1 + 8 * (i + 1) if i + 1 < k else (int(old[0]) + 8 * k if old[0] > 0 else int(old[0]))
+        head[1 + 8 * i + slots[i]] = below
+    octree = np.concatenate([head, body]).astype(np.int32)
+    off = embed_offset(depth, slots)
+    camera = np.asarray(scene.camera, np.float32).copy()
+    if off.any():
+        if not (np.array_equal(scene.world_bvh, empty_bvh()) and np.array_equal(scene.actor_bvh, empty_bvh())):
+            raise ValueError("entity BVHs do not move with the world: embed first, then add_entities(..., region=...)")
+        if scene.projector_type == -1:
+            rays = camera.reshape(-1, 6)
+            rays[:, :3] += off.astype(np.float32)
+        else:
+            camera[:3] += off.astype(np.float32)
+    return dataclasses.replace(scene, octree=octree, octree_depth=int(depth), camera=camera, name=scene.name + f"@depth{depth}")
+
+
 def tiny_scene(seed: int = 3, size: int = 16, width: int = 48, height: int = 32,
                entities: int = 40, sun_flag: bool = True, water: bool = False,
                atlas_tiles: Tuple[int, int] = (8, 8)) -> PackedScene:
@@ -900,8 +955,8 @@ def big_outdoor_world(chunks: int = 128, height: int = 256, seed: int = 20260606
                        camera=cam, width=width, height=img_height, name=f"bigworld{chunks}x{chunks}")
 
 
-def cached_big_outdoor_world(**kw) -> PackedScene:
-    """big_outdoor_world(**kw) through the on-disk cache (a few minutes and ~12 GB of numpy to generate at 128 x 128 chunks)."""
+def big_outdoor_world_cache_path(**kw) -> str:
+    """Where cached_big_outdoor_world(**kw) keeps its world (the file need not exist)."""
     import hashlib
     import inspect
     import os
@@ -909,7 +964,13 @@ def cached_big_outdoor_world(**kw) -> PackedScene:
     bound.apply_defaults()
     src = inspect.getsource(big_outdoor_world) + inspect.getsource(build_octree_slab) + inspect.getsource(outdoor_world)
     key = hashlib.sha256((repr(sorted(bound.arguments.items())) + src).encode()).hexdigest()[:16]
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), ".scene_cache", f"bigworld_{key}.npz")
+    return os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), ".scene_cache", f"bigworld_{key}.npz")
+
+
+def cached_big_outdoor_world(**kw) -> PackedScene:
+    """big_outdoor_world(**kw) through the on-disk cache (a few minutes and ~12 GB of numpy to generate at 128 x 128 chunks)."""
+    import os
+    path = big_outdoor_world_cache_path(**kw)
     if os.path.exists(path):
         try:
             return load_scene(path)

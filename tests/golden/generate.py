@@ -13,6 +13,8 @@ exposures, and the ARGB words for every filter type, plus pow known answers.
 timed_rows.npz (`... generate.py timed`): rows of the five BASELINE views at their timed sizes (write_timed).
 timed_camera_rows.npz (`... generate.py cameras`): rows of the camera / tint / atlas views at the timed sizes (write_cameras).
 helpers.npz (`... generate.py helpers`): known answers of the reference's exported helper functions (write_helpers).
+deep.npz (`... generate.py deep`): the golden worlds inside octrees of depth 11 - 16 (write_deep).
+timed_big_rows.npz (`... generate.py timed` writes it beside timed_rows.npz): eight rows of the beyond-cache view (write_timed_big).
 libm_platform.npz (`... generate.py libm`): images of the reference object on a second platform layer (glibc libm): write_libm.
 """
 import os
@@ -72,6 +74,37 @@ def write_timed(ref):
         out[name + "_res"] = res
         print(name, sc.width, sc.height, "rows", rows, "mean", float(res.mean()), flush=True)
     np.savez_compressed(os.path.join(HERE, "timed_rows.npz"), **out)
+
+
+def write_timed_big(ref):
+    """timed_big_rows.npz: eight whole rows (golden_scenes.camera_rows) of the view bench.py --config 5 times — the 128 x 128-chunk
+    world, a depth-11 octree: a dense top over TWO 8^3 levels — rendered by the reference build, TIMED_PASSES passes of the
+    java.util.Random(0) seed stream."""
+    seeds = scenes.java_random_ints(gs.TIMED_PASSES)
+    sc = gs.timed_view("big")
+    h = binding.SceneHandle(sc)
+    rows = gs.camera_rows(sc)
+    res = np.zeros((len(rows), sc.width, 3), np.float32)
+    for k, y in enumerate(rows):
+        full = ref.render_passes(h, seeds, gid_range=(y * sc.width, (y + 1) * sc.width), threads=binding.usable_threads())
+        res[k] = full.reshape(-1, 3)[y * sc.width:(y + 1) * sc.width]
+    print("big", sc.width, sc.height, "rows", rows, "mean", float(res.mean()), flush=True)
+    savez_lzma(os.path.join(HERE, "timed_big_rows.npz"), seeds=seeds, big_digest=gs.input_digest(sc), big_rows=np.array(rows, np.int32), big_res=res)
+
+
+def write_deep(ref):
+    """deep.npz: golden_scenes.embed_cases — four golden worlds at the origin of octrees of depth 11, 13, 15 and 16, and "outdoor" in
+    a depth-12 octree at x = z = 1024 beside a full-cube leaf of level 6 — whole images after the N_PASSES golden seeds, previews
+    and input digests, by the reference build."""
+    seeds = scenes.java_random_ints(gs.N_PASSES)
+    out = {"seeds": seeds}
+    for key, sc in gs.embed_cases():
+        h = binding.SceneHandle(sc)
+        out[key + "_digest"] = gs.input_digest(sc)
+        out[key + "_res"] = ref.render_passes(h, seeds)
+        out[key + "_preview"] = ref.preview(h)
+        print(key, "depth", sc.octree_depth, "res mean", float(np.nanmean(out[key + "_res"])), flush=True)
+    savez_lzma(os.path.join(HERE, "deep.npz"), **out)
 
 
 def write_cameras(ref):
@@ -161,8 +194,13 @@ def main():
     assert ref is not None, "needs /root/reference"
     if "filter" in sys.argv[1:]:
         return write_filter(ref)
+    if "timed_big" in sys.argv[1:]:   # the new rows alone (timed_rows.npz stays as it is)
+        return write_timed_big(ref)
     if "timed" in sys.argv[1:]:
-        return write_timed(ref)
+        write_timed(ref)
+        return write_timed_big(ref)
+    if "deep" in sys.argv[1:]:
+        return write_deep(ref)
     if "helpers" in sys.argv[1:]:
         return write_helpers(ref)
     if "cameras" in sys.argv[1:]:
@@ -202,6 +240,8 @@ def main():
     print("kats written")
     write_filter(ref)
     write_timed(ref)
+    write_timed_big(ref)
+    write_deep(ref)
     write_cameras(ref)
     write_helpers(ref)
     write_libm()

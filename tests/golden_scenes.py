@@ -63,6 +63,38 @@ DEEP_NAMES = ["outdoor_nosun", "dof", "pregen", "inside", "water", "atlas_layers
 DEEP_CHUNKS = 8
 RECORD_GIDS = np.arange(0, W * H, 37, dtype=np.int32)
 
+# ---- the golden worlds inside deeper octrees (scenes.embed_deeper; tests/golden/deep.npz: the reference build's images) ----
+# depth 11 - 13: a dense top over TWO 8^3 levels (tree form 18), 14 - 15 over THREE (19), above 15 no wide tree at all (form 0)
+EMBED_SCENES = ["outdoor", "entities", "inside", "pregen"]
+EMBED_DEPTHS = [11, 13, 15, 16]
+EMBED_FORM = {11: 18, 12: 18, 13: 18, 14: 19, 15: 19, 16: 0, 20: 0}
+EMBED_OFFSET = "outdoor_at_1024"
+
+
+def embedded(name: str, depth: int) -> scenes.PackedScene:
+    """Golden scene `name` at the origin of a depth-`depth` octree, air around it."""
+    return scenes.embed_deeper(make(name), depth)
+
+
+def embedded_offset() -> scenes.PackedScene:
+    """"outdoor" in a depth-12 octree with its corner at x = z = 1024 (child slot 5 of the level-10 cubes), and the 64^3 cube
+    diagonally behind it (x and z from 1088 on: child slot 5 of the last new level) one leaf of full-cube stone."""
+    return scenes.embed_deeper(make("outdoor"), 12, slots=[0, 5, 0, 0, 0, 0], siblings={(5, 5): 2})
+
+
+def embedded_any() -> scenes.PackedScene:
+    """"outdoor" at the origin of a depth-15 octree whose upper half above it (y >= 16384: child slot 2 of the root) is one
+    ANY_TYPE leaf of level 14: rays that leave upwards walk through a leaf that cannot be hit before they leave the octree."""
+    return scenes.embed_deeper(make("outdoor"), 15, siblings={(0, 2): scenes.ANY_TYPE})
+
+
+def embed_cases():
+    """(key in deep.npz, scene) of every image the file holds."""
+    for name in EMBED_SCENES:
+        for depth in EMBED_DEPTHS:
+            yield f"{name}_d{depth}", embedded(name, depth)
+    yield EMBED_OFFSET, embedded_offset()
+
 
 def input_digest(sc: scenes.PackedScene) -> str:
     h = hashlib.sha256()
@@ -95,6 +127,8 @@ def timed_view(name: str) -> scenes.PackedScene:
         sc = scenes.add_entities(scenes.cached_outdoor_world(chunks=32, height=256), 100000, seed=11, actor_tris=5000,
                                  region=((40, 90, 40), (470, 170, 470)))
         return sc.with_view(3840, 2160) if name == "entities4k" else sc
+    if name == "big":   # bench.py --config 5 (not a BASELINE configuration, not in TIMED_VIEWS: tests/golden/timed_big_rows.npz)
+        return scenes.cached_big_outdoor_world(width=1920, img_height=1080)
     raise KeyError(name)
 
 

@@ -1,5 +1,8 @@
 """Host-side packers/generators (wire formats of SURVEY.md Appendix A)."""
+import dataclasses
+
 import numpy as np
+import pytest
 
 from chunkyclplugin_amd import scenes
 
@@ -204,3 +207,118 @@ def test_big_world_generator_small():
             lv -= 1
             v = int(sc.octree[v + ((((x >> lv) & 1) << 2) | (((y >> lv) & 1) << 1) | ((z >> lv) & 1))])
         assert (-v, lv) == (int(d), int(l))
+
+
+# ---- scenes.embed_deeper and the default split of the wide tree above depth 10 ----
+EMBED_SLOTS = {"origin": lambda k: [0] * k, "offset": lambda k: [(3 * i + 5) % 8 for i in range(k)]}
+# default_wide_levels (csrc/widetree.cpp): bits of the dense top node and 8^3 levels below it, by octree depth
+DEFAULT_SPLIT = {6: (6, 0), 7: (4, 1), 8: (5, 1), 9: (6, 1), 10: (7, 1), 11: (5, 2), 12: (6, 2), 13: (7, 2), 14: (5, 3), 15: (6, 3)}
+
+
+def _embedded(depth, which):
+    """A depth-6 golden world in a depth-`depth` octree, siblings of every new level alternately stone, ANY_TYPE and air."""
+    sc = scenes.outdoor_world(chunks=2, height=48, seed=101)
+    k = depth - sc.octree_depth
+    slots = EMBED_SLOTS[which](k)
+    sib = {}
+    for i in range(k):
+        free = [s for s in range(8) if s != slots[i]]
+        sib[(i, free[i % 7])] = 2
+        sib[(i, free[(i + 3) % 7])] = scenes.ANY_TYPE
+    return sc, scenes.embed_deeper(sc, depth, slots=slots, siblings=sib), slots, sib
+
+
+def _sibling_cells(rng, depth, slots, n_per):
+    """Cells inside every sibling cube of every new level, with the (level, slot) they belong to."""
+    cells, want = [], []
+    for i in range(len(slots)):
+        level = depth - 1 - i
+        base = scenes.embed_offset(depth, slots[:i])
+        for s in range(8):
+            if s == slots[i]:
+                continue
+            corner = base + (np.array([(s >> 2) & 1, (s >> 1) & 1, s & 1], np.int64) << level)
+            pts = corner + rng.integers(0, 1 << level, size=(n_per, 3))
+            pts[0], pts[1] = corner, corner + (1 << level) - 1        # the cube's first and last cell
+            cells.append(pts)
+            want += [(i, s)] * n_per
+    return np.concatenate(cells), want
+
+
+@pytest.mark.parametrize("which", list(EMBED_SLOTS))
+@pytest.mark.parametrize("depth", range(7, 21))
+def test_embed_deeper_keeps_every_lookup(depth, which):
+    """The reference walk (K/octree.h:23-39) of the embedded tree at cell + offset is the walk of the original at cell; elsewhere it
+    finds the sibling's value at the sibling's level.  Up to depth 15 the wide re-layout with the default split answers the same
+    (data, level) — big sibling leaves included — and its entry count names the split: 2^(3 top bits) + 512 per 8^3 node."""
+    from chunkyclplugin_amd import native
+    rng = np.random.default_rng(depth)
+    sc, deep, slots, sib = _embedded(depth, which)
+    off = scenes.embed_offset(depth, slots)
+    assert deep.octree_depth == depth and deep.octree.size == sc.octree.size + 8 * (depth - 6)
+    assert (off == 0).all() == (which == "origin")
+    np.testing.assert_array_equal(deep.camera[:3], (sc.camera[:3] + off.astype(np.float32)).astype(np.float32))
+    inner = rng.integers(0, 64, size=(3000, 3))
+    inner[:8] = [[(c >> 2 & 1) * 63, (c >> 1 & 1) * 63, (c & 1) * 63] for c in range(8)]     # the world's corners
+    want_in = [lookup(sc.octree, 6, *map(int, c)) for c in inner]
+    got_in = [lookup(deep.octree, depth, *map(int, c + off)) for c in inner]
+    assert got_in == want_in
+    outer, owner = _sibling_cells(rng, depth, slots, 6)
+    want_out = []
+    for (i, s) in owner:
+        t = sib.get((i, s), 0)
+        want_out.append((scenes.ANY_TYPE if t == scenes.ANY_TYPE else 2 * t, depth - 1 - i))
+    assert [lookup(deep.octree, depth, *map(int, c)) for c in outer] == want_out
+    assert {v for v, _l in want_out} == {0, 4, scenes.ANY_TYPE}
+    xyz = np.concatenate([inner + off, outer]).astype(np.int32)
+    if depth > 15:
+        with pytest.raises(native.ChunkyHipError):
+            native.widetree_lookup(deep.octree, depth, xyz)
+        return
+    data, level, n = native.widetree_lookup(deep.octree, depth, xyz)
+    np.testing.assert_array_equal(data, [v for v, _l in want_in + want_out])
+    np.testing.assert_array_equal(level, [l for _v, l in want_in + want_out])
+    top, n3 = DEFAULT_SPLIT[depth]
+    # the top node and some 8^3 nodes: far fewer entries than the next larger top alone would have
+    assert n >= (1 << (3 * top)) and (n - (1 << (3 * top))) % 512 == 0, (n, top)
+    assert n < (1 << (3 * (top + 1))), "the entry count of a sparse world names the top node"
+    assert top + 3 * n3 == depth
+
+
+@pytest.mark.parametrize("depth", sorted(DEFAULT_SPLIT))
+def test_default_split_by_entry_count(depth):
+    """The default split itself, through the entry count of a world that is ONE branch chain down to a single stone cell at the
+    origin: the top node plus exactly one 8^3 node per lower level — 2^(3 top) + 512 n3 identifies (top, n3) uniquely."""
+    from chunkyclplugin_amd import native
+    tree = [1]
+    for i in range(depth):
+        tree += [1 + 8 * (i + 1) if i + 1 < depth else -4] + [0] * 7
+    tree = np.array(tree, np.int32)
+    cells = [[0, 0, 0], [1, 0, 0], [(1 << depth) - 1] * 3]
+    data, level, n = native.widetree_lookup(tree, depth, cells)
+    assert data.tolist() == [4, 0, 0] and level.tolist() == [0, 0, depth - 1]
+    top, n3 = DEFAULT_SPLIT[depth]
+    assert n == (1 << (3 * top)) + 512 * n3, (depth, n)
+    sizes = {(1 << (3 * t)) + 512 * k: (t, k) for t in range(1, 8) for k in range(0, 6) if t + 3 * k == depth}
+    assert sizes[n] == (top, n3)
+
+
+def test_embed_deeper_moves_pregenerated_rays_and_refuses_what_it_cannot_do():
+    sc = scenes.outdoor_world(chunks=2, height=48, seed=101, width=8, img_height=4)
+    rays = np.arange(8 * 4 * 6, dtype=np.float32)
+    pre = sc.with_view(8, 4, camera=rays, projector_type=-1)
+    deep = scenes.embed_deeper(pre, 9, slots=[4, 0, 3])
+    off = scenes.embed_offset(9, [4, 0, 3])
+    assert off.tolist() == [256, 64, 64]
+    np.testing.assert_array_equal(deep.camera.reshape(-1, 6)[:, :3], rays.reshape(-1, 6)[:, :3] + off.astype(np.float32))
+    np.testing.assert_array_equal(deep.camera.reshape(-1, 6)[:, 3:], rays.reshape(-1, 6)[:, 3:])
+    assert pre.camera[0] == 0.0                                        # the input is left alone
+    single = scenes.embed_deeper(dataclasses.replace(sc, octree=np.array([-4], np.int32), octree_depth=2), 4, slots=[7, 7])
+    assert lookup(single.octree, 4, 15, 15, 15) == (4, 2) and lookup(single.octree, 4, 0, 0, 0) == (0, 3)
+    ents = scenes.add_entities(sc, 8)
+    assert scenes.embed_deeper(ents, 8).world_bvh is ents.world_bvh     # at the origin entities stay where they are
+    for bad in (lambda: scenes.embed_deeper(sc, 6), lambda: scenes.embed_deeper(sc, 8, slots=[0]),
+                lambda: scenes.embed_deeper(sc, 8, slots=[0, 8]), lambda: scenes.embed_deeper(sc, 8, siblings={(0, 0): 2}),
+                lambda: scenes.embed_deeper(sc, 8, siblings={(2, 1): 2}), lambda: scenes.embed_deeper(ents, 8, slots=[1, 0])):
+        with pytest.raises(ValueError):
+            bad()

@@ -131,3 +131,77 @@ def test_hip_matches_the_live_reference_build_on_the_whole_image(gpu_instance, r
     assert same.all(), f"{name}: {int((~same).sum())} of {same.size} pixels differ from the live reference build (first gid {int(np.argmin(same))})"
     r.close()
     loader.close()
+
+
+# ---- the beyond-cache view bench.py --config 5 times (not a BASELINE configuration): 128 x 128 chunks, a depth-11 octree, the dense
+# top over TWO 8^3 levels (tree form 18).  tests/golden/timed_big_rows.npz: eight whole rows by the reference build ----
+BIG = np.load(os.path.join(os.path.dirname(__file__), "golden", "timed_big_rows.npz"))
+BIG_GENERATOR_BYTES = 16 << 30   # scenes.big_outdoor_world: about 12 GB of numpy at 128 x 128 chunks, and headroom
+
+
+def big_view():
+    sc = gs.timed_view("big")
+    assert sc.octree_depth == 11 and (sc.width, sc.height) == (1920, 1080)
+    assert gs.input_digest(sc) == str(BIG["big_digest"]), "regenerated scene differs from the one the golden rows were made from"
+    assert BIG["big_rows"].tolist() == gs.camera_rows(sc)
+    return sc
+
+
+def test_restatement_matches_the_reference_on_the_beyond_cache_view(port):
+    from chunkyclplugin_amd import scenes
+    if not os.path.exists(scenes.big_outdoor_world_cache_path(width=1920, img_height=1080)):
+        free = 0
+        for line in open("/proc/meminfo"):
+            if line.startswith("MemAvailable:"):
+                free = int(line.split()[1]) * 1024
+        if free < BIG_GENERATOR_BYTES:
+            pytest.skip(f"the 128 x 128-chunk world is not in .scene_cache and generating it needs about 12 GB of memory ({free >> 30} GiB available); "
+                        "the world is not shrunk: the point is the timed scene itself")
+    sc = big_view()
+    gids = row_gids(sc, BIG["big_rows"])
+    got = port.render_gids(binding.SceneHandle(sc), BIG["seeds"], gids, threads=THREADS).reshape(-1, 3)[gids]
+    np.testing.assert_array_equal(bits(got), bits(BIG["big_res"].reshape(-1, 3)))
+    assert BIG["seeds"].tolist() == GOLD["seeds"].tolist()
+
+
+@pytest.mark.gpu
+def test_hip_matches_the_reference_on_the_beyond_cache_view(gpu_instance):
+    """The one timed kernel that had no test: render_pool<18, 64> on the world bench.py --config 5 builds."""
+    from chunkyclplugin_amd.renderer import HipPathTracingRenderer, HipSceneLoader
+    sc = big_view()
+    loader = HipSceneLoader(gpu_instance)
+    loader.load_packed(sc)
+    r = HipPathTracingRenderer(loader, sc.width, sc.height)
+    r.set_camera(sc.projector_type, sc.camera)
+    r.render_passes(BIG["seeds"])
+    info = r.kernel_info()
+    assert (info["tree"], info["pool"], info["bvh"]) == (18, 64, False) and not info["sorted"], info
+    gids = row_gids(sc, BIG["big_rows"])
+    got = r.read().reshape(-1, 3)[gids]
+    want = BIG["big_res"].reshape(-1, 3)
+    same = (bits(got) == bits(want)).all(axis=1)
+    assert same.all(), f"big: {int((~same).sum())} of {len(gids)} pixels differ from the reference build's rows (first gid {int(gids[np.argmin(same)])})"
+    r.close()
+    loader.close()
+
+
+@pytest.mark.gpu
+def test_hip_matches_the_live_reference_build_on_the_whole_beyond_cache_image(gpu_instance, ref):
+    """Where the reference build travelled to the GPU box (skipped elsewhere): every pixel of the view, two passes of a seed stream the
+    fixture does not hold."""
+    from chunkyclplugin_amd import native
+    from chunkyclplugin_amd.renderer import HipPathTracingRenderer, HipSceneLoader
+    sc = big_view()
+    seeds = native.java_random_ints(2, seed=987654321)
+    want = ref.render_passes(binding.SceneHandle(sc), seeds, threads=THREADS)
+    loader = HipSceneLoader(gpu_instance)
+    loader.load_packed(sc)
+    r = HipPathTracingRenderer(loader, sc.width, sc.height)
+    r.set_camera(sc.projector_type, sc.camera)
+    r.render_passes(seeds)
+    info = r.kernel_info()
+    assert (info["tree"], info["pool"], info["bvh"]) == (18, 64, False), info
+    same = (bits(r.read()) == bits(want)).reshape(-1, 3).all(axis=1)
+    assert same.all(), f"big: {int((~same).sum())} of {same.size} pixels differ from the live reference build (first gid {int(np.argmin(same))})"
+    r.close()
+    loader.close()
