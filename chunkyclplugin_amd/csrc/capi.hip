@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/chunky_hip.h"
+#include "denoise_spec.h"
 #include "kernels.hpp"
 #include "rccl_dyn.hpp"
 #include "rt_device.hpp"
@@ -169,7 +170,17 @@ struct chunky_render {
     int aov_launches = 0;
     AovChoice aov_choice{0, 0, 0};
     int aov_last_launches = 0;  // launches of the most recent chunky_render_aov_passes
+    // chunky_render_denoise: the filter's workspace (kept between calls) and its timing, apart from the render and AOV launches'
+    DevBuf dn_work, dn_out;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> dn_pending;
+    std::vector<int> dn_pending_launches;
+    float dn_ms = 0;
+    int dn_launches = 0;
     ~chunky_render() {
+        for (auto& p : dn_pending) {
+            (void)hipEventDestroy(p.first);
+            (void)hipEventDestroy(p.second);
+        }
         for (auto& p : pending) {
             (void)hipEventDestroy(p.first);
             (void)hipEventDestroy(p.second);
@@ -223,6 +234,7 @@ extern "C" const char* chunky_last_error(void) { return tls_error.c_str(); }
 // 0.5: chunky_group_transport / chunky_group_set_transport (the group's read-back exchange through RCCL, bound at run time)
 // 0.6: albedo and normal images for denoisers: chunky_render_aov_passes / _read / _reset / _kernel_time / _kernel_info
 //      also: projected cameras (CHUNKY_PROJ_PARALLEL .. CHUNKY_PROJ_STEREOGRAPHIC), chunky_camera_rays, chunky_selftest_camera_rays
+//      also: the À-Trous denoiser: chunky_denoise_default_params / _host / _frame / _exp, chunky_render_denoise / _denoise_kernel_time
 //      (additions only, so the version string stays "0.6": hosts that check it for the AOV calls keep working)
 extern "C" const char* chunky_version(void) { return "chunky-hip 0.6 gfx950"; }
 
@@ -2196,6 +2208,208 @@ extern "C" int chunky_render_aov_kernel_info(chunky_render* r, int32_t out4[4]) 
     out4[1] = r->aov_choice.bvh;
     out4[2] = r->aov_choice.blocks;
     out4[3] = r->aov_last_launches;
+    return CHUNKY_OK;
+}
+
+// ------------------------------------------------------------------------------------ denoiser (denoise_spec.h, denoise.hip)
+static_assert(CHUNKY_DENOISE_KERNEL_MASK >> CHUNKY_DENOISE_KERNEL_SHIFT == 3, "two bits of kernel form");
+constexpr float kDenoiseSigmaColor = 4.0f, kDenoiseSigmaNormal = 0.5f, kDenoiseSigmaAlbedo = 0.1f;
+constexpr int kDenoiseIterations = 5;
+
+extern "C" int chunky_denoise_default_params(chunky_denoise_params* p) {
+    if (!p) return fail(CHUNKY_E_INVALID, "denoise_default_params: NULL params");
+    p->size = sizeof(chunky_denoise_params);
+    p->iterations = kDenoiseIterations;
+    p->sigma_color = kDenoiseSigmaColor;
+    p->sigma_normal = kDenoiseSigmaNormal;
+    p->sigma_albedo = kDenoiseSigmaAlbedo;
+    p->flags = CHUNKY_DENOISE_DEMODULATE;
+    return CHUNKY_OK;
+}
+
+// the caller's struct, as far as this library knows it, turned into the per-iteration coefficients and the kernel form
+static int denoise_params(const char* who, const chunky_denoise_params* params, DnCoeffs* K, int* form) {
+    if (!params) return fail(CHUNKY_E_INVALID, "%s: NULL params", who);
+    constexpr size_t kFirst = offsetof(chunky_denoise_params, flags) + sizeof(uint32_t);  // the first version of the struct
+    if (params->size < kFirst) return fail(CHUNKY_E_INVALID, "%s: params.size %zu is smaller than the struct (%zu)", who, params->size, kFirst);
+    chunky_denoise_params p;
+    memcpy(&p, params, params->size < sizeof p ? params->size : sizeof p);  // a larger struct: only the part known here
+    if (p.iterations < 1 || p.iterations > DN_MAX_ITERATIONS) return fail(CHUNKY_E_INVALID, "%s: iterations %d outside 1 .. %d", who, p.iterations, DN_MAX_ITERATIONS);
+    const float sig[3] = {p.sigma_color, p.sigma_normal, p.sigma_albedo};
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(sig[i]) || !(sig[i] > 0.0f)) return fail(CHUNKY_E_INVALID, "%s: sigma %d must be finite and > 0, got %g", who, i, (double)sig[i]);
+    if (p.flags & ~(CHUNKY_DENOISE_DEMODULATE | CHUNKY_DENOISE_KERNEL_MASK)) return fail(CHUNKY_E_INVALID, "%s: unknown flags 0x%x", who, p.flags);
+    const int f = (int)((p.flags & CHUNKY_DENOISE_KERNEL_MASK) >> CHUNKY_DENOISE_KERNEL_SHIFT);
+    if (f != kDenoisePacked && f != kDenoiseGather) return fail(CHUNKY_E_INVALID, "%s: unknown kernel form %d", who, f);
+    if (!dn_coeffs(p.iterations, p.sigma_color, p.sigma_normal, p.sigma_albedo, (int)(p.flags & CHUNKY_DENOISE_DEMODULATE), K))
+        return fail(CHUNKY_E_INVALID, "%s: a sigma is too small or too large for a float coefficient", who);
+    if (form) *form = f;
+    return CHUNKY_OK;
+}
+
+static int denoise_images(const char* who, int width, int height, const void* color, const void* albedo, const void* normal, const void* out) {
+    if (width <= 0 || height <= 0 || (int64_t)width * height > INT32_MAX / 16 || height > 65535 * 4)
+        return fail(CHUNKY_E_INVALID, "%s: bad size %dx%d", who, width, height);
+    if (!color || !albedo || !normal || !out) return fail(CHUNKY_E_INVALID, "%s: NULL image", who);
+    return CHUNKY_OK;
+}
+
+namespace {
+struct HostFetch {  // 3 floats per pixel in each image
+    const float *d, *n, *a;
+    int width;
+    void load(int x, int y, float* dq, float* nq, float* aq) const {
+        const size_t o = 3 * ((size_t)y * width + x);
+        for (int k = 0; k < 3; k++) {
+            dq[k] = d[o + k];
+            nq[k] = n[o + k];
+            aq[k] = a[o + k];
+        }
+    }
+};
+// rows [y0, y1) of every band at once: pixels are independent, so the split changes no bit
+template <class F>
+void over_rows(int height, F body) {
+    unsigned n = std::thread::hardware_concurrency();
+    n = n < 1 ? 1 : (n > 16 ? 16 : n);
+    if ((int)n > height) n = (unsigned)height;
+    std::vector<std::thread> pool;
+    for (unsigned t = 1; t < n; t++) pool.emplace_back(body, (int)((int64_t)height * t / n), (int)((int64_t)height * (t + 1) / n));
+    body(0, (int)((int64_t)height / n));
+    for (auto& t : pool) t.join();
+}
+}  // namespace
+
+extern "C" int chunky_denoise_host(int width, int height, const float* color, const float* albedo, const float* normal,
+                                   const chunky_denoise_params* params, float* out) {
+    DnCoeffs K;
+    if (int rc = denoise_params("denoise_host", params, &K, nullptr)) return rc;
+    if (int rc = denoise_images("denoise_host", width, height, color, albedo, normal, out)) return rc;
+    const size_t n = (size_t)width * height;
+    std::vector<float> buf[2];
+    buf[0].resize(3 * n);
+    buf[1].resize(3 * n);
+    over_rows(height, [&](int y0, int y1) {
+        for (size_t i = (size_t)y0 * width; i < (size_t)y1 * width; i++) dn_demodulate(color + 3 * i, albedo + 3 * i, K.demodulate, &buf[0][3 * i]);
+    });
+    for (int it = 0; it < K.iterations; it++) {
+        const float* src = buf[it & 1].data();
+        float* dst = buf[(it + 1) & 1].data();
+        over_rows(height, [&, src, dst](int y0, int y1) {
+            const HostFetch F{src, normal, albedo, width};
+            for (int y = y0; y < y1; y++)
+                for (int x = 0; x < width; x++) dn_filter_pixel(F, x, y, width, height, 1 << it, K.c_i[it], K.c_n, K.c_a, dst + 3 * ((size_t)y * width + x));
+        });
+    }
+    const float* last = buf[K.iterations & 1].data();
+    over_rows(height, [&](int y0, int y1) {
+        for (size_t i = (size_t)y0 * width; i < (size_t)y1 * width; i++) dn_finish(last + 3 * i, albedo + 3 * i, color + 3 * i, K.demodulate, out + 3 * i);
+    });
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_denoise_exp(const float* x, int n, float* out) {
+    if (n < 0 || (n > 0 && (!x || !out))) return fail(CHUNKY_E_INVALID, "denoise_exp: bad arguments");
+    for (int i = 0; i < n; i++) out[i] = dn_exp(x[i]);
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_denoise_frame(chunky_ctx* ctx, int width, int height, const float* color, const float* albedo, const float* normal,
+                                    const chunky_denoise_params* params, float* out) {
+    if (!ctx) return fail(CHUNKY_E_INVALID, "denoise_frame: NULL context");
+    if (!ctx->members.empty()) ctx = ctx->members[0];  // a group: one frame is filtered on its first member
+    DnCoeffs K;
+    int form = 0;
+    if (int rc = denoise_params("denoise_frame", params, &K, &form)) return rc;
+    if (int rc = denoise_images("denoise_frame", width, height, color, albedo, normal, out)) return rc;
+    if (!launch_denoise) return fail(CHUNKY_E_STATE, "denoise_frame: this build has no denoise kernels (denoise.hip)");
+    std::lock_guard<std::recursive_mutex> guard(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)width * height * 12;
+    DevBuf c, a, n, o, work;
+    HIP_TRY(c.upload(color, bytes, ctx->stream));
+    HIP_TRY(a.upload(albedo, bytes, ctx->stream));
+    HIP_TRY(n.upload(normal, bytes, ctx->stream));
+    HIP_TRY(hipMalloc(&o.p, bytes));
+    o.bytes = bytes;
+    work.bytes = denoise_work_bytes(width, height);
+    HIP_TRY(hipMalloc(&work.p, work.bytes));
+    HIP_TRY(launch_denoise(form, width, height, (const float*)c.p, (const float*)a.p, (const float*)n.p, K, (float*)o.p, work.p, work.bytes, ctx->stream, nullptr));
+    HIP_TRY(hipMemcpyAsync(out, o.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return CHUNKY_OK;
+}
+
+static int collect_denoise_timing(chunky_render* r) {
+    for (size_t i = 0; i < r->dn_pending.size(); i++) {
+        float ms = 0;
+        HIP_TRY(hipEventSynchronize(r->dn_pending[i].second));
+        HIP_TRY(hipEventElapsedTime(&ms, r->dn_pending[i].first, r->dn_pending[i].second));
+        r->dn_ms += ms;
+        r->dn_launches += r->dn_pending_launches[i];
+        r->free_events.push_back(r->dn_pending[i].first);
+        r->free_events.push_back(r->dn_pending[i].second);
+    }
+    r->dn_pending.clear();
+    r->dn_pending_launches.clear();
+    return CHUNKY_OK;
+}
+
+// on one device: r's framebuffer holds the whole image (a single-device target, or member 0 of a group after the exchange)
+static int render_denoise(chunky_render* r, const DnCoeffs& K, int form, float* out) {
+    LOCK_RENDER(r);
+    if (!r->aov.p) return fail(CHUNKY_E_STATE, "render_denoise before any AOV pass");
+    if (!launch_denoise) return fail(CHUNKY_E_STATE, "render_denoise: this build has no denoise kernels (denoise.hip)");
+    const size_t bytes = aov_image_bytes(r), need = denoise_work_bytes(r->width, r->height);
+    if (!r->dn_work.p) {
+        HIP_TRY(hipMalloc(&r->dn_work.p, need));
+        r->dn_work.bytes = need;
+        HIP_TRY(hipMalloc(&r->dn_out.p, bytes));
+        r->dn_out.bytes = bytes;
+    }
+    if (r->dn_pending.size() > 1024)
+        if (int rc = collect_denoise_timing(r)) return rc;
+    const float* albedo = (const float*)r->aov.p;
+    const float* normal = (const float*)((const char*)r->aov.p + bytes);
+    hipEvent_t e0, e1;
+    HIP_TRY(get_event(r, &e0));
+    HIP_TRY(get_event(r, &e1));
+    int launches = 0;
+    HIP_TRY(hipEventRecord(e0, r->ctx->stream));
+    HIP_TRY(launch_denoise(form, r->width, r->height, r->fb, albedo, normal, K, (float*)r->dn_out.p, r->dn_work.p, r->dn_work.bytes, r->ctx->stream, &launches));
+    HIP_TRY(hipEventRecord(e1, r->ctx->stream));
+    r->dn_pending.emplace_back(e0, e1);
+    r->dn_pending_launches.push_back(launches);
+    HIP_TRY(hipMemcpyAsync(out, r->dn_out.p, bytes, hipMemcpyDeviceToHost, r->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_denoise(chunky_render* r, const chunky_denoise_params* params, float* out, int64_t n_floats) {
+    if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
+    DnCoeffs K;
+    int form = 0;
+    if (int rc = denoise_params("render_denoise", params, &K, &form)) return rc;
+    const int64_t need = (int64_t)r->width * r->height * 3;
+    if (!out || n_floats != need) return fail(CHUNKY_E_INVALID, "render_denoise: need %lld floats, got %lld", (long long)need, (long long)n_floats);
+    if (int rc = denoise_images("render_denoise", r->width, r->height, out, out, out, out)) return rc;
+    std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
+    const ShardView& share = r->parts.empty() ? r->shard : r->outer;
+    if (share.world > 1) return fail(CHUNKY_E_STATE, "render_denoise: this target holds rank %d of %d of the image, not all of it", share.rank, share.world);
+    if (r->parts.empty()) return render_denoise(r, K, form, out);
+    if (!r->parts[0]->aov.p) return fail(CHUNKY_E_STATE, "render_denoise before any AOV pass");
+    if (int rc = group_gather(r)) return rc;  // member 0's buffer then holds the whole image (chunky_render_read's exchange)
+    return render_denoise(r->parts[0], K, form, out);
+}
+
+extern "C" int chunky_render_denoise_kernel_time(chunky_render* r, float* total_ms, int* launches) {
+    if (r && !r->parts.empty()) return chunky_render_denoise_kernel_time(r->parts[0], total_ms, launches);
+    LOCK_RENDER(r);
+    if (int rc = collect_denoise_timing(r)) return rc;
+    if (total_ms) *total_ms = r->dn_ms;
+    if (launches) *launches = r->dn_launches;
+    r->dn_ms = 0;
+    r->dn_launches = 0;
     return CHUNKY_OK;
 }
 

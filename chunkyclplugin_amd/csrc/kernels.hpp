@@ -1,10 +1,12 @@
 // kernels.hpp — host-visible launch interface of the kernel translation units (render_pool.hip, render_fallback.hip,
-// aux_kernels.hip, filter.hip, aov.hip).
+// aux_kernels.hip, filter.hip, aov.hip, denoise.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <atomic>
+
+struct DnCoeffs;  // denoise_spec.h
 
 namespace chunky {
 
@@ -119,6 +121,16 @@ struct AovChoice {
 // linked in, chunky_render_aov_passes fails with CHUNKY_E_STATE instead of calling it.
 __attribute__((weak)) hipError_t launch_aov(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
                       float* albedo, float* normal, int* counter, hipStream_t stream, AovChoice* chosen);
+// The À-Trous denoiser (denoise.hip; specification: denoise_spec.h).  color / albedo / normal / out: 3 * width * height floats on the
+// device (out may not alias an input); `work`: denoise_work_bytes of device memory, 16-byte aligned, the launch's own while it runs.
+// One launch per iteration plus the pack (or demodulation) pass, all on `stream`; *launches receives their number.  `form` picks how taps
+// are fetched (all bit-identical).  Weak for the same reason as launch_aov: where denoise.hip is not linked in, the device entry
+// points fail with CHUNKY_E_STATE.
+constexpr int kDenoiseGather = 0;  // the images as they arrive, 3 floats per pixel (the default: the faster of the two)
+constexpr int kDenoisePacked = 1;  // 16-byte words per pixel, written by a pack pass
+inline size_t denoise_work_bytes(int width, int height) { return (size_t)width * height * 64; }  // enough for either form (packed: two colour planes + two guide planes of float4)
+__attribute__((weak)) hipError_t launch_denoise(int form, int width, int height, const float* color, const float* albedo, const float* normal, const ::DnCoeffs& K,
+                                                float* out, void* work, size_t work_bytes, hipStream_t stream, int* launches);
 // thresholds: 256 floats on the device (capi.hip gamma_thresholds) or null = evaluate pow per channel
 hipError_t launch_filter(long long n_pixels, float exposure, const double* in, unsigned* out, int type, hipStream_t stream,
                          const float* thresholds = nullptr);

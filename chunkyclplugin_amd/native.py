@@ -18,7 +18,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("CHUNKY_HIP_LIB") or os.path.join(PKG_DIR, "libchunky_hip.so")  # override: tuning builds (tools/variants.sh)
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
-SOURCES = ["render_pool.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "capi.hip", "widetree.cpp"]
+SOURCES = ["render_pool.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "denoise.hip", "capi.hip", "widetree.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
 
 MAX_TRACES = 10
@@ -32,6 +32,9 @@ PEER_LOCAL, PEER_DIRECT, PEER_STAGED = 0, 1, 2
 TRANSPORT_PEER_COPY, TRANSPORT_RCCL_SENDRECV, TRANSPORT_RCCL_REDUCE = 0, 1, 2
 E_INVALID, E_NO_DEVICE, E_HIP, E_STATE, E_ABORTED = -1, -2, -3, -4, -5
 AOV_ALBEDO, AOV_NORMAL = 0, 1  # chunky_render_aov_read
+DENOISE_DEMODULATE = 1  # chunky_denoise_params.flags
+DENOISE_KERNEL_SHIFT = 8  # ... bits 8-9: 0 the default kernels (the images as they are), 1 the packed words
+DENOISE_KERNEL_GATHER, DENOISE_KERNEL_PACKED = 0, 1
 PROJ_PREGENERATED, PROJ_PINHOLE = -1, 0  # chunky_render_set_camera: the reference's two projector types
 PROJ_PARALLEL, PROJ_FISHEYE, PROJ_PANORAMIC, PROJ_PANORAMIC_SLOT, PROJ_STEREOGRAPHIC = 1, 2, 3, 4, 5  # CHUNKY_PROJ_* (projected cameras)
 
@@ -131,6 +134,12 @@ class RunCallbacks(C.Structure):
                 ("poll_gate", POST_RENDER_FN)]
 
 
+class DenoiseParams(C.Structure):
+    """chunky_denoise_params (include/chunky_hip.h)."""
+    _fields_ = [("size", C.c_size_t), ("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_albedo", C.c_float), ("flags", C.c_uint32)]
+
+
 def lib() -> C.CDLL:
     global _lib
     if _lib is None:
@@ -184,6 +193,12 @@ def lib() -> C.CDLL:
             "chunky_render_aov_reset": [vp],
             "chunky_render_aov_kernel_time": [vp, C.POINTER(f32), C.POINTER(C.c_int)],
             "chunky_render_aov_kernel_info": [vp, vp],
+            "chunky_denoise_default_params": [C.POINTER(DenoiseParams)],
+            "chunky_denoise_host": [C.c_int, C.c_int, vp, vp, vp, C.POINTER(DenoiseParams), vp],
+            "chunky_denoise_frame": [vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(DenoiseParams), vp],
+            "chunky_render_denoise": [vp, C.POINTER(DenoiseParams), vp, i64],
+            "chunky_render_denoise_kernel_time": [vp, C.POINTER(f32), C.POINTER(C.c_int)],
+            "chunky_denoise_exp": [vp, C.c_int, vp],
             "chunky_render_run": [vp, vp, C.POINTER(i32), i32, i32, POST_RENDER_FN, vp],
             "chunky_render_run_ex": [vp, vp, C.POINTER(i32), i32, i32, C.POINTER(RunCallbacks)],
             "chunky_java_random_ints": [i64, vp, C.c_int],
@@ -241,3 +256,49 @@ def widetree_lookup(tree: np.ndarray, depth: int, xyz: np.ndarray, level_bits=No
                                        0 if lb is None else lb.size, ptr(xyz), len(xyz), ptr(data), ptr(level),
                                        C.byref(n_entries)))
     return data, level, n_entries.value
+
+
+def denoise_params(iterations: Optional[int] = None, sigma_color: Optional[float] = None, sigma_normal: Optional[float] = None,
+                   sigma_albedo: Optional[float] = None, demodulate: Optional[bool] = None, kernel: int = 0) -> DenoiseParams:
+    """chunky_denoise_default_params with the given members replaced; `kernel` picks the tap-fetch form (bit-identical)."""
+    p = DenoiseParams()
+    check(lib().chunky_denoise_default_params(C.byref(p)))
+    if iterations is not None:
+        p.iterations = int(iterations)
+    if sigma_color is not None:
+        p.sigma_color = float(sigma_color)
+    if sigma_normal is not None:
+        p.sigma_normal = float(sigma_normal)
+    if sigma_albedo is not None:
+        p.sigma_albedo = float(sigma_albedo)
+    if demodulate is not None:
+        p.flags = (p.flags & ~DENOISE_DEMODULATE) | (DENOISE_DEMODULATE if demodulate else 0)
+    p.flags |= int(kernel) << DENOISE_KERNEL_SHIFT
+    return p
+
+
+def _images(width, height, *arrays):
+    out = []
+    for a in arrays:
+        a = np.ascontiguousarray(a, np.float32).reshape(-1)
+        if a.size != 3 * int(width) * int(height):
+            raise ValueError(f"expected {3 * int(width) * int(height)} floats, got {a.size}")
+        out.append(a)
+    return out
+
+
+def denoise_host(width: int, height: int, color, albedo, normal, params: Optional[DenoiseParams] = None) -> np.ndarray:
+    """chunky_denoise_host: the filter's specification, evaluated on the host (no device needed)."""
+    c, a, n = _images(width, height, color, albedo, normal)
+    p = params if params is not None else denoise_params()
+    out = np.zeros(c.size, np.float32)
+    check(lib().chunky_denoise_host(int(width), int(height), ptr(c), ptr(a), ptr(n), C.byref(p), ptr(out)))
+    return out
+
+
+def denoise_exp(x) -> np.ndarray:
+    """chunky_denoise_exp: the filter's e^(-x) on the host."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    out = np.zeros(x.size, np.float32)
+    check(lib().chunky_denoise_exp(ptr(x), x.size, ptr(out)))
+    return out

@@ -33,6 +33,16 @@ def camera_rays(projector_type: int, settings, width: int, height: int, seed: in
     return native.camera_rays(projector_type, settings, width, height, seed)
 
 
+def denoise_frame(instance, width: int, height: int, color, albedo, normal, params=None) -> np.ndarray:
+    """chunky_denoise_frame: the A-Trous filter on `instance`'s device over host images (3 floats per pixel each); returns a
+    (height, width, 3) float32 array equal, bit for bit, to native.denoise_host on the same inputs.  `params`: native.denoise_params()."""
+    c, a, n = native._images(width, height, color, albedo, normal)
+    p = params if params is not None else native.denoise_params()
+    out = np.empty((int(height), int(width), 3), np.float32)
+    check(native.lib().chunky_denoise_frame(instance._h, int(width), int(height), ptr(c), ptr(a), ptr(n), C.byref(p), ptr(out)))
+    return out
+
+
 class RendererInstance:
     """One GPU context per device index (the reference keeps a singleton for its one cl_device,
     RendererInstance.java:23-28; `clDevice` index from PersistentSettings :33)."""
@@ -330,6 +340,21 @@ class HipPathTracingRenderer:
         out = np.zeros(4, np.int32)
         check(native.lib().chunky_render_aov_kernel_info(self._h, ptr(out)))
         return {"tree": int(out[0]), "bvh": bool(out[1]), "blocks": int(out[2]), "launches": int(out[3])}
+
+    # --- denoising (chunky_render_denoise) ------------------------------------------------------------
+    def denoise(self, params=None) -> np.ndarray:
+        """The framebuffer filtered with this target's AOV images, all on the device; only the (height, width, 3) result is read
+        back.  Needs render_aov first; the framebuffer and the AOV images are left as they are."""
+        p = params if params is not None else native.denoise_params()
+        out = np.empty((self.height, self.width, 3), np.float32)
+        check(native.lib().chunky_render_denoise(self._h, C.byref(p), ptr(out), out.size))
+        return out
+
+    def denoise_kernel_time(self):
+        """(milliseconds, launches) of the denoise kernels since the last call."""
+        ms, n = C.c_float(), C.c_int()
+        check(native.lib().chunky_render_denoise_kernel_time(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
     def render(self, sample_buffer: np.ndarray, scene_spp: int, target_spp: int, merge_interval: int = 1024) -> int:
         """The pass loop of OpenClPathTracingRenderer.render (:95-184) run natively; merges into the

@@ -341,6 +341,60 @@ int chunky_render_aov_kernel_time(chunky_render* r, float* total_ms, int* launch
  * workgroups launched, launches made by the most recent chunky_render_aov_passes}. */
 int chunky_render_aov_kernel_info(chunky_render* r, int32_t out4[4]);
 
+/* ---- denoising (no reference counterpart): an edge-avoiding À-Trous wavelet filter (Dammertz et al. 2010) guided by the albedo
+ * and normal images above.  Closed-form and deterministic; the exact arithmetic is chunkyclplugin_amd/csrc/denoise_spec.h, which the
+ * kernels and chunky_denoise_host both compile, so the device result equals the host's bit for bit.
+ * Per pixel, colour C, albedo A, normal N (3 floats each, interleaved as chunky_render_read / chunky_render_aov_read deliver them),
+ * m = max(A, 2^-10) per channel:
+ *   D0 = C / m with CHUNKY_DENOISE_DEMODULATE, else C (a pure-sky pixel, whose albedo is its radiance, demodulates to about 1);
+ *   iteration i = 0 .. iterations-1, step s = 1 << i: taps q = p + s (dx, dy), dy = -2..2 outer, dx = -2..2 inner, those outside
+ *     the image skipped; h = k[|dx|] k[|dy|], k = {3/8, 1/4, 1/16}; dc, dn, da = sums over channels of the squared differences of
+ *     D, N, A between q and p; x = (dc c_i + dn c_n) + da c_a with c_i = 4^i / sigma_color^2 (the colour sigma halves per
+ *     iteration), c_n = 1 / sigma_normal^2, c_a = 1 / sigma_albedo^2, computed once in float; w = h e^(-x);
+ *     D'(p) = (sum w D(q)) / (sum w), each sum in tap order;
+ *   out = D m with CHUNKY_DENOISE_DEMODULATE.
+ * Non-finite values do not spread: a tap whose D has a non-finite channel, or whose x is not finite, has weight 0; a pixel whose D
+ * is non-finite, or whose weights sum to 0, keeps its D; a pixel whose input colour has a non-finite channel comes back as that
+ * input colour.  albedo = 0 is legal (that is what the 2^-10 is for). */
+#define CHUNKY_DENOISE_DEMODULATE 1u    /* flags bit 0 */
+/* flags bits 8-9: how the kernels fetch their taps (no effect on the result or on chunky_denoise_host): 0 the default (the three
+ * images read as they are, 3 floats per pixel), 1 the packed form (16-byte words per pixel written by a pack pass; measured slower) */
+#define CHUNKY_DENOISE_KERNEL_SHIFT 8
+#define CHUNKY_DENOISE_KERNEL_MASK 0x300u
+typedef struct chunky_denoise_params {
+    size_t size;          /* sizeof(chunky_denoise_params) as the CALLER was compiled (as chunky_run_callbacks::struct_size): members
+                           * are appended over time and the library reads only those the caller's struct holds */
+    int32_t iterations;   /* 1 .. 8 */
+    float sigma_color;    /* finite and > 0, also the next two */
+    float sigma_normal;
+    float sigma_albedo;
+    uint32_t flags;       /* CHUNKY_DENOISE_* ; unknown bits are CHUNKY_E_INVALID */
+} chunky_denoise_params;
+/* Fills *p with the defaults (5 iterations, demodulation on) and p->size with this library's struct size. */
+int chunky_denoise_default_params(chunky_denoise_params* p);
+/* The filter on the host, threaded over rows; takes no context and uses no device.  color / albedo / normal / out: 3*width*height
+ * floats; out may not overlap an input.  This function is the specification the device entry points are held to.
+ * CHUNKY_E_INVALID: a NULL pointer, width or height <= 0, size smaller than the first version of the struct (through `flags`),
+ * iterations outside 1 .. 8, a sigma that is not finite or <= 0 (or so small or large that its coefficient is not a positive
+ * finite float).  Images of 1 x 1, 1 x N and N x 1 are legal. */
+int chunky_denoise_host(int width, int height, const float* color, const float* albedo, const float* normal,
+                        const chunky_denoise_params* params, float* out);
+/* The same on the device: uploads the three images, filters, reads the result back (blocking).  What a host calls on its merged
+ * image after several read-backs.  Same validation. */
+int chunky_denoise_frame(chunky_ctx* ctx, int width, int height, const float* color, const float* albedo, const float* normal,
+                         const chunky_denoise_params* params, float* out);
+/* Filters the target's own framebuffer with the target's own AOV images, all resident on the device; only the result crosses to the
+ * host (out: n_floats = 3*width*height).  The framebuffer and the AOV images are read, never written: chunky_render_read /
+ * chunky_render_aov_read return afterwards what they returned before.  Waits for the queued passes; on a group it runs on member 0
+ * after the exchange of chunky_render_read.  CHUNKY_E_STATE before any AOV pass, and on a target whose shard
+ * (chunky_render_set_shard with world > 1) does not hold the whole image. */
+int chunky_render_denoise(chunky_render* r, const chunky_denoise_params* params, float* out, int64_t n_floats);
+/* Device time of the denoise launches since the last call, from HIP events on the stream they run on (as
+ * chunky_render_aov_kernel_time), and their number: one per iteration, plus one for the demodulation (or pack) pass. */
+int chunky_render_denoise_kernel_time(chunky_render* r, float* total_ms, int* launches);
+/* The filter's e^(-x) (x >= 0) evaluated on the host for n values: the instrument of its accuracy test. */
+int chunky_denoise_exp(const float* x, int n, float* out);
+
 /* ---- host pass loop (replaces OpenClPathTracingRenderer.render, J/opencl/OpenClPathTracingRenderer.java:54-191):
  * seeds from java.util.Random(0).nextInt(), bufferSpp restarting at 0 after each read-back, merge
  * sample = (sample*sampSpp + pass*passSpp) / (sampSpp+passSpp) in double (:167-173).

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""tools/kernel_resources.py [out.json] — registers, spills and occupancy of every render_pool / fold_kernel instantiation as hipcc
-reports them for gfx950 (-Rpass-analysis=kernel-resource-usage on csrc/render_pool.hip with the library's flags).  CPU only."""
+"""tools/kernel_resources.py [out.json] — registers, spills and occupancy of every render_pool / fold_kernel instantiation and of the
+denoise kernels as hipcc reports them for gfx950 (-Rpass-analysis=kernel-resource-usage on csrc/render_pool.hip and csrc/denoise.hip
+with the library's flags).  CPU only."""
 import json
 import os
 import re
@@ -12,8 +13,10 @@ sys.path.insert(0, ROOT)
 from chunkyclplugin_amd import native  # noqa: E402
 
 flags = [f for f in native.HIPCC_FLAGS if f not in ("-shared",)]
-cmd = ["hipcc", *flags, "-x", "hip", "-c", os.path.join(native.CSRC, "render_pool.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
-err = subprocess.run(cmd, capture_output=True, text=True).stderr
+err = ""
+for src in ("render_pool.hip", "denoise.hip"):
+    cmd = ["hipcc", *flags, "-x", "hip", "-c", os.path.join(native.CSRC, src), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
+    err += subprocess.run(cmd, capture_output=True, text=True).stderr
 out, cur = {}, None
 for line in err.splitlines():
     m = re.search(r"Function Name: (\S+)", line)
