@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/chunky_hip.h"
+#include "adaptive_spec.h"
 #include "denoise_spec.h"
 #include "kernels.hpp"
 #include "rccl_dyn.hpp"
@@ -176,7 +177,16 @@ struct chunky_render {
     std::vector<int> dn_pending_launches;
     float dn_ms = 0;
     int dn_launches = 0;
+    // chunky_render_adaptive: (m, M2) per pixel, the sample counts, the active / unconverged flags (a byte per pixel each), the tile
+    // counts and offsets of the compaction with the total behind them, the active list, and the pinned word the total is read from;
+    // allocated by the first adaptive call.  Its timing is kept apart from the other launches'
+    DevBuf ad_stat, ad_count, ad_flags, ad_tiles, ad_list;
+    int32_t* ad_total_host = nullptr;
+    bool ad_valid = false;  // an adaptive run has finished: the maps can be read
+    float ad_ms = 0;
+    int ad_rounds = 0;
     ~chunky_render() {
+        if (ad_total_host) (void)hipHostFree(ad_total_host);
         for (auto& p : dn_pending) {
             (void)hipEventDestroy(p.first);
             (void)hipEventDestroy(p.second);
@@ -2208,6 +2218,309 @@ extern "C" int chunky_render_aov_kernel_info(chunky_render* r, int32_t out4[4]) 
     out4[1] = r->aov_choice.bvh;
     out4[2] = r->aov_choice.blocks;
     out4[3] = r->aov_last_launches;
+    return CHUNKY_OK;
+}
+
+// ------------------------------------------------------------------------------------ adaptive sampling (adaptive_spec.h, adaptive.hip)
+// The threshold is an UNMEASURED PLACEHOLDER: tools/adaptive_bench.py, which is to choose it, has not been run on a device yet
+// 
+constexpr float kAdaptiveThreshold = 0.05f, kAdaptiveFloor = 0.01f;
+constexpr int kAdaptiveMinSpp = 16, kAdaptiveInterval = 16;
+
+extern "C" int chunky_adaptive_default_params(chunky_adaptive_params* p) {
+    if (!p) return fail(CHUNKY_E_INVALID, "adaptive_default_params: NULL params");
+    p->size = sizeof(chunky_adaptive_params);
+    p->threshold = kAdaptiveThreshold;
+    p->floor = kAdaptiveFloor;
+    p->min_spp = kAdaptiveMinSpp;
+    p->check_interval = kAdaptiveInterval;
+    p->flags = 0;
+    p->reserved = 0;
+    return CHUNKY_OK;
+}
+
+// the caller's struct, as far as this library knows it, checked against the pass count
+static int adaptive_params(const char* who, const chunky_adaptive_params* params, int max_spp, chunky_adaptive_params* p) {
+    if (!params) return fail(CHUNKY_E_INVALID, "%s: NULL params", who);
+    constexpr size_t kFirst = offsetof(chunky_adaptive_params, flags) + sizeof(uint32_t);  // the first version of the struct
+    if (params->size < kFirst) return fail(CHUNKY_E_INVALID, "%s: params.size %zu is smaller than the struct (%zu)", who, params->size, kFirst);
+    memset(p, 0, sizeof *p);
+    memcpy(p, params, params->size < sizeof *p ? params->size : sizeof *p);  // a larger struct: only the part known here
+    if (!std::isfinite(p->threshold) || p->threshold < 0.0f) return fail(CHUNKY_E_INVALID, "%s: threshold must be finite and >= 0, got %g", who, (double)p->threshold);
+    if (!std::isfinite(p->floor) || !(p->floor > 0.0f)) return fail(CHUNKY_E_INVALID, "%s: floor must be finite and > 0, got %g", who, (double)p->floor);
+    if (p->min_spp < 2) return fail(CHUNKY_E_INVALID, "%s: min_spp %d < 2", who, p->min_spp);
+    if (p->check_interval < 1) return fail(CHUNKY_E_INVALID, "%s: check_interval %d < 1", who, p->check_interval);
+    if (p->flags) return fail(CHUNKY_E_INVALID, "%s: unknown flags 0x%x", who, p->flags);
+    if (max_spp < p->min_spp) return fail(CHUNKY_E_INVALID, "%s: %d passes are fewer than min_spp %d", who, max_spp, p->min_spp);
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_adaptive_host(int width, int height, const float* samples, int n, const chunky_adaptive_params* params,
+                                    int32_t* count_out, float* mean_out, float* stat_out) {
+    chunky_adaptive_params p;
+    if (int rc = adaptive_params("adaptive_host", params, n, &p)) return rc;
+    if (width <= 0 || height <= 0 || (int64_t)width * height > INT32_MAX / 16) return fail(CHUNKY_E_INVALID, "adaptive_host: bad size %dx%d", width, height);
+    if (!samples) return fail(CHUNKY_E_INVALID, "adaptive_host: NULL samples");
+    const size_t np = (size_t)width * height;
+    const float t2 = p.threshold * p.threshold;
+    std::vector<float> mean(3 * np, 0.0f), stat(2 * np, 0.0f);
+    std::vector<int32_t> count(np, 0);
+    std::vector<unsigned char> active(np, 1), unconv(np, 0);
+    size_t n_active = np;
+    int done = 0;
+    while (done < n && n_active > 0) {
+        const float* s = samples + 3 * np * (size_t)done;
+        for (size_t i = 0; i < np; i++) {
+            if (!active[i]) continue;
+            for (int c = 0; c < 3; c++) mean[3 * i + c] = ad_mean(mean[3 * i + c], s[3 * i + c], done);
+            ad_welford(ad_luma(s[3 * i], s[3 * i + 1], s[3 * i + 2]), done, &stat[2 * i], &stat[2 * i + 1]);
+        }
+        done += 1;
+        if (!ad_check_due(done, p.min_spp, p.check_interval, n)) continue;
+        for (size_t i = 0; i < np; i++) unconv[i] = (unsigned char)(active[i] && ad_unconverged(stat[2 * i], stat[2 * i + 1], done, t2, p.floor));
+        for (int y = 0; y < height; y++)
+            for (int x = 0; x < width; x++) {
+                const size_t i = (size_t)y * width + x;
+                if (!active[i]) continue;
+                int any = 0;
+                for (int yy = y > 0 ? y - 1 : y; yy <= (y < height - 1 ? y + 1 : y); yy++)
+                    for (int xx = x > 0 ? x - 1 : x; xx <= (x < width - 1 ? x + 1 : x); xx++) any |= unconv[(size_t)yy * width + xx];
+                if (!any) {
+                    active[i] = 0;
+                    count[i] = done;
+                    n_active -= 1;
+                }
+            }
+    }
+    for (size_t i = 0; i < np; i++)
+        if (active[i]) count[i] = done;
+    if (count_out) memcpy(count_out, count.data(), np * sizeof(int32_t));
+    if (mean_out) memcpy(mean_out, mean.data(), 3 * np * sizeof(float));
+    if (stat_out) memcpy(stat_out, stat.data(), 2 * np * sizeof(float));
+    return CHUNKY_OK;
+}
+
+static int adaptive_tiles(const chunky_render* r) { return ((r->width + 15) / 16) * ((r->height + 15) / 16); }
+
+static int adaptive_ensure(chunky_render* r) {
+    const size_t np = (size_t)r->width * r->height;
+    DevBuf* bufs[5] = {&r->ad_stat, &r->ad_count, &r->ad_flags, &r->ad_tiles, &r->ad_list};
+    const size_t bytes[5] = {np * 8, np * 4, np * 2, ((size_t)adaptive_tiles(r) * 2 + 1) * 4, np * 4};
+    for (int i = 0; i < 5; i++) {  // each on its own: a call that failed half way left the others in place
+        if (bufs[i]->p) continue;
+        HIP_TRY(hipMalloc(&bufs[i]->p, bytes[i]));
+        bufs[i]->bytes = bytes[i];
+    }
+    if (!r->ad_total_host) HIP_TRY(hipHostMalloc((void**)&r->ad_total_host, sizeof(int32_t), hipHostMallocDefault));
+    return CHUNKY_OK;
+}
+
+// a pair of timing events borrowed from the target's pool and handed back on every way out
+struct AdaptiveEvents {
+    chunky_render* r;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    explicit AdaptiveEvents(chunky_render* r_) : r(r_) {}
+    ~AdaptiveEvents() {
+        if (e0) r->free_events.push_back(e0);
+        if (e1) r->free_events.push_back(e1);
+    }
+};
+
+// what an adaptive call needs of the target: one device, the whole image, and render_pool for the scene and options as they are
+static int adaptive_state(const char* who, chunky_render* r, SceneView* S) {
+    if (r->shard.world > 1) return fail(CHUNKY_E_STATE, "%s: this target holds rank %d of %d of the image, not all of it", who, r->shard.rank, r->shard.world);
+    if (!r->have_camera) return fail(CHUNKY_E_STATE, "%s before set_camera", who);
+    if (!launch_render_stats || !launch_fold_stats || !launch_adaptive_check || !launch_adaptive_finish) return fail(CHUNKY_E_STATE, "%s: this build has no adaptive kernels (adaptive.hip)", who);
+    if (int rc = scene_view(r->scene, S, r->opts.nee != 0)) return rc;
+    S->bvh_cull = r->opts.bvh_cull;
+    const bool bvh = !S->world_bvh_empty || !S->actor_bvh_empty;
+    if (opts_extended(r->opts) && ((r->kernel_variant & (1 | 2 | 4 | 8)) || (bvh && !(S->bvh_rec && S->tri_rec && S->mat8)) || !S->wide))
+        return fail(CHUNKY_E_STATE, "%s: the extended light-transport options need the default kernel and an octree the wide re-layout takes", who);
+    if (!pool_kernel_applies(r->kernel_variant, *S, r->opts, r->work_counter.p != nullptr))
+        return fail(CHUNKY_E_STATE, "%s: the scene or the options send this target to the fallback kernels, which stage no samples", who);
+    return CHUNKY_OK;
+}
+
+// The most passes one launch over the pixel slots of T carries (as launch_pass_cap, sized from T and not from r->shard; at most
+// kMaxPassesPerLaunch: the seeds travel in the kernel-argument segment), and the staging array grown to hold a launch of
+// min(n, cap) passes — before the round's timing bracket opens, so that no allocation is timed.  It grows only: chunky_render_passes
+// reuses it, and r->launch_cap is not touched.
+static int adaptive_stage(chunky_render* r, const ShardView& T, int n, int* cap_out) {
+    const int64_t n_slots = (int64_t)(staging_floats(T, r->width, r->height, 1) / 3);  // padded tiles
+    *cap_out = kMaxPassesPerLaunch;
+    if (n_slots <= 0) return CHUNKY_OK;
+    int64_t cap = (int64_t)(kStagingBytes / 12) / n_slots;
+    const int64_t cap31 = ((int64_t)1 << 31) / n_slots - 1;
+    if (cap > cap31) cap = cap31;
+    if (cap > kMaxPassesPerLaunch) cap = kMaxPassesPerLaunch;
+    if (cap < 1) return fail(CHUNKY_E_INVALID, "adaptive: the image is too large to stage one pass");
+    *cap_out = (int)cap;
+    const size_t need = staging_floats(T, r->width, r->height, n < (int)cap ? n : (int)cap) * sizeof(float);
+    if (r->staging.bytes < need) {
+        HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+        r->staging.release();
+        HIP_TRY(hipMalloc(&r->staging.p, need));
+        r->staging.bytes = need;
+    }
+    return CHUNKY_OK;
+}
+
+// n passes (bufferSpp first_spp ..) over the pixel slots of T — the target's own shard, or a list of pixels — folded with the
+// luminance statistic, in launches of at most `cap` passes (adaptive_stage)
+static int adaptive_launch(chunky_render* r, const SceneView& S, const ShardView& T, const int32_t* seeds, int n, int first_spp, int cap) {
+    if (T.n_local <= 0) return CHUNKY_OK;
+    for (int done = 0; done < n;) {
+        PassSeeds ps;
+        ps.n = (n - done) < cap ? (n - done) : cap;
+        ps.first_spp = first_spp + done;
+        memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
+        HIP_TRY(launch_render_stats(r->kernel_variant, S, r->cam, r->opts, T, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream, &r->last_choice,
+                                    (float*)r->staging.p, nullptr, (float*)r->ad_stat.p));
+        done += ps.n;
+    }
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_adaptive(chunky_render* r, const int32_t* seeds, int max_spp, const chunky_adaptive_params* params,
+                                      chunky_adaptive_summary* summary_out) {
+    if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
+    chunky_adaptive_params p;
+    if (int rc = adaptive_params("render_adaptive", params, max_spp, &p)) return rc;
+    if (!seeds) return fail(CHUNKY_E_INVALID, "render_adaptive: NULL seeds");
+    if (!r->parts.empty()) return fail(CHUNKY_E_STATE, "render_adaptive: a group's target (the active list lives on one device)");
+    LOCK_RENDER(r);
+    SceneView S;
+    if (int rc = adaptive_state("render_adaptive", r, &S)) return rc;
+    if (int rc = adaptive_ensure(r)) return rc;
+    hipStream_t st = r->ctx->stream;
+    const int np = r->width * r->height, n_tiles = adaptive_tiles(r);
+    unsigned char* active = (unsigned char*)r->ad_flags.p;
+    unsigned char* unconv = active + np;
+    int* tile_counts = (int*)r->ad_tiles.p;
+    int* tile_offsets = tile_counts + n_tiles;
+    int* total = tile_offsets + n_tiles;
+    r->ad_valid = false;
+    HIP_TRY(hipMemsetAsync(r->fb, 0, (size_t)np * 3 * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(r->ad_stat.p, 0, r->ad_stat.bytes, st));
+    HIP_TRY(hipMemsetAsync(r->ad_count.p, 0, r->ad_count.bytes, st));
+    HIP_TRY(hipMemsetAsync(active, 1, (size_t)np, st));
+    const float t2 = p.threshold * p.threshold;
+    chunky_adaptive_summary sum;
+    memset(&sum, 0, sizeof sum);
+    AdaptiveEvents ev(r);
+    HIP_TRY(get_event(r, &ev.e0));
+    HIP_TRY(get_event(r, &ev.e1));
+    const hipEvent_t e0 = ev.e0, e1 = ev.e1;
+    int done = 0, n_active = np;
+    while (done < max_spp && n_active > 0) {
+        const int left = max_spp - done;
+        const int round_n = done == 0 ? p.min_spp : (p.check_interval < left ? p.check_interval : left);
+        // every pixel still active: the ordinary block mapping; else the active pixels from the list of the last check (a temporary
+        // view with world != 1 and tile != 0, the route of shard_gid through T.list)
+        ShardView T = r->shard;
+        if (n_active < np) T = ShardView{0, 2, 1, n_active, (const int*)r->ad_list.p, n_active};
+        int cap = 0;
+        if (int rc = adaptive_stage(r, T, round_n, &cap)) return rc;
+        HIP_TRY(hipEventRecord(e0, st));
+        if (int rc = adaptive_launch(r, S, T, seeds + done, round_n, done, cap)) return rc;
+        sum.samples += (int64_t)n_active * round_n;
+        done += round_n;
+        sum.rounds += 1;
+        const bool check = ad_check_due(done, p.min_spp, p.check_interval, max_spp) != 0;
+        if (check) {
+            HIP_TRY(launch_adaptive_check(r->width, r->height, (const float*)r->ad_stat.p, active, unconv, (int*)r->ad_count.p, done, t2, p.floor,
+                                          tile_counts, tile_offsets, (int*)r->ad_list.p, total, st));
+            HIP_TRY(hipMemcpyAsync(r->ad_total_host, total, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipEventRecord(e1, st));
+        HIP_TRY(hipStreamSynchronize(st));  // once per round: the host loop needs the total
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        r->ad_ms += ms;
+        r->ad_rounds += 1;
+        if (check) {
+            n_active = *r->ad_total_host;
+            if (n_active < 0 || n_active > np) return fail(CHUNKY_E_HIP, "render_adaptive: the compaction reported %d active pixels of %d", n_active, np);
+            if (sum.checks < CHUNKY_ADAPTIVE_MAX_CHECKS) sum.active[sum.checks] = n_active;
+            sum.checks += 1;
+        }
+    }
+    HIP_TRY(launch_adaptive_finish(np, active, (int*)r->ad_count.p, done, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    sum.passes = done;
+    r->ad_valid = true;
+    if (summary_out) *summary_out = sum;
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_adaptive_counts(chunky_render* r, int32_t* out, int64_t n) {
+    if (r && !r->parts.empty()) return fail(CHUNKY_E_STATE, "render_adaptive_counts: a group's target has no adaptive run");
+    LOCK_RENDER(r);
+    const int64_t need = (int64_t)r->width * r->height;
+    if (!out || n != need) return fail(CHUNKY_E_INVALID, "render_adaptive_counts: need %lld values, got %lld", (long long)need, (long long)n);
+    if (!r->ad_valid) return fail(CHUNKY_E_STATE, "render_adaptive_counts before any adaptive run");
+    HIP_TRY(hipMemcpyAsync(out, r->ad_count.p, (size_t)n * 4, hipMemcpyDeviceToHost, r->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_adaptive_noise(chunky_render* r, float* out, int64_t n_floats) {
+    if (r && !r->parts.empty()) return fail(CHUNKY_E_STATE, "render_adaptive_noise: a group's target has no adaptive run");
+    LOCK_RENDER(r);
+    const int64_t need = (int64_t)r->width * r->height * 2;
+    if (!out || n_floats != need) return fail(CHUNKY_E_INVALID, "render_adaptive_noise: need %lld floats, got %lld", (long long)need, (long long)n_floats);
+    if (!r->ad_valid) return fail(CHUNKY_E_STATE, "render_adaptive_noise before any adaptive run");
+    HIP_TRY(hipMemcpyAsync(out, r->ad_stat.p, (size_t)n_floats * 4, hipMemcpyDeviceToHost, r->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_adaptive_kernel_time(chunky_render* r, float* total_ms, int* rounds) {
+    if (r && !r->parts.empty()) return fail(CHUNKY_E_STATE, "render_adaptive_kernel_time: a group's target has no adaptive run");
+    LOCK_RENDER(r);
+    if (total_ms) *total_ms = r->ad_ms;
+    if (rounds) *rounds = r->ad_rounds;
+    r->ad_ms = 0;
+    r->ad_rounds = 0;
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_selftest_render_list(chunky_render* r, const int32_t* pixels, int n_pixels, const int32_t* seeds, int n) {
+    if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
+    if (n < 0 || n_pixels < 0 || (n > 0 && !seeds) || (n_pixels > 0 && !pixels)) return fail(CHUNKY_E_INVALID, "selftest_render_list: bad arguments");
+    if (!r->parts.empty()) return fail(CHUNKY_E_STATE, "selftest_render_list: a group's target");
+    LOCK_RENDER(r);
+    const int np = r->width * r->height;
+    if (n_pixels > np) return fail(CHUNKY_E_INVALID, "selftest_render_list: %d pixels listed, the image has %d", n_pixels, np);
+    std::vector<unsigned char> seen((size_t)np, 0);
+    for (int i = 0; i < n_pixels; i++) {
+        if (pixels[i] < 0 || pixels[i] >= np || seen[pixels[i]]) return fail(CHUNKY_E_INVALID, "selftest_render_list: entry %d (%d) is outside the image or listed twice", i, pixels[i]);
+        seen[pixels[i]] = 1;
+    }
+    SceneView S;
+    if (int rc = adaptive_state("selftest_render_list", r, &S)) return rc;
+    if (int rc = adaptive_ensure(r)) return rc;
+    if (n == 0 || n_pixels == 0) return CHUNKY_OK;
+    hipStream_t st = r->ctx->stream;
+    r->ad_valid = false;  // the statistic and the list are overwritten
+    HIP_TRY(hipMemsetAsync(r->ad_stat.p, 0, r->ad_stat.bytes, st));
+    HIP_TRY(hipMemcpyAsync(r->ad_list.p, pixels, (size_t)n_pixels * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the caller may reuse its array on return
+    const ShardView T{0, 2, 1, n_pixels, (const int*)r->ad_list.p, n_pixels};
+    AdaptiveEvents ev(r);
+    HIP_TRY(get_event(r, &ev.e0));
+    HIP_TRY(get_event(r, &ev.e1));
+    const hipEvent_t e0 = ev.e0, e1 = ev.e1;
+    int cap = 0;
+    if (int rc = adaptive_stage(r, T, n, &cap)) return rc;
+    HIP_TRY(hipEventRecord(e0, st));
+    if (int rc = adaptive_launch(r, S, T, seeds, n, 0, cap)) return rc;
+    HIP_TRY(hipEventRecord(e1, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    r->ad_ms += ms;
+    r->ad_rounds += 1;
     return CHUNKY_OK;
 }
 

@@ -96,6 +96,13 @@ bool pool_kernel_applies(int variant, const SceneView& S, const RenderOpts& O, b
 hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                          const PassSeeds& P, float* res, int* work_counter, hipStream_t stream,
                          KernelChoice* chosen = nullptr, float* staging = nullptr, const int* seeds_dev = nullptr);
+// launch_render with the launch's samples folded by fold_stats_kernel (adaptive.hip) in place of fold_kernel: fold_stats holds two
+// floats per pixel of the image, the luminance statistic that kernel updates beside the running mean.  render_pool only
+// (hipErrorNotSupported under the other kernels, which stage no samples); fold_stats == nullptr is launch_render.  Weak for the same
+// reason as launch_aov below.
+__attribute__((weak)) hipError_t launch_render_stats(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
+                                                     const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
+                                                     float* staging, const int* seeds_dev, float* fold_stats);
 // the kernels behind render_pool (render_fallback.hip): render_waves, render_lanes
 hipError_t launch_fallback(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                            const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen);
@@ -131,6 +138,18 @@ constexpr int kDenoisePacked = 1;  // 16-byte words per pixel, written by a pack
 inline size_t denoise_work_bytes(int width, int height) { return (size_t)width * height * 64; }  // enough for either form (packed: two colour planes + two guide planes of float4)
 __attribute__((weak)) hipError_t launch_denoise(int form, int width, int height, const float* color, const float* albedo, const float* normal, const ::DnCoeffs& K,
                                                 float* out, void* work, size_t work_bytes, hipStream_t stream, int* launches);
+// Adaptive sampling (adaptive.hip; specification: adaptive_spec.h).  Weak for the same reason as launch_aov: where adaptive.hip is not
+// linked in, the adaptive entry points fail with CHUNKY_E_STATE.
+// fold_kernel's running mean over the staged samples of n_tiles tiles of shard T, and the Welford update of stat (2 floats per pixel)
+__attribute__((weak)) hipError_t launch_fold_stats(const float* staging, float* res, float* stat, const ShardView& T, int width, int height, long long n_tiles,
+                                                   int n_passes, int first_spp, hipStream_t stream);
+// the check after n passes: unconverged flags (unconv), activity (active; pixels that leave get count = n), then the active pixels in
+// whole-image pool-slot order in `list` and their number in *total.  active / unconv: width * height bytes; count / list: width * height
+// ints; tile_counts / tile_offsets: one int per 16 x 16 tile; all on the device
+__attribute__((weak)) hipError_t launch_adaptive_check(int width, int height, const float* stat, unsigned char* active, unsigned char* unconv, int* count, int n,
+                                                       float t2, float floor_, int* tile_counts, int* tile_offsets, int* list, int* total, hipStream_t stream);
+// pixels still active record n
+__attribute__((weak)) hipError_t launch_adaptive_finish(int n_pixels, const unsigned char* active, int* count, int n, hipStream_t stream);
 // thresholds: 256 floats on the device (capi.hip gamma_thresholds) or null = evaluate pow per channel
 hipError_t launch_filter(long long n_pixels, float exposure, const double* in, unsigned* out, int type, hipStream_t stream,
                          const float* thresholds = nullptr);

@@ -519,7 +519,7 @@ __global__ void __launch_bounds__(256) clear_foreign_kernel(ShardView T, int wid
 // the generic tree form only).
 static hipError_t launch_pool(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
-                              float* staging, const int* seeds_dev) {
+                              float* staging, const int* seeds_dev, float* fold_stats = nullptr) {
     const int block = 256;
     int n_cu = 0;
     if (hipError_t e = current_device_cus(&n_cu)) return e;
@@ -623,6 +623,10 @@ static hipError_t launch_pool(int variant, const SceneView& S, const CameraView&
     hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, stream, A);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
+    if (fold_stats) {  // adaptive sampling: the same running mean, and the pixels' luminance statistic from the same read
+        if (!launch_fold_stats) return hipErrorNotSupported;
+        return launch_fold_stats(staging, res, fold_stats, T, C.width, C.height, n_tiles, P.n, P.first_spp, stream);
+    }
     const long long threads = 3ll * n_tiles * kSampleTile;
     hipLaunchKernelGGL(fold_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, (const float*)staging, res, T,
                        C.width * C.height, C.width, n_tiles * kSampleTile, P.n, P.first_spp);
@@ -643,10 +647,16 @@ bool pool_kernel_applies(int variant, const SceneView& S, const RenderOpts& O, b
 hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                          const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
                          float* staging, const int* seeds_dev) {
+    return launch_render_stats(variant, S, C, O, T, P, res, work_counter, stream, chosen, staging, seeds_dev, nullptr);
+}
+hipError_t launch_render_stats(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
+                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
+                               float* staging, const int* seeds_dev, float* fold_stats) {
     if (pool_kernel_applies(variant, S, O, work_counter && staging)) {
         if (P.n > kMaxPoolPasses || (P.n > kMaxPassesPerLaunch && !seeds_dev)) return hipErrorInvalidValue;
-        return launch_pool(variant, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr);
+        return launch_pool(variant, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr, fold_stats);
     }
+    if (fold_stats) return hipErrorNotSupported;  // only render_pool stages samples
     if (P.n > kMaxPassesPerLaunch) return hipErrorInvalidValue;
     if (T.world != 1 && T.tile == 0) {
         // shards of 16 x 16 blocks are mapped by render_pool only: the other kernels take the rank's pixels as a list

@@ -18,7 +18,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("CHUNKY_HIP_LIB") or os.path.join(PKG_DIR, "libchunky_hip.so")  # override: tuning builds (tools/variants.sh)
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
-SOURCES = ["render_pool.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "denoise.hip", "capi.hip", "widetree.cpp"]
+SOURCES = ["render_pool.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "denoise.hip", "adaptive.hip", "capi.hip", "widetree.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
 
 MAX_TRACES = 10
@@ -140,6 +140,21 @@ class DenoiseParams(C.Structure):
                 ("sigma_albedo", C.c_float), ("flags", C.c_uint32)]
 
 
+class AdaptiveParams(C.Structure):
+    """chunky_adaptive_params (include/chunky_hip.h)."""
+    _fields_ = [("size", C.c_size_t), ("threshold", C.c_float), ("floor", C.c_float), ("min_spp", C.c_int32), ("check_interval", C.c_int32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+ADAPTIVE_MAX_CHECKS = 64
+
+
+class AdaptiveSummary(C.Structure):
+    """chunky_adaptive_summary (include/chunky_hip.h)."""
+    _fields_ = [("rounds", C.c_int32), ("checks", C.c_int32), ("passes", C.c_int32), ("reserved", C.c_int32), ("samples", C.c_int64),
+                ("active", C.c_int32 * ADAPTIVE_MAX_CHECKS)]
+
+
 def lib() -> C.CDLL:
     global _lib
     if _lib is None:
@@ -199,6 +214,13 @@ def lib() -> C.CDLL:
             "chunky_render_denoise": [vp, C.POINTER(DenoiseParams), vp, i64],
             "chunky_render_denoise_kernel_time": [vp, C.POINTER(f32), C.POINTER(C.c_int)],
             "chunky_denoise_exp": [vp, C.c_int, vp],
+            "chunky_adaptive_default_params": [C.POINTER(AdaptiveParams)],
+            "chunky_adaptive_host": [C.c_int, C.c_int, vp, C.c_int, C.POINTER(AdaptiveParams), vp, vp, vp],
+            "chunky_render_adaptive": [vp, vp, C.c_int, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveSummary)],
+            "chunky_render_adaptive_counts": [vp, vp, i64],
+            "chunky_render_adaptive_noise": [vp, vp, i64],
+            "chunky_render_adaptive_kernel_time": [vp, C.POINTER(f32), C.POINTER(C.c_int)],
+            "chunky_selftest_render_list": [vp, vp, C.c_int, vp, C.c_int],
             "chunky_render_run": [vp, vp, C.POINTER(i32), i32, i32, POST_RENDER_FN, vp],
             "chunky_render_run_ex": [vp, vp, C.POINTER(i32), i32, i32, C.POINTER(RunCallbacks)],
             "chunky_java_random_ints": [i64, vp, C.c_int],
@@ -302,3 +324,34 @@ def denoise_exp(x) -> np.ndarray:
     out = np.zeros(x.size, np.float32)
     check(lib().chunky_denoise_exp(ptr(x), x.size, ptr(out)))
     return out
+
+
+def adaptive_params(threshold: Optional[float] = None, floor: Optional[float] = None, min_spp: Optional[int] = None,
+                    check_interval: Optional[int] = None) -> AdaptiveParams:
+    """chunky_adaptive_default_params with the given members replaced."""
+    p = AdaptiveParams()
+    check(lib().chunky_adaptive_default_params(C.byref(p)))
+    if threshold is not None:
+        p.threshold = float(threshold)
+    if floor is not None:
+        p.floor = float(floor)
+    if min_spp is not None:
+        p.min_spp = int(min_spp)
+    if check_interval is not None:
+        p.check_interval = int(check_interval)
+    return p
+
+
+def adaptive_host(samples, params: Optional[AdaptiveParams] = None):
+    """chunky_adaptive_host: the specification of adaptive sampling evaluated on the host (no device needed).  samples: (n, height,
+    width, 3) float32, the sample of every pass.  Returns (counts (h, w) int32, image (h, w, 3), noise (h, w, 2) = (m, M2))."""
+    s = np.ascontiguousarray(samples, np.float32)
+    if s.ndim != 4 or s.shape[3] != 3:
+        raise ValueError(f"expected samples of shape (n, height, width, 3), got {s.shape}")
+    n, h, w, _ = s.shape
+    p = params if params is not None else adaptive_params()
+    counts = np.zeros((h, w), np.int32)
+    mean = np.zeros((h, w, 3), np.float32)
+    stat = np.zeros((h, w, 2), np.float32)
+    check(lib().chunky_adaptive_host(w, h, ptr(s), n, C.byref(p), ptr(counts), ptr(mean), ptr(stat)))
+    return counts, mean, stat

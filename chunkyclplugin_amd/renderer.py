@@ -356,6 +356,41 @@ class HipPathTracingRenderer:
         check(native.lib().chunky_render_denoise_kernel_time(self._h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    # --- adaptive sampling (chunky_render_adaptive) ---------------------------------------------------
+    def render_adaptive(self, seeds, params=None):
+        """Renders until every pixel's noise estimate is under params.threshold or len(seeds) passes are done (blocking; resets the
+        target first).  Returns (image (h, w, 3), counts (h, w) int32, noise (h, w, 2) = Welford (m, M2) of luminance, summary dict)."""
+        s = np.ascontiguousarray(seeds, np.int32)
+        p = params if params is not None else native.adaptive_params()
+        summ = native.AdaptiveSummary()
+        check(native.lib().chunky_render_adaptive(self._h, ptr(s), s.size, C.byref(p), C.byref(summ)))
+        image = self.read().reshape(self.height, self.width, 3)
+        summary = {"rounds": summ.rounds, "checks": summ.checks, "passes": summ.passes, "samples": summ.samples,
+                   "active": [int(a) for a in summ.active[:min(summ.checks, native.ADAPTIVE_MAX_CHECKS)]]}
+        return image, self.adaptive_counts(), self.adaptive_noise(), summary
+
+    def adaptive_counts(self) -> np.ndarray:
+        out = np.empty((self.height, self.width), np.int32)
+        check(native.lib().chunky_render_adaptive_counts(self._h, ptr(out), out.size))
+        return out
+
+    def adaptive_noise(self) -> np.ndarray:
+        out = np.empty((self.height, self.width, 2), np.float32)
+        check(native.lib().chunky_render_adaptive_noise(self._h, ptr(out), out.size))
+        return out
+
+    def adaptive_kernel_time(self):
+        """(milliseconds, rounds) of the adaptive runs since the last call: render launches, folds, checks and compactions."""
+        ms, n = C.c_float(), C.c_int()
+        check(native.lib().chunky_render_adaptive_kernel_time(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def render_list(self, pixels, seeds) -> None:
+        """chunky_selftest_render_list: len(seeds) passes on the listed pixel indices only, through the list route of the adaptive rounds."""
+        px = np.ascontiguousarray(pixels, np.int32)
+        s = np.ascontiguousarray(seeds, np.int32)
+        check(native.lib().chunky_selftest_render_list(self._h, ptr(px), px.size, ptr(s), s.size))
+
     def render(self, sample_buffer: np.ndarray, scene_spp: int, target_spp: int, merge_interval: int = 1024) -> int:
         """The pass loop of OpenClPathTracingRenderer.render (:95-184) run natively; merges into the
         caller's double sample buffer and returns the new scene.spp."""
@@ -436,3 +471,23 @@ class HipPostProcessingFilter:
         check(native.lib().chunky_filter_frame_device(self.instance._h, n_pixels, float(np.float32(exposure)), C.c_void_p(d_input),
                                                       C.c_void_p(d_argb), self.type, repeat, C.byref(ms)))
         return ms.value
+
+
+def adaptive_host(samples, params=None):
+    """The specification of adaptive sampling on the host (native.adaptive_host): (counts, image, noise) for per-pass samples."""
+    return native.adaptive_host(samples, params)
+
+
+def pool_slot_order(width: int, height: int) -> np.ndarray:
+    """Every pixel index of a width x height image in whole-image pool-slot order — 16 x 16 tiles row-major, 2 x 2 sub-blocks row-major
+    inside a tile, row-major inside a sub-block (csrc/path_state.hpp pool_slot_gid with one rank), padding slots left out: the order of
+    the active list chunky_render_adaptive builds."""
+    bw, bh = (width + 15) // 16, (height + 15) // 16
+    i = np.arange(256)
+    sb, px = i // 4, i % 4
+    dx, dy = (sb % 8) * 2 + px % 2, (sb // 8) * 2 + px // 2
+    b = np.arange(bw * bh)
+    x = ((b % bw) * 16)[:, None] + dx[None, :]
+    y = ((b // bw) * 16)[:, None] + dy[None, :]
+    keep = (x < width) & (y < height)
+    return (y * width + x)[keep].astype(np.int32)

@@ -395,6 +395,92 @@ int chunky_render_denoise_kernel_time(chunky_render* r, float* total_ms, int* la
 /* The filter's e^(-x) (x >= 0) evaluated on the host for n values: the instrument of its accuracy test. */
 int chunky_denoise_exp(const float* x, int n, float* out);
 
+/* ---- adaptive sampling: pixels stop when their noise estimate falls under a threshold; the rest are rendered from a list ----
+ * No counterpart in the reference (it renders every pass on every pixel).  The arithmetic is chunkyclplugin_amd/csrc/adaptive_spec.h,
+ * compiled by the kernels and the host alike; every operation is ONE exactly rounded float operation, no multiply-add is fused.
+ *
+ * State per pixel: n_p, the passes folded so far; the running-mean colour (the framebuffer, folded as K/rayTracer.cl:109-112:
+ * mean = (mean * (float)k + c) / (float)(k + 1)); a Welford pair (m, M2) on luminance, both 0 at the start.
+ *
+ * Update for the sample c = (r, g, b) of pass k (k counted from 0, passes taken in order):
+ *     y  = (r * 0.2126f + g * 0.7152f) + b * 0.0722f
+ *     d  = y - m
+ *     m  = m + d / (float)(k + 1)
+ *     M2 = M2 + d * (y - m)                                    (the m just updated)
+ *
+ * Convergence test, applied only after n = min_spp + j * check_interval passes (j = 0, 1, ...) while n < max_spp (a check after
+ * the last pass would change no result and is not run):
+ *     b   = m > floor ? m : floor
+ *     lim = ((t2 * ((float)n * (float)(n - 1))) * b) * b       with t2 = threshold * threshold, one float product made on the host
+ *     the pixel is UNCONVERGED iff it is active and M2 > lim.
+ * A pixel whose m or M2 is not finite (NaN or infinite) is converged: one bad pixel cannot hold a frame to max_spp.  The test reads
+ * "relative standard error of the mean luminance > threshold": M2 / (n (n - 1)) is the variance of the mean.
+ *
+ * Activity: all pixels start active.  At a check a pixel stays active iff it was active and some pixel of its 3 x 3 neighbourhood,
+ * clipped to the image, is unconverged (inactive pixels are never unconverged).  An inactive pixel never becomes active again, so
+ * every active pixel has seen exactly the passes rendered so far.  A pixel that leaves at the check after n passes records n_p = n;
+ * pixels still active after max_spp passes record max_spp.
+ *
+ * Result: pixel p of the framebuffer is, bit for bit, pixel p of chunky_render_passes(seeds[0 .. n_p), first_buffer_spp = 0) from a
+ * reset target; count[p] = n_p; (m, M2)[p] is the Welford state after n_p samples.
+ *
+ * threshold = 0 renders max_spp passes wherever M2 > 0 (a pixel with M2 == 0, e.g. a constant one, converges at the first check). */
+typedef struct chunky_adaptive_params {
+    size_t size;            /* sizeof(chunky_adaptive_params) as the caller was compiled (members may be appended) */
+    float threshold;        /* finite, >= 0: relative standard error of the mean luminance under which a pixel is converged */
+    float floor;            /* finite, > 0: the least luminance the error is taken relative to (dark pixels) */
+    int32_t min_spp;        /* >= 2: passes before the first check */
+    int32_t check_interval; /* >= 1: passes between checks */
+    uint32_t flags;         /* no bit is defined yet: must be 0 */
+    uint32_t reserved;      /* ignored */
+} chunky_adaptive_params;
+/* Fills the defaults: threshold 0.05, floor 0.01, min_spp 16, check_interval 16.  The threshold is a PLACEHOLDER that has not been
+ * tuned on the device yet (DESIGN.md section 13 says what is missing): set it yourself until it is. */
+int chunky_adaptive_default_params(chunky_adaptive_params* p);
+
+/* What one chunky_render_adaptive call did.  active[i] = active pixels after the i-th check, for the first
+ * CHUNKY_ADAPTIVE_MAX_CHECKS checks; `checks` counts all of them (it may exceed the array). */
+#define CHUNKY_ADAPTIVE_MAX_CHECKS 64
+typedef struct chunky_adaptive_summary {
+    int32_t rounds;   /* rounds of passes rendered (the first of min_spp passes, the others of check_interval or what was left) */
+    int32_t checks;   /* checks run */
+    int32_t passes;   /* passes rendered on the pixels that stayed to the end (<= max_spp) */
+    int32_t reserved;
+    int64_t samples;  /* samples rendered: the sum of count[p] over the image */
+    int32_t active[CHUNKY_ADAPTIVE_MAX_CHECKS];
+} chunky_adaptive_summary;
+
+/* The specification as code: needs no context and no device.  samples = n images [n][height][width][3], the sample of pass k of every
+ * pixel; n is max_spp.  count_out: width * height; mean_out: 3 * width * height, the running mean at each pixel's n_p; stat_out:
+ * 2 * width * height, (m, M2) per pixel.  Any output may be NULL.  CHUNKY_E_INVALID for: a params.size smaller than the first version
+ * of the struct, a threshold that is not finite or < 0, a floor that is not finite and > 0, min_spp < 2, check_interval < 1, unknown
+ * flag bits, n < min_spp. */
+int chunky_adaptive_host(int width, int height, const float* samples, int n, const chunky_adaptive_params* params,
+                         int32_t* count_out, float* mean_out, float* stat_out);
+
+/* Renders adaptively, blocking: resets the framebuffer and the adaptive state, then runs rounds — min_spp passes, then check_interval
+ * at a time, pass k with seeds[k] — each followed by a check, until no pixel is active or max_spp passes are done.  While every pixel
+ * is active a round is an ordinary launch; afterwards the active pixels are rendered from a list built on the device in the order of
+ * the kernel's pixel slots (the same list on every run).  summary_out may be NULL.  Afterwards chunky_render_read,
+ * chunky_render_denoise and the AOV calls see the adaptive image like any other; the target's shard and options are untouched.
+ * Parameter errors as chunky_adaptive_host (max_spp in the place of n).  CHUNKY_E_STATE, never a fallback: a group's target, a target
+ * with a shard of world > 1, and a scene / option set that the staged-sample kernel (render_pool) does not take — the statistic is
+ * computed from the staged samples, which only that kernel writes. */
+int chunky_render_adaptive(chunky_render* r, const int32_t* seeds, int max_spp, const chunky_adaptive_params* params,
+                           chunky_adaptive_summary* summary_out);
+/* The maps of the last adaptive run: count[p] (n must be width * height) and (m, M2)[p] (n_floats must be 2 * width * height).
+ * CHUNKY_E_STATE before any adaptive run on the target. */
+int chunky_render_adaptive_counts(chunky_render* r, int32_t* out, int64_t n);
+int chunky_render_adaptive_noise(chunky_render* r, float* out, int64_t n_floats);
+/* Device time of the adaptive runs since the last call — their render launches, folds, checks and compactions — and the number of
+ * rounds; apart from chunky_render_kernel_time, which does not see them. */
+int chunky_render_adaptive_kernel_time(chunky_render* r, float* total_ms, int* rounds);
+/* ---- self test of the list route: renders n passes (seeds[k], bufferSpp k) on the listed pixels only, through the launch the later
+ * rounds of chunky_render_adaptive use (the staged-sample kernel over a device-resident list of pixel indices), folding into the
+ * framebuffer as it is.  pixels: n_pixels distinct indices y * width + x in any order.  Blocking.  Same state errors as
+ * chunky_render_adaptive. */
+int chunky_selftest_render_list(chunky_render* r, const int32_t* pixels, int n_pixels, const int32_t* seeds, int n);
+
 /* ---- host pass loop (replaces OpenClPathTracingRenderer.render, J/opencl/OpenClPathTracingRenderer.java:54-191):
  * seeds from java.util.Random(0).nextInt(), bufferSpp restarting at 0 after each read-back, merge
  * sample = (sample*sampSpp + pass*passSpp) / (sampSpp+passSpp) in double (:167-173).
