@@ -3,6 +3,7 @@
 // J/opencl/renderer/{RendererInstance,ClSceneLoader}.java and J/opencl/OpenClPathTracingRenderer.java).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -22,6 +23,7 @@
 #include "kernels.hpp"
 #include "rccl_dyn.hpp"
 #include "rt_device.hpp"
+#include "scene_records.hpp"
 #include "widetree.hpp"
 
 using namespace chunky;
@@ -29,13 +31,28 @@ using namespace chunky;
 static_assert(sizeof(chunky_hit_record) == sizeof(HitRecord), "record layouts must agree");
 static_assert(CHUNKY_MAX_TRACES == kMaxTraces, "trace capacity must agree");
 
-// placement of the entity-BVH records (relayout_bvh_records): records in the breadth-first top, records per treelet; 0 = off
+// placement of the entity-BVH records (scene_records.cpp relayout_bvh_records): records in the breadth-first top, records per treelet; 0 = off
 #ifndef CHUNKY_BVH_TOP_RECORDS
 #define CHUNKY_BVH_TOP_RECORDS 0
 #endif
 #ifndef CHUNKY_BVH_TREELET_RECORDS
 #define CHUNKY_BVH_TREELET_RECORDS 0
 #endif
+// top / treelet sizes of relayout_bvh_records; CHUNKY_BVH_LAYOUT="top,treelet" overrides them for tuning runs ("0,0" = the
+// plain depth-first order of round 2)
+static void bvh_layout_params(int* top, int* treelet) {
+    *top = CHUNKY_BVH_TOP_RECORDS;
+    *treelet = CHUNKY_BVH_TREELET_RECORDS;
+#ifdef CHUNKY_TUNING
+    if (const char* e = getenv("CHUNKY_BVH_LAYOUT")) {
+        int a = 0, b = 0;
+        if (sscanf(e, "%d,%d", &a, &b) == 2 && a >= 0 && b >= 0) {
+            *top = a;
+            *treelet = b;
+        }
+    }
+#endif
+}
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local std::string tls_error;
@@ -84,6 +101,12 @@ struct DevBuf {
         p = nullptr;
         bytes = 0;
     }
+    hipError_t alloc(size_t n) {  // (contents undefined)
+        release();
+        const hipError_t e = hipMalloc(&p, n);
+        if (e == hipSuccess) bytes = n;
+        return e;
+    }
     hipError_t upload(const void* src, size_t n, hipStream_t s) {
         if (n != bytes || !p) {
             release();
@@ -127,6 +150,30 @@ struct chunky_scene {
     std::vector<chunky_scene*> replicas;  // on a group: the scene's copy on every member (this object holds no data)
 };
 
+// Device time of the launches of one kind on a render target: brackets of two events around each launch (or run of launches),
+// read and zeroed by the target's *_kernel_time call.  Events come from the target's pool and go back to it when a bracket has
+// been collected; a bracket that was opened and never closed (an error return in between) keeps its events for the next open.
+constexpr size_t kClockDrain = 4096;  // brackets a clock may hold before the call that adds more collects them first
+struct LaunchClock {
+    struct Bracket {
+        hipEvent_t e0, e1;
+        int weight;
+    };
+    std::vector<hipEvent_t>* pool;
+    std::vector<Bracket> pending;
+    hipEvent_t e0 = nullptr, e1 = nullptr;  // the open bracket
+    float ms = 0;
+    int count = 0;
+    explicit LaunchClock(std::vector<hipEvent_t>* pool_) : pool(pool_) {}
+    LaunchClock(const LaunchClock&) = delete;
+    ~LaunchClock();
+    bool full() const { return pending.size() > kClockDrain; }
+    int open(hipStream_t stream);
+    int close(hipStream_t stream, int weight = 1);
+    int collect();                      // waits for the closed brackets and adds them to ms / count
+    int take(float* ms_out, int* count_out);  // collect, report the totals since the last take, zero them
+};
+
 struct chunky_render {
     chunky_ctx* ctx = nullptr;
     chunky_scene* scene = nullptr;
@@ -141,10 +188,8 @@ struct chunky_render {
     DevBuf staging;  // render_pool: one launch's samples, [tile of 256 slots][pass][slot][3] floats
     DevBuf block_list;  // block shards under a kernel without the block mapping: this rank's pixels (ShardView::list)
     float* fb = nullptr;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;  // timing brackets of enqueued launches
-    std::vector<hipEvent_t> free_events;
-    float timed_ms = 0;
-    int timed_launches = 0;
+    std::vector<hipEvent_t> free_events;  // the one pool the four clocks below borrow from
+    LaunchClock clock{&free_events};      // the render launches (chunky_render_kernel_time)
     KernelChoice last_choice{0, 0, 0, 0, -1, 0};  // what the most recent launch ran (chunky_render_kernel_info)
     int launch_cap = 0;  // most passes one launch carries here (staging size); 0 = not determined yet
     int launch_cap_most = 0;  // ... determined for launches of at most this many passes (kMaxPassesPerLaunch / kMaxPoolPasses)
@@ -166,39 +211,21 @@ struct chunky_render {
     // kernel's claim counter; allocated (and zeroed) by the first AOV call.  Timing and the last instantiation are kept apart from
     // the render kernels' (chunky_render_kernel_time / _kernel_info do not see AOV launches)
     DevBuf aov;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> aov_pending;
-    float aov_ms = 0;
-    int aov_launches = 0;
+    LaunchClock aov_clock{&free_events};
     AovChoice aov_choice{0, 0, 0};
     int aov_last_launches = 0;  // launches of the most recent chunky_render_aov_passes
     // chunky_render_denoise: the filter's workspace (kept between calls) and its timing, apart from the render and AOV launches'
     DevBuf dn_work, dn_out;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> dn_pending;
-    std::vector<int> dn_pending_launches;
-    float dn_ms = 0;
-    int dn_launches = 0;
+    LaunchClock dn_clock{&free_events};  // (a bracket holds all launches of one call: their number is its weight)
     // chunky_render_adaptive: (m, M2) per pixel, the sample counts, the active / unconverged flags (a byte per pixel each), the tile
     // counts and offsets of the compaction with the total behind them, the active list, and the pinned word the total is read from;
     // allocated by the first adaptive call.  Its timing is kept apart from the other launches'
     DevBuf ad_stat, ad_count, ad_flags, ad_tiles, ad_list;
     int32_t* ad_total_host = nullptr;
     bool ad_valid = false;  // an adaptive run has finished: the maps can be read
-    float ad_ms = 0;
-    int ad_rounds = 0;
+    LaunchClock ad_clock{&free_events};  // one bracket per round
     ~chunky_render() {
         if (ad_total_host) (void)hipHostFree(ad_total_host);
-        for (auto& p : dn_pending) {
-            (void)hipEventDestroy(p.first);
-            (void)hipEventDestroy(p.second);
-        }
-        for (auto& p : pending) {
-            (void)hipEventDestroy(p.first);
-            (void)hipEventDestroy(p.second);
-        }
-        for (auto& p : aov_pending) {
-            (void)hipEventDestroy(p.first);
-            (void)hipEventDestroy(p.second);
-        }
         for (auto e : free_events) (void)hipEventDestroy(e);
         for (SeedSlot& s : seed_ring) {
             if (s.copied) (void)hipEventDestroy(s.copied);
@@ -364,8 +391,7 @@ static int group_probe_rccl(chunky_ctx* g, std::vector<DevBuf>& send, std::vecto
         HIP_TRY(hipSetDevice(m->device));
         HIP_TRY(send[i].upload(host.data(), count * 4, m->stream));  // (synchronises the member's stream)
         HIP_TRY(hipSetDevice(g->members[0]->device));
-        HIP_TRY(hipMalloc(&recv[i].p, count * 4));
-        recv[i].bytes = count * 4;
+        HIP_TRY(recv[i].alloc(count * 4));
         HIP_TRY(hipMemsetAsync(recv[i].p, 0, count * 4, g->members[0]->stream));
         devices.push_back(m->device);
         streams.push_back(m->stream);
@@ -711,30 +737,15 @@ extern "C" int chunky_scene_set_bvh(chunky_scene* scene, int which, const int32_
         memcpy(&f, &nodes[k], 4);
         empty = f != f;
     }
-    // height of the tree = most entries the to-visit stack can hold; also rejects child links that
-    // leave the array or form a cycle (a malformed BVH would hang the traversal)
+    // a malformed BVH would hang the traversal; the height bounds the to-visit stack
+    std::vector<int32_t> host(nodes, nodes + n);
     int height = 0;
-    if (!empty) {
-        std::vector<std::pair<int64_t, int>> todo;
-        todo.emplace_back(0, 0);
-        int64_t visited = 0;
-        while (!todo.empty()) {
-            auto [at, d] = todo.back();
-            todo.pop_back();
-            if (at < 0 || at + 7 > n || ++visited > n) return fail(CHUNKY_E_INVALID, "set_bvh: node link outside the array or cyclic");
-            if (d > height) height = d;
-            const int32_t head = nodes[at];
-            if (head > 0) {
-                todo.emplace_back(at + 7, d + 1);
-                todo.emplace_back((int64_t)head, d + 1);
-            }
-        }
-        if (height > 63) return fail(CHUNKY_E_INVALID, "set_bvh: tree deeper than the reference's 64-entry stack");
-    }
+    if (!empty && !bvh_links_height(host, &height))
+        return fail(CHUNKY_E_INVALID, "set_bvh: node link outside the array or cyclic, or a tree deeper than the reference's 64-entry stack");
     (which == CHUNKY_BVH_WORLD ? scene->world_height : scene->actor_height) = height;
     DevBuf& dst = which == CHUNKY_BVH_WORLD ? scene->world_bvh : scene->actor_bvh;
     HIP_TRY(dst.upload(nodes, (size_t)n * 4, scene->ctx->stream));
-    (which == CHUNKY_BVH_WORLD ? scene->host_world_bvh : scene->host_actor_bvh).assign(nodes, nodes + n);
+    (which == CHUNKY_BVH_WORLD ? scene->host_world_bvh : scene->host_actor_bvh).swap(host);
     scene->bvh_dirty = true;
     if (which == CHUNKY_BVH_WORLD) {
         scene->world_empty = empty;
@@ -754,9 +765,7 @@ extern "C" int chunky_scene_set_atlas(chunky_scene* scene, const uint8_t* rgba, 
     if (rgba) {
         HIP_TRY(scene->atlas.upload(rgba, bytes, scene->ctx->stream));
     } else {
-        scene->atlas.release();
-        HIP_TRY(hipMalloc(&scene->atlas.p, bytes));
-        scene->atlas.bytes = bytes;
+        HIP_TRY(scene->atlas.alloc(bytes));
         HIP_TRY(hipMemsetAsync(scene->atlas.p, 0, bytes, scene->ctx->stream));
         HIP_TRY(hipStreamSynchronize(scene->ctx->stream));
     }
@@ -795,12 +804,11 @@ extern "C" int chunky_scene_set_sky(chunky_scene* scene, const uint8_t* rgba, in
     return CHUNKY_OK;
 }
 
-static void list_emitters(const chunky_scene* s, std::vector<int32_t>* out);
 // The emitter list exists only for CHUNKY_OPT_EMITTER_NEE and chunky_scene_emitters: built on first use after a change.
 static int refresh_emitters(chunky_scene* s) {
     if (!s->emitters_dirty) return CHUNKY_OK;
     HIP_TRY(hipStreamSynchronize(s->ctx->stream));  // queued passes may still read the old list
-    list_emitters(s, &s->host_emitters);
+    list_emitters(s->host_octree, s->octree_depth, s->host_blocks, s->host_materials, &s->host_emitters);
     s->emitters.release();
     if (!s->host_emitters.empty()) HIP_TRY(s->emitters.upload(s->host_emitters.data(), s->host_emitters.size() * 4, s->ctx->stream));
     s->emitters_dirty = false;
@@ -827,201 +835,6 @@ extern "C" int chunky_scene_set_sun(chunky_scene* scene, const int32_t sun[6]) {
     return CHUNKY_OK;
 }
 
-static float bits_to_float(int32_t i) {
-    float f;
-    memcpy(&f, &i, 4);
-    return f;
-}
-
-// quad_aux (rt_device.hpp): for every quad of every quad model the block palette points at, the
-// ray-independent values of K/primitives.h:262-276 — normalize(cross(xv, yv)), dot(n, origin), dot(xv, xv),
-// dot(yv, yv) — written at the quad's own int offset.  Same rt_math.h expressions as the kernel, so
-// the stored floats are the ones the kernel would compute.  Returns false (no table) when two
-// models overlap in a way that would make entries collide, or a pointer leaves the array.
-static bool build_quad_aux(const std::vector<int32_t>& B, const std::vector<int32_t>& Q, std::vector<float>* out) {
-    out->assign(Q.size(), 0.0f);
-    std::vector<int64_t> owner(Q.size(), -1);
-    bool any = false;
-    for (size_t k = 0; k + 1 < B.size(); k += 2) {
-        if (B[k] != 3) continue;
-        const int64_t ptr = B[k + 1];
-        if (ptr < 0 || (size_t)ptr >= Q.size()) return false;
-        const int64_t count = Q[(size_t)ptr];
-        if (count < 0 || (size_t)(ptr + 1 + 15 * count) > Q.size()) return false;
-        for (int64_t i = 0; i < count; i++) {
-            const int64_t q = ptr + 1 + 15 * i;
-            for (int w = 0; w < 6; w++) {
-                if (owner[(size_t)(q + w)] >= 0 && owner[(size_t)(q + w)] != q) return false;
-                owner[(size_t)(q + w)] = q;
-            }
-            float f[9];
-            memcpy(f, &Q[(size_t)q], sizeof f);
-            const float cx = rt_cross_c(f[4], f[8], f[5], f[7]), cy = rt_cross_c(f[5], f[6], f[3], f[8]),
-                        cz = rt_cross_c(f[3], f[7], f[4], f[6]);
-            const float rl = rt_rlen3(cx, cy, cz);
-            const float nx = cx * rl, ny = cy * rl, nz = cz * rl;
-            float* a = out->data() + q;
-            a[0] = nx;
-            a[1] = ny;
-            a[2] = nz;
-            a[3] = rt_dot3(nx, ny, nz, f[0], f[1], f[2]);
-            a[4] = rt_dot3(f[3], f[4], f[5], f[3], f[4], f[5]);
-            a[5] = rt_dot3(f[6], f[7], f[8], f[6], f[7], f[8]);
-            any = true;
-        }
-    }
-    return any;
-}
-
-// How common model blocks are in a world: octree leaves whose block is an AABB or quad model (types 2, 3), per thousand leaves that
-// can be hit at all.  render_pool tests full cubes and model blocks in phases of their own where that pays: the model tests cost
-// three times the cube test and a wave runs them whenever ONE lane of a block test has a model block, but a class more costs every
-// iteration of every wave 1 % in bookkeeping.  Measured: the benchmark city (110 per thousand; 58 % of the block tests on its saved
-// view) +2.3 ... +2.8 %, the synthetic outdoor world (10) +0.1 ... +0.5 %, the same world 16 times larger -1.5 %, the indoor room
-// (0.3) -1 %: sorted from 30 per thousand on.  (CHUNKY_OPT_KERNEL bits 8 / 9 force it on / off.)
-constexpr int kSortBlocksPermille = 30;
-static int model_leaf_permille(const std::vector<int32_t>& T, const std::vector<int32_t>& B) {
-    int64_t cubes = 0, models = 0;
-    for (const int32_t v : T) {
-        if (v > 0) continue;  // a branch
-        const int64_t ptr = -(int64_t)v;
-        if (ptr == 0 || ptr + 1 >= (int64_t)B.size()) continue;  // air, ANY_TYPE, a pointer beyond the palette
-        const int32_t type = B[(size_t)ptr];
-        cubes += type == 1;
-        models += type == 2 || type == 3;
-    }
-    return cubes + models > 0 ? (int)(models * 1000 / (cubes + models)) : 0;
-}
-
-// Everything the kernels read that is derived from the four palettes (rt_device.hpp has the layouts):
-//   block_info  per block {type, pointer, 5 material words of a full cube, model record}
-//   mat8        materials at a 32-byte stride (two 16-byte reads instead of five unaligned dwords)
-//   aabb_rec    AABB-model boxes as three 16-byte words each, materials as mat8 indices
-//   quad_rec    quad-model quads as six 16-byte words each (the material's five words inline), with the ray-independent values of K/primitives.h:262-276
-//               (unit normal, its dot with the origin, |xv|^2, |yv|^2) evaluated here with the kernel's own rt_math.h
-// A block whose model cannot be re-laid out (pointer outside its palette, more than 255 primitives, a material pointer
-// that is not a whole material) keeps model record 0 and takes the path that reads the packed palettes as they are.
-// The host half of rebuild_derived: everything it derives from the four palettes, as plain vectors (no device call: this is the part
-// that reads caller-supplied ints, and tests/sanitize/capi_host_fuzz.cpp runs it under AddressSanitizer on hostile palettes).
-struct DerivedRecords {
-    std::vector<int32_t> info, mat8, aabb_rec, quad_rec;
-};
-static void derive_records(const std::vector<int32_t>& B, const std::vector<int32_t>& M, const std::vector<int32_t>& A, const std::vector<int32_t>& Q,
-                           DerivedRecords* out) {
-    const size_t n_blocks = B.size() / 2, n_mats = M.size() / 6;
-    std::vector<int32_t>&mat8 = out->mat8, &info = out->info, &aabb_rec = out->aabb_rec, &quad_rec = out->quad_rec;
-    mat8.assign(n_mats * 8, 0);
-    for (size_t m = 0; m < n_mats; m++)
-        for (int w = 0; w < 6; w++) mat8[m * 8 + w] = M[m * 6 + w];  // word 5 (spec | metal | rough) rides in the second word
-    auto mat_index = [&](int32_t ptr, int32_t* out) {  // packed material pointer -> index of its first 16-byte word in mat8
-        if (ptr < 0 || ptr % 6 != 0 || (size_t)ptr / 6 >= n_mats) return false;
-        *out = (ptr / 6) * 2;
-        return true;
-    };
-    info.assign(n_blocks * 8, 0);
-    aabb_rec.clear();
-    quad_rec.clear();
-    std::vector<int64_t> aabb_at(A.size(), -1), quad_at(Q.size(), -1);  // model pointer -> first record (models are shared between blocks)
-    for (size_t k = 0; k < n_blocks; k++) {
-        int32_t* e = &info[k * 8];
-        const int32_t type = B[2 * k], ptr = B[2 * k + 1];
-        e[0] = type;
-        e[1] = ptr;
-        if (type == 1) {
-            if (ptr >= 0 && (size_t)ptr + 5 <= M.size()) {
-                for (int w = 0; w < 5; w++) e[2 + w] = M[(size_t)ptr + w];
-                if ((size_t)ptr + 6 <= M.size()) e[7] = M[(size_t)ptr + 5];  // material word 5 (extensions)
-            } else {
-                e[0] = 0x7FFFFFFF;  // malformed cube: an unknown model type never hits (K/block.h:44-47)
-            }
-        } else if (type == 2 || type == 3) {
-            // A model whose pointer, primitive count or material pointers leave their palettes would make the kernels read outside
-            // device memory (the reference has no such check: its behaviour there is undefined).  Such a block never hits, like
-            // an unknown model type (K/block.h:44-47); every well-formed block is untouched by this.
-            const std::vector<int32_t>& P = type == 2 ? A : Q;
-            const int64_t stride = type == 2 ? 13 : 15;
-            bool sound = ptr >= 0 && (size_t)ptr < P.size();
-            if (sound) {
-                const int64_t count = P[(size_t)ptr];
-                sound = count >= 0 && (size_t)(ptr + 1 + stride * count) <= P.size();
-                for (int64_t i = 0; sound && i < count; i++) {
-                    const int32_t* prim = &P[(size_t)(ptr + 1 + stride * i)];
-                    if (type == 2) {
-                        for (int w = 1; w < 6 && sound; w++) sound = prim[7 + w] >= 0 && (size_t)prim[7 + w] + 6 <= M.size();  // E, S, W, T, B: the ones that are read
-                    } else {
-                        sound = prim[13] >= 0 && (size_t)prim[13] + 6 <= M.size();
-                    }
-                }
-            }
-            if (!sound) e[0] = 0x7FFFFFFF;
-        }
-        if (e[0] == 2) {
-            const int64_t count = A[(size_t)ptr];
-            if (count < 1 || count > 255) continue;
-            if (aabb_at[(size_t)ptr] < 0) {
-                const int64_t first = (int64_t)aabb_rec.size() / 12;
-                bool ok = true;
-                std::vector<int32_t> rec((size_t)count * 12);
-                for (int64_t i = 0; i < count && ok; i++) {
-                    const int32_t* b = &A[(size_t)(ptr + 1 + 13 * i)];
-                    int32_t* r = &rec[(size_t)i * 12];
-                    for (int w = 0; w < 7; w++) r[w] = b[w];  // six bounds, flags
-                    for (int w = 0; w < 5 && ok; w++) ok = mat_index(b[8 + w], &r[7 + w]);  // E, S, W, T, B (N is never read: K/primitives.h:209-234)
-                }
-                if (!ok) {
-                    aabb_at[(size_t)ptr] = -2;
-                } else {
-                    aabb_at[(size_t)ptr] = first;
-                    aabb_rec.insert(aabb_rec.end(), rec.begin(), rec.end());
-                }
-            }
-            if (aabb_at[(size_t)ptr] >= 0 && aabb_at[(size_t)ptr] < (1 << 22)) e[7] = (int32_t)((aabb_at[(size_t)ptr] << 8) | count);
-        } else if (e[0] == 3) {
-            const int64_t count = Q[(size_t)ptr];
-            if (count < 1 || count > 255) continue;
-            if (quad_at[(size_t)ptr] < 0) {
-                const int64_t first = (int64_t)quad_rec.size() / 24;
-                bool ok = true;
-                std::vector<int32_t> rec((size_t)count * 24);
-                for (int64_t i = 0; i < count && ok; i++) {
-                    const int32_t* q = &Q[(size_t)(ptr + 1 + 15 * i)];
-                    float f[9];
-                    memcpy(f, q, sizeof f);
-                    const float cx = rt_cross_c(f[4], f[8], f[5], f[7]), cy = rt_cross_c(f[5], f[6], f[3], f[8]),
-                                cz = rt_cross_c(f[3], f[7], f[4], f[6]);
-                    const float rl = rt_rlen3(cx, cy, cz);
-                    const float nx = cx * rl, ny = cy * rl, nz = cz * rl;
-                    const float aux[6] = {nx, ny, nz, rt_dot3(nx, ny, nz, f[0], f[1], f[2]), rt_dot3(f[3], f[4], f[5], f[3], f[4], f[5]),
-                                          rt_dot3(f[6], f[7], f[8], f[6], f[7], f[8])};
-                    int32_t a[6];
-                    memcpy(a, aux, sizeof a);
-                    int32_t* r = &rec[(size_t)i * 24];
-                    r[0] = q[0]; r[1] = q[1]; r[2] = q[2]; r[3] = a[3];      // origin, dot(n, origin)
-                    r[4] = q[3]; r[5] = q[4]; r[6] = q[5]; r[7] = a[4];      // xv, |xv|^2
-                    r[8] = q[6]; r[9] = q[7]; r[10] = q[8]; r[11] = a[5];    // yv, |yv|^2
-                    r[12] = q[9]; r[13] = q[10]; r[14] = q[11]; r[15] = q[12];  // uv
-                    r[16] = a[0]; r[17] = a[1]; r[18] = a[2];                // unit normal
-                    int32_t m8 = 0;
-                    ok = mat_index(q[13], &m8);                              // the quad's material, inline: one dependent read less
-                    if (ok && (M[(size_t)q[13]] & 2)) ok = false;          // an emittance texture needs the full word: packed path
-                    if (ok) {
-                        const int32_t* m = &M[(size_t)q[13]];
-                        r[19] = (m[4] & 0xFF) | (int32_t)((uint32_t)m[5] << 8);
-                        r[20] = m[0]; r[21] = m[1]; r[22] = m[2]; r[23] = m[3];
-                    }
-                }
-                if (!ok) {
-                    quad_at[(size_t)ptr] = -2;
-                } else {
-                    quad_at[(size_t)ptr] = first;
-                    quad_rec.insert(quad_rec.end(), rec.begin(), rec.end());
-                }
-            }
-            if (quad_at[(size_t)ptr] >= 0 && quad_at[(size_t)ptr] < (1 << 22)) e[7] = (int32_t)((quad_at[(size_t)ptr] << 8) | count);
-        }
-    }
-}
-
 static int rebuild_derived(chunky_scene* s) {
     const std::vector<int32_t>&B = s->host_blocks, &M = s->host_materials, &A = s->host_aabbs, &Q = s->host_quads;
     hipStream_t st = s->ctx->stream;
@@ -1043,255 +856,6 @@ static int rebuild_derived(chunky_scene* s) {
     std::vector<float> aux;  // for quads that kept the packed path
     if (build_quad_aux(B, Q, &aux)) HIP_TRY(s->quad_aux.upload(aux.data(), aux.size() * 4, st));
     return CHUNKY_OK;
-}
-
-// The two entity BVHs re-laid out for aligned 16-byte reads (rt_device.hpp has the layouts): every inner node becomes a
-// 64-byte record holding BOTH children (their references and boxes — what one visit of K/bvh.h:72-85 reads), every
-// triangle an 80-byte record with its material as a mat8 index.  A reference is the index of an inner record, or
-// -1 - (first triangle record << 6 | count) for a leaf.  The walk order, the tests and the arithmetic stay the reference's.
-// Returns false (no records: the packed arrays are walked as they are) when something does not fit: a leaf of more than
-// 63 triangles, a triangle pointer outside the palette, a material pointer that is not a whole material.
-// Placement of the inner records of one BVH (records [lo, hi) of bvh_rec, root reference *root): the first `top` records
-// breadth-first from the root (the levels every walk crosses, contiguous), then every subtree below that cut as depth-first
-// TREELETS of at most `treelet` records, each treelet breadth-first from its own root — a walker that enters a treelet finds
-// its next few visits in the same 1–2 KB.  References are renumbered; nothing else changes.
-static void relayout_bvh_records(std::vector<int32_t>* bvh_rec, size_t lo, size_t hi, int* root, int top, int treelet) {
-    if (hi <= lo || *root < 0) return;
-    const size_t n = hi - lo;
-    std::vector<int32_t> order;  // order[k] = old index of the record that moves to lo + k
-    order.reserve(n);
-    auto rec = [&](int32_t idx) { return &(*bvh_rec)[(size_t)idx * 16]; };
-    std::vector<int32_t> frontier{*root};
-    {   // the top, breadth-first
-        size_t head = 0;
-        while (head < frontier.size() && order.size() < (size_t)top) {
-            const int32_t at = frontier[head++];
-            order.push_back(at);
-            for (int c = 0; c < 2; c++)
-                if (rec(at)[c] >= 0) frontier.push_back(rec(at)[c]);
-        }
-        frontier.erase(frontier.begin(), frontier.begin() + (ptrdiff_t)head);
-    }
-    // below the cut: treelets, depth-first (a stack of treelet roots; the first child's treelet follows its parent's)
-    std::vector<int32_t> roots(frontier.rbegin(), frontier.rend()), members, next;
-    while (!roots.empty()) {
-        members.assign(1, roots.back());
-        roots.pop_back();
-        next.clear();
-        for (size_t head = 0; head < members.size(); head++) {
-            const int32_t at = members[head];
-            order.push_back(at);
-            for (int c = 0; c < 2; c++) {
-                const int32_t r = rec(at)[c];
-                if (r < 0) continue;
-                if (members.size() < (size_t)treelet) members.push_back(r); else next.push_back(r);
-            }
-        }
-        roots.insert(roots.end(), next.rbegin(), next.rend());
-    }
-    if (order.size() != n) return;  // (cannot happen: every record of the range hangs under the root exactly once)
-    std::vector<int32_t> where(n), moved(n * 16);
-    for (size_t k = 0; k < n; k++) where[(size_t)order[k] - lo] = (int32_t)(lo + k);
-    for (size_t k = 0; k < n; k++) {
-        const int32_t* from = rec(order[k]);
-        int32_t* to = &moved[k * 16];
-        std::copy(from, from + 16, to);
-        for (int c = 0; c < 2; c++)
-            if (to[c] >= 0) to[c] = where[(size_t)to[c] - lo];
-    }
-    std::copy(moved.begin(), moved.end(), bvh_rec->begin() + (ptrdiff_t)(lo * 16));
-    *root = where[(size_t)*root - lo];
-}
-
-// Triangle records in the order in which the inner records (as placed) refer to their leaves, so that the leaves under one
-// treelet lie together.  A leaf shared by several references moves once.
-static void reorder_triangles(std::vector<int32_t>* bvh_rec, std::vector<int32_t>* tri_rec, int* world_root, int* actor_root) {
-    const size_t n_tri = tri_rec->size() / 20;
-    std::vector<int32_t> moved;
-    moved.reserve(tri_rec->size());
-    std::vector<int32_t> first_at(n_tri + 1, -1);  // old first triangle of a leaf -> new
-    auto move_leaf = [&](int32_t* ref) {
-        if (*ref >= 0) return;
-        const int32_t l = -1 - *ref, first = l >> 6, count = l & 63;
-        if (count == 0 || (size_t)first + (size_t)count > n_tri) return;
-        if (first_at[(size_t)first] < 0) {
-            first_at[(size_t)first] = (int32_t)(moved.size() / 20);
-            moved.insert(moved.end(), tri_rec->begin() + (ptrdiff_t)first * 20, tri_rec->begin() + (ptrdiff_t)(first + count) * 20);
-        }
-        *ref = -1 - ((first_at[(size_t)first] << 6) | count);
-    };
-    move_leaf(world_root);
-    move_leaf(actor_root);
-    for (size_t k = 0; k < bvh_rec->size() / 16; k++) {
-        move_leaf(&(*bvh_rec)[k * 16]);
-        move_leaf(&(*bvh_rec)[k * 16 + 1]);
-    }
-    tri_rec->swap(moved);  // every reference now points into `moved`
-}
-
-// top / treelet sizes of relayout_bvh_records; CHUNKY_BVH_LAYOUT="top,treelet" overrides them for tuning runs ("0,0" = the
-// plain depth-first order of round 2)
-static void bvh_layout_params(int* top, int* treelet) {
-    *top = CHUNKY_BVH_TOP_RECORDS;
-    *treelet = CHUNKY_BVH_TREELET_RECORDS;
-#ifdef CHUNKY_TUNING
-    if (const char* e = getenv("CHUNKY_BVH_LAYOUT")) {
-        int a = 0, b = 0;
-        if (sscanf(e, "%d,%d", &a, &b) == 2 && a >= 0 && b >= 0) {
-            *top = a;
-            *treelet = b;
-        }
-    }
-#endif
-}
-
-static bool build_bvh_records(const chunky_scene* s, std::vector<int32_t>* bvh_rec, std::vector<int32_t>* tri_rec, int* world_root,
-                              int* actor_root) {
-    const std::vector<int32_t>&T = s->host_trigs, &M = s->host_materials;
-    const size_t n_mats = M.size() / 6;
-    std::vector<int64_t> leaf_at(T.size(), -1);  // triangle pointer -> its leaf reference (leaves may be shared)
-    auto leaf_ref = [&](int64_t prim, int32_t* ref) {
-        if (prim < 0 || (size_t)prim >= T.size()) return false;
-        if (leaf_at[(size_t)prim] >= 0) {
-            *ref = (int32_t)(-1 - leaf_at[(size_t)prim]);
-            return true;
-        }
-        const int64_t count = T[(size_t)prim];
-        if (count < 0 || count > 63 || (size_t)(prim + 1 + 20 * count) > T.size()) return false;
-        const int64_t first = (int64_t)tri_rec->size() / 20;
-        if (first >= (1 << 24)) return false;
-        for (int64_t i = 0; i < count; i++) {
-            const int32_t* t = &T[(size_t)(prim + 1 + 20 * i)];
-            const int32_t mp = t[19];
-            if (mp < 0 || mp % 6 != 0 || (size_t)mp / 6 >= n_mats) return false;
-            const int32_t r[20] = {t[1], t[2], t[3], t[0],             // e1, flags
-                                   t[4], t[5], t[6], (mp / 6) * 2,     // e2, material (mat8 index)
-                                   t[7], t[8], t[9], t[13],            // o, t1.u
-                                   t[10], t[11], t[12], t[14],         // n, t1.v
-                                   t[15], t[16], t[17], t[18]};        // t2.u, t2.v, t3.u, t3.v
-            tri_rec->insert(tri_rec->end(), r, r + 20);
-        }
-        leaf_at[(size_t)prim] = (first << 6) | count;
-        *ref = (int32_t)(-1 - leaf_at[(size_t)prim]);
-        return true;
-    };
-    auto build = [&](const std::vector<int32_t>& N, bool empty, int* root) {
-        *root = 0;
-        if (empty || N.size() < 7) return true;
-        // reference of the node at int offset `at`: inner nodes get records in visiting (depth-first) order
-        struct Job { int64_t at; int32_t* slot; };
-        std::vector<std::pair<int64_t, int64_t>> todo;  // (node offset, index of the int in bvh_rec that receives its reference)
-        int32_t root_ref = 0;
-        // iterative: slot index -1 means the root reference
-        todo.emplace_back(0, -1);
-        int64_t guard = 0;
-        while (!todo.empty()) {
-            auto [at, slot] = todo.back();
-            todo.pop_back();
-            if (at < 0 || (size_t)at + 7 > N.size() || ++guard > (int64_t)N.size()) return false;
-            const int32_t head = N[(size_t)at];
-            int32_t ref;
-            if (head <= 0) {
-                if (!leaf_ref(-(int64_t)head, &ref)) return false;
-            } else {
-                const int64_t a = at + 7, b = head;
-                if ((size_t)a + 7 > N.size() || b < 0 || (size_t)b + 7 > N.size()) return false;
-                const int64_t idx = (int64_t)bvh_rec->size() / 16;
-                if (idx >= (1 << 24)) return false;  // (with at most 2^24 triangles: every record within 32-bit byte offsets)
-                ref = (int32_t)idx;
-                bvh_rec->resize(bvh_rec->size() + 16, 0);
-                int32_t* r = &(*bvh_rec)[(size_t)idx * 16];
-                for (int w = 0; w < 6; w++) {
-                    r[4 + w] = N[(size_t)a + 1 + w];    // first child's box  (words 1, 2.xy)
-                    r[10 + w] = N[(size_t)b + 1 + w];   // second child's box (words 2.zw, 3)
-                }
-                todo.emplace_back(b, idx * 16 + 1);
-                todo.emplace_back(a, idx * 16 + 0);
-            }
-            if (slot < 0) root_ref = ref; else (*bvh_rec)[(size_t)slot] = ref;
-        }
-        *root = root_ref;
-        return true;
-    };
-    bvh_rec->clear();
-    tri_rec->clear();
-    if (!build(s->host_world_bvh, s->world_empty, world_root)) return false;
-    const size_t world_records = bvh_rec->size() / 16;
-    if (!build(s->host_actor_bvh, s->actor_empty, actor_root)) return false;
-    // where the records sit (addresses only: the walk's order, tests and arithmetic do not see it)
-    int top = 0, treelet = 0;
-    bvh_layout_params(&top, &treelet);
-    if (treelet > 1) {
-        relayout_bvh_records(bvh_rec, 0, world_records, world_root, top, treelet);
-        relayout_bvh_records(bvh_rec, world_records, bvh_rec->size() / 16, actor_root, top, treelet);
-        reorder_triangles(bvh_rec, tri_rec, world_root, actor_root);
-    }
-    return true;
-}
-
-// Every leaf of an entity BVH has to lie inside the triangle palette, every triangle's material inside the material palette: the
-// kernels follow these ints as they are (the reference does too — with hostile data its reads are undefined; here the render call
-// is refused instead).  Node links were checked by chunky_scene_set_bvh.
-static bool bvh_leaves_sound(const std::vector<int32_t>& N, bool empty, const std::vector<int32_t>& T, const std::vector<int32_t>& M) {
-    if (empty || N.size() < 7) return true;
-    std::vector<int64_t> todo{0};  // the nodes the walk can reach (first child at +7, second at node[0]: K/bvh.h:72-85)
-    size_t visited = 0;
-    while (!todo.empty()) {
-        const int64_t at = todo.back();
-        todo.pop_back();
-        if (at < 0 || (size_t)at + 7 > N.size() || ++visited > N.size()) return false;
-        const int32_t head = N[(size_t)at];
-        if (head > 0) {
-            todo.push_back(at + 7);
-            todo.push_back((int64_t)head);
-            continue;
-        }
-        const int64_t prim = -(int64_t)head;
-        if ((size_t)prim >= T.size()) return false;
-        const int64_t count = T[(size_t)prim];
-        if (count < 0 || (size_t)(prim + 1 + 20 * count) > T.size()) return false;
-        for (int64_t i = 0; i < count; i++) {
-            const int32_t mp = T[(size_t)(prim + 20 + 20 * i)];  // word 19 of the triangle
-            if (mp < 0 || (size_t)mp + 6 > M.size()) return false;
-        }
-    }
-    return true;
-}
-
-// The emitter list of the next-event-estimation extension (same rule and order as oracle/port.c
-// port_list_emitters): every octree leaf whose block is a full cube with a non-zero emittance byte and no emittance
-// texture, in pre-order (children in index order), as {x, y, z, level << 25 | block pointer}.
-static void list_emitters(const chunky_scene* s, std::vector<int32_t>* out) {
-    out->clear();
-    const std::vector<int32_t>&T = s->host_octree, &B = s->host_blocks, &M = s->host_materials;
-    if (T.empty() || s->octree_depth < 0 || s->octree_depth > 15) return;
-    struct Item { int64_t node; int x, y, z, level; };
-    std::vector<Item> todo{{0, 0, 0, 0, s->octree_depth}};
-    // chunky_scene_set_octree only checks that branch values stay inside the array: a tree with a cycle, or with branches
-    // below level 0, must not make this walk run or allocate without end — the kernels' walk is bounded by the depth, so
-    // here a node at level 0 is a leaf whatever it holds, and no more nodes are visited than the array has
-    size_t visited = 0;
-    while (!todo.empty()) {
-        const Item it = todo.back();
-        todo.pop_back();
-        if (++visited > T.size()) break;
-        const int32_t v = T[(size_t)it.node];
-        if (v > 0 && it.level > 0) {
-            const int h = 1 << (it.level - 1);
-            for (int c = 7; c >= 0; c--)  // pushed in reverse: popped in index order
-                todo.push_back({(int64_t)v + c, it.x + ((c >> 2) & 1) * h, it.y + ((c >> 1) & 1) * h, it.z + (c & 1) * h, it.level - 1});
-            continue;
-        }
-        if (v > 0) continue;  // a branch below level 0: not a leaf the kernels can reach
-        const int64_t block = -(int64_t)v;
-        if (block == 0 || block == 0x7FFFFFFE || block + 1 >= (int64_t)B.size() || block >= (1 << 25)) continue;
-        if (B[(size_t)block] != 1) continue;
-        const int64_t mp = B[(size_t)block + 1];
-        if (mp < 0 || (size_t)mp + 6 > M.size()) continue;
-        if ((M[(size_t)mp] & 2) || (M[(size_t)mp + 4] & 0xFF) == 0) continue;
-        const int32_t rec[4] = {it.x, it.y, it.z, (int32_t)((it.level << 25) | (int32_t)block)};
-        out->insert(out->end(), rec, rec + 4);
-    }
 }
 
 // Assemble the kernel-side view; Sun_new (K/sky.h:19-40) is evaluated here, on the host, with the
@@ -1360,7 +924,11 @@ static int scene_view(chunky_scene* s, SceneView* v, bool want_emitters = false)
             !bvh_leaves_sound(s->host_actor_bvh, s->actor_empty, s->host_trigs, s->host_materials))
             return fail(CHUNKY_E_INVALID, "an entity BVH leaf or a triangle's material lies outside its palette");
         std::vector<int32_t> nodes, tris;
-        if ((!s->world_empty || !s->actor_empty) && build_bvh_records(s, &nodes, &tris, &s->world_root, &s->actor_root)) {
+        int top = 0, treelet = 0;  // where the records sit (addresses only: the walk's order, tests and arithmetic do not see it)
+        bvh_layout_params(&top, &treelet);
+        if ((!s->world_empty || !s->actor_empty) &&
+            build_bvh_records(s->host_world_bvh, s->world_empty, s->host_actor_bvh, s->actor_empty, s->host_trigs, s->host_materials, top, treelet,
+                              &nodes, &tris, &s->world_root, &s->actor_root)) {
             if (nodes.empty()) nodes.resize(16, 0);  // both roots are leaves
             tris.resize(tris.size() + 20, 0);        // a step at the end of the last leaf reads one record past it
             // ONE allocation — nodes, then triangles — so the walk addresses either kind of record as a 32-bit byte offset off
@@ -1461,13 +1029,11 @@ extern "C" int chunky_render_create(chunky_ctx* ctx, chunky_scene* scene, int wi
     r->width = width;
     r->height = height;
     size_t bytes = (size_t)width * height * 3 * sizeof(float);
-    HIP_TRY(hipMalloc(&r->own_fb.p, bytes));
-    r->own_fb.bytes = bytes;
+    HIP_TRY(r->own_fb.alloc(bytes));
     r->fb = (float*)r->own_fb.p;
     HIP_TRY(hipMemsetAsync(r->fb, 0, bytes, ctx->stream));
     // [0] the sample / pixel queue, [2..49] the phase profile, [64..127] render_pool's range counters (render_pool.hip xcd_claim)
-    HIP_TRY(hipMalloc(&r->work_counter.p, 512));
-    r->work_counter.bytes = 512;
+    HIP_TRY(r->work_counter.alloc(512));
     HIP_TRY(hipMemsetAsync(r->work_counter.p, 0, 512, ctx->stream));
     r->shard = ShardView{0, 1, 256, width * height};
     scene->refs++;
@@ -1651,41 +1217,94 @@ extern "C" int chunky_render_reset(chunky_render* r) {
     return CHUNKY_OK;
 }
 
-static hipError_t get_event(chunky_render* r, hipEvent_t* e) {
-    if (!r->free_events.empty()) {
-        *e = r->free_events.back();
-        r->free_events.pop_back();
-        return hipSuccess;
+LaunchClock::~LaunchClock() {
+    for (Bracket& b : pending) {
+        (void)hipEventDestroy(b.e0);
+        (void)hipEventDestroy(b.e1);
     }
-    return hipEventCreate(e);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
 }
 
-static int collect_timing(chunky_render* r) {
-    for (auto& p : r->pending) {
-        float ms = 0;
-        HIP_TRY(hipEventSynchronize(p.second));
-        HIP_TRY(hipEventElapsedTime(&ms, p.first, p.second));
-        r->timed_ms += ms;
-        r->timed_launches += 1;
-        r->free_events.push_back(p.first);
-        r->free_events.push_back(p.second);
+int LaunchClock::open(hipStream_t stream) {
+    for (hipEvent_t* e : {&e0, &e1}) {
+        if (*e) continue;  // left by a bracket that was never closed
+        if (pool->empty()) {
+            HIP_TRY(hipEventCreate(e));
+        } else {
+            *e = pool->back();
+            pool->pop_back();
+        }
     }
-    r->pending.clear();
+    HIP_TRY(hipEventRecord(e0, stream));
     return CHUNKY_OK;
 }
 
-// The most passes one launch of this target carries: render_pool stages every sample of a launch (12 bytes each) — at most
-// kStagingBytes of it, fewer than 2^31 samples, at most `most` passes (kMaxPassesPerLaunch: the seeds fit the kernel-argument
+int LaunchClock::close(hipStream_t stream, int weight) {
+    HIP_TRY(hipEventRecord(e1, stream));
+    pending.push_back(Bracket{e0, e1, weight});
+    e0 = e1 = nullptr;
+    return CHUNKY_OK;
+}
+
+int LaunchClock::collect() {
+    for (Bracket& b : pending) {
+        float t = 0;
+        HIP_TRY(hipEventSynchronize(b.e1));
+        HIP_TRY(hipEventElapsedTime(&t, b.e0, b.e1));
+        ms += t;
+        count += b.weight;
+        pool->push_back(b.e0);
+        pool->push_back(b.e1);
+    }
+    pending.clear();
+    return CHUNKY_OK;
+}
+
+int LaunchClock::take(float* ms_out, int* count_out) {
+    if (int rc = collect()) return rc;
+    if (ms_out) *ms_out = ms;
+    if (count_out) *count_out = count;
+    ms = 0;
+    count = 0;
+    return CHUNKY_OK;
+}
+
+// The most passes one launch over the pixel slots of T carries: render_pool stages every sample of a launch (12 bytes each) — at
+// most `budget` bytes of it, fewer than 2^31 samples, at most `most` passes (kMaxPassesPerLaunch: the seeds fit the kernel-argument
 // segment; kMaxPoolPasses for render_pool, which reads longer launches' seeds from device memory — a share of the image on several
-// GPUs then pays the end-of-launch tail once per 1024 passes instead of four times).  Sized by the tiles THIS rank renders.
-static int launch_pass_cap(const chunky_render* r, size_t budget, int most = kMaxPassesPerLaunch) {
-    const int64_t n_slots = (int64_t)(staging_floats(r->shard, r->width, r->height, 1) / 3);  // padded tiles
+// GPUs then pays the end-of-launch tail once per 1024 passes instead of four times).  Below 1 when not even one pass fits.
+static int launch_pass_cap(const ShardView& T, int width, int height, size_t budget, int most) {
+    const int64_t n_slots = (int64_t)(staging_floats(T, width, height, 1) / 3);  // padded tiles
     if (n_slots <= 0) return most;
     int64_t cap = (int64_t)(budget / 12) / n_slots;
     const int64_t cap31 = ((int64_t)1 << 31) / n_slots - 1;
     if (cap > cap31) cap = cap31;
-    if (cap > most) cap = most;
-    return cap < 1 ? 1 : (int)cap;
+    return (int)(cap > most ? most : cap);
+}
+
+// the extended light-transport options exist in render_pool's default instantiations only: CHUNKY_E_STATE where r's kernel
+// option, scene or max depth would send it elsewhere
+static int check_extended_opts(const char* who, const chunky_render* r, const SceneView& S) {
+    if (!opts_extended(r->opts)) return CHUNKY_OK;
+    const bool bvh = !S.world_bvh_empty || !S.actor_bvh_empty;
+    if ((r->kernel_variant & (1 | 2 | 4 | 8)) || (bvh && !(S.bvh_rec && S.tri_rec && S.mat8)))
+        return fail(CHUNKY_E_STATE, "%s: the extended light-transport options need the default kernel (CHUNKY_OPT_KERNEL 0)", who);
+    if (!S.wide)  // their instantiations walk the re-laid-out tree only (an octree deeper than 15 levels has none)
+        return fail(CHUNKY_E_STATE, "%s: the extended light-transport options need an octree the wide re-layout takes (depth <= 15)", who);
+    // the fallback kernels never read these options: a set render_pool refuses (max depth 255) would render the reference's transport
+    if (!pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr))
+        return fail(CHUNKY_E_STATE, "%s: the extended light-transport options need max depth <= 254 (CHUNKY_OPT_MAX_DEPTH)", who);
+    return CHUNKY_OK;
+}
+
+// a device-to-host read-back of exactly `need` 4-byte values on r's stream; src == nullptr: nothing has been rendered into it yet
+static int read_floats(const char* who, chunky_render* r, const void* src, void* out, int64_t n, int64_t need) {
+    if (!out || n != need) return fail(CHUNKY_E_INVALID, "%s: need %lld floats, got %lld", who, (long long)need, (long long)n);
+    if (!src) return fail(CHUNKY_E_STATE, "%s before anything was rendered into it", who);
+    HIP_TRY(hipMemcpyAsync(out, src, (size_t)n * 4, hipMemcpyDeviceToHost, r->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    return CHUNKY_OK;
 }
 
 extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp) {
@@ -1696,18 +1315,9 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
     SceneView S;
     if (int rc = scene_view(r->scene, &S, r->opts.nee != 0)) return rc;
     S.bvh_cull = r->opts.bvh_cull;
-    if (opts_extended(r->opts)) {  // the extensions exist in render_pool only
-        const bool bvh = !S.world_bvh_empty || !S.actor_bvh_empty;
-        if ((r->kernel_variant & (1 | 2 | 4 | 8)) || (bvh && !(S.bvh_rec && S.tri_rec && S.mat8)))
-            return fail(CHUNKY_E_STATE, "the extended light-transport options need the default kernel (CHUNKY_OPT_KERNEL 0)");
-        if (!S.wide)  // their instantiations walk the re-laid-out tree only (an octree deeper than 15 levels has none)
-            return fail(CHUNKY_E_STATE, "the extended light-transport options need an octree the wide re-layout takes (depth <= 15)");
-        // the fallback kernels never read these options: a set render_pool refuses (max depth 255) would render the reference's transport
-        if (!pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr))
-            return fail(CHUNKY_E_STATE, "the extended light-transport options need max depth <= 254 (CHUNKY_OPT_MAX_DEPTH)");
-    }
-    if (r->pending.size() > 4096)
-        if (int rc = collect_timing(r)) return rc;
+    if (int rc = check_extended_opts("render_passes", r, S)) return rc;
+    if (r->clock.full())
+        if (int rc = r->clock.collect()) return rc;
     if (r->shard.n_local <= 0) return CHUNKY_OK;  // this rank (or group member) owns no tile of so small an image: nothing to render
     if (r->shard.world != 1 && r->shard.tile == 0 && !r->shard.list &&
         !pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr)) {
@@ -1722,7 +1332,7 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
     // render_pool takes up to kMaxPoolPasses per launch, the other kernels what the kernel-argument segment holds
     const int most = pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr) ? kMaxPoolPasses : kMaxPassesPerLaunch;
     if (r->launch_cap <= 0 || r->launch_cap_most != most) {
-        r->launch_cap = launch_pass_cap(r, kStagingBytes, most);
+        r->launch_cap = std::max(1, launch_pass_cap(r->shard, r->width, r->height, kStagingBytes, most));  // sized by the tiles THIS rank renders
         r->launch_cap_most = most;
     }
     for (int done = 0; done < n;) {
@@ -1766,8 +1376,7 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
             memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
         } else {  // a long launch: its seeds go to device memory, in stream order behind the launch that read the buffer last
             if (!r->seed_buf.p) {
-                HIP_TRY(hipMalloc(&r->seed_buf.p, (size_t)kMaxPoolPasses * 4));
-                r->seed_buf.bytes = (size_t)kMaxPoolPasses * 4;
+                HIP_TRY(r->seed_buf.alloc((size_t)kMaxPoolPasses * 4));
             }
             // from a pinned slot of the target's own (the caller may reuse or free `seeds` as soon as this call returns — the JNI
             // glue releases the Java array — and a copy out of pageable memory is only safe if the runtime happens to stage it)
@@ -1783,14 +1392,10 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
             HIP_TRY(hipEventRecord(slot.copied, r->ctx->stream));
             seeds_dev = (const int*)r->seed_buf.p;
         }
-        hipEvent_t e0, e1;
-        HIP_TRY(get_event(r, &e0));
-        HIP_TRY(get_event(r, &e1));
-        HIP_TRY(hipEventRecord(e0, r->ctx->stream));
+        if (int rc = r->clock.open(r->ctx->stream)) return rc;
         HIP_TRY(launch_render(r->kernel_variant, S, r->cam, r->opts, r->shard, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream,
                               &r->last_choice, (float*)r->staging.p, seeds_dev));
-        HIP_TRY(hipEventRecord(e1, r->ctx->stream));
-        r->pending.emplace_back(e0, e1);
+        if (int rc = r->clock.close(r->ctx->stream)) return rc;
         done += ps.n;
     }
     return CHUNKY_OK;
@@ -1813,15 +1418,11 @@ static int gather_buffers(chunky_render* r, size_t i, size_t bytes) {
     chunky_render* pi = r->parts[i];
     if (r->gather_recv[i].bytes < bytes) {
         HIP_TRY(hipSetDevice(r->parts[0]->ctx->device));
-        r->gather_recv[i].release();
-        HIP_TRY(hipMalloc(&r->gather_recv[i].p, bytes));
-        r->gather_recv[i].bytes = bytes;
+        HIP_TRY(r->gather_recv[i].alloc(bytes));
     }
     HIP_TRY(hipSetDevice(pi->ctx->device));
     if (r->gather_send[i].bytes < bytes) {
-        r->gather_send[i].release();
-        HIP_TRY(hipMalloc(&r->gather_send[i].p, bytes));
-        r->gather_send[i].bytes = bytes;
+        HIP_TRY(r->gather_send[i].alloc(bytes));
     }
     return CHUNKY_OK;
 }
@@ -1997,11 +1598,7 @@ extern "C" int chunky_render_read(chunky_render* r, float* out, int64_t n) {
         return chunky_render_read(r->parts[0], out, n);
     }
     LOCK_RENDER(r);
-    int64_t need = (int64_t)r->width * r->height * 3;
-    if (!out || n != need) return fail(CHUNKY_E_INVALID, "render_read: need %lld floats, got %lld", (long long)need, (long long)n);
-    HIP_TRY(hipMemcpyAsync(out, r->fb, (size_t)n * 4, hipMemcpyDeviceToHost, r->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
-    return CHUNKY_OK;
+    return read_floats("render_read", r, r->fb, out, n, (int64_t)r->width * r->height * 3);
 }
 
 extern "C" int chunky_render_kernel_time(chunky_render* r, float* total_ms, int* launches) {
@@ -2019,12 +1616,7 @@ extern "C" int chunky_render_kernel_time(chunky_render* r, float* total_ms, int*
         return CHUNKY_OK;
     }
     LOCK_RENDER(r);
-    if (int rc = collect_timing(r)) return rc;
-    if (total_ms) *total_ms = r->timed_ms;
-    if (launches) *launches = r->timed_launches;
-    r->timed_ms = 0;
-    r->timed_launches = 0;
-    return CHUNKY_OK;
+    return r->clock.take(total_ms, launches);
 }
 
 extern "C" int chunky_render_kernel_info(chunky_render* r, int32_t out8[8]) {
@@ -2045,7 +1637,7 @@ extern "C" int chunky_render_kernel_info(chunky_render* r, int32_t out8[8]) {
         SceneView S;
         int most = kMaxPassesPerLaunch;
         if (scene_view(r->scene, &S, false) == CHUNKY_OK && pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr)) most = kMaxPoolPasses;
-        out8[6] = launch_pass_cap(r, kStagingBytes, most);
+        out8[6] = std::max(1, launch_pass_cap(r->shard, r->width, r->height, kStagingBytes, most));
     }
     return CHUNKY_OK;
 }
@@ -2070,8 +1662,7 @@ extern "C" int chunky_render_preview(chunky_render* r, int32_t* argb_out) {
     S.bvh_cull = r->opts.bvh_cull;
     DevBuf out;
     size_t bytes = (size_t)r->width * r->height * 4;
-    HIP_TRY(hipMalloc(&out.p, bytes));
-    out.bytes = bytes;
+    HIP_TRY(out.alloc(bytes));
     HIP_TRY(launch_preview(r->kernel_variant, S, r->cam, r->opts, (int*)out.p, r->ctx->stream));
     HIP_TRY(hipMemcpyAsync(argb_out, out.p, bytes, hipMemcpyDeviceToHost, r->ctx->stream));
     HIP_TRY(hipStreamSynchronize(r->ctx->stream));
@@ -2112,23 +1703,8 @@ extern "C" int chunky_render_trace_records(chunky_render* r, int32_t seed, const
 static int aov_ensure(chunky_render* r) {
     if (r->aov.p) return CHUNKY_OK;
     const size_t bytes = aov_image_bytes(r) * 2 + 256;  // albedo, normal, the claim counter
-    HIP_TRY(hipMalloc(&r->aov.p, bytes));
-    r->aov.bytes = bytes;
+    HIP_TRY(r->aov.alloc(bytes));
     HIP_TRY(hipMemsetAsync(r->aov.p, 0, bytes, r->ctx->stream));
-    return CHUNKY_OK;
-}
-
-static int collect_aov_timing(chunky_render* r) {
-    for (auto& p : r->aov_pending) {
-        float ms = 0;
-        HIP_TRY(hipEventSynchronize(p.second));
-        HIP_TRY(hipEventElapsedTime(&ms, p.first, p.second));
-        r->aov_ms += ms;
-        r->aov_launches += 1;
-        r->free_events.push_back(p.first);
-        r->free_events.push_back(p.second);
-    }
-    r->aov_pending.clear();
     return CHUNKY_OK;
 }
 
@@ -2136,15 +1712,14 @@ static int collect_aov_timing(chunky_render* r) {
 static int aov_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n, int first_buffer_spp) {
     LOCK_RENDER(r);
     if (!r->have_camera) return fail(CHUNKY_E_STATE, "aov_passes before set_camera");
-    if (!launch_aov) return fail(CHUNKY_E_STATE, "aov_passes: this build has no AOV kernels (aov.hip)");
     if (int rc = aov_ensure(r)) return rc;
     r->aov_last_launches = 0;
     if (n == 0 || T.n_local <= 0) return CHUNKY_OK;
     SceneView S;
     if (int rc = scene_view(r->scene, &S)) return rc;
     S.bvh_cull = r->opts.bvh_cull;
-    if (r->aov_pending.size() > 4096)
-        if (int rc = collect_aov_timing(r)) return rc;
+    if (r->aov_clock.full())
+        if (int rc = r->aov_clock.collect()) return rc;
     float* albedo = (float*)r->aov.p;
     float* normal = (float*)((char*)r->aov.p + aov_image_bytes(r));
     int* counter = (int*)((char*)r->aov.p + 2 * aov_image_bytes(r));
@@ -2153,13 +1728,9 @@ static int aov_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n
         ps.n = (n - done) < kMaxPassesPerLaunch ? (n - done) : kMaxPassesPerLaunch;
         ps.first_spp = first_buffer_spp + done;
         memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
-        hipEvent_t e0, e1;
-        HIP_TRY(get_event(r, &e0));
-        HIP_TRY(get_event(r, &e1));
-        HIP_TRY(hipEventRecord(e0, r->ctx->stream));
+        if (int rc = r->aov_clock.open(r->ctx->stream)) return rc;
         HIP_TRY(launch_aov(r->kernel_variant, S, r->cam, r->opts, T, ps, albedo, normal, counter, r->ctx->stream, &r->aov_choice));
-        HIP_TRY(hipEventRecord(e1, r->ctx->stream));
-        r->aov_pending.emplace_back(e0, e1);
+        if (int rc = r->aov_clock.close(r->ctx->stream)) return rc;
         r->aov_last_launches += 1;
         done += ps.n;
     }
@@ -2183,13 +1754,8 @@ extern "C" int chunky_render_aov_read(chunky_render* r, int which, float* out, i
     if (r && !r->parts.empty()) return chunky_render_aov_read(r->parts[0], which, out, n);
     LOCK_RENDER(r);
     if (which != CHUNKY_AOV_ALBEDO && which != CHUNKY_AOV_NORMAL) return fail(CHUNKY_E_INVALID, "aov_read: unknown image %d", which);
-    const int64_t need = (int64_t)r->width * r->height * 3;
-    if (!out || n != need) return fail(CHUNKY_E_INVALID, "aov_read: need %lld floats, got %lld", (long long)need, (long long)n);
-    if (!r->aov.p) return fail(CHUNKY_E_STATE, "aov_read before any AOV pass");
-    const char* src = (const char*)r->aov.p + (which == CHUNKY_AOV_NORMAL ? aov_image_bytes(r) : 0);
-    HIP_TRY(hipMemcpyAsync(out, src, (size_t)n * 4, hipMemcpyDeviceToHost, r->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
-    return CHUNKY_OK;
+    const char* src = r->aov.p ? (const char*)r->aov.p + (which == CHUNKY_AOV_NORMAL ? aov_image_bytes(r) : 0) : nullptr;  // null before any AOV pass
+    return read_floats("aov_read", r, src, out, n, (int64_t)r->width * r->height * 3);
 }
 
 extern "C" int chunky_render_aov_reset(chunky_render* r) {
@@ -2202,12 +1768,7 @@ extern "C" int chunky_render_aov_reset(chunky_render* r) {
 extern "C" int chunky_render_aov_kernel_time(chunky_render* r, float* total_ms, int* launches) {
     if (r && !r->parts.empty()) return chunky_render_aov_kernel_time(r->parts[0], total_ms, launches);
     LOCK_RENDER(r);
-    if (int rc = collect_aov_timing(r)) return rc;
-    if (total_ms) *total_ms = r->aov_ms;
-    if (launches) *launches = r->aov_launches;
-    r->aov_ms = 0;
-    r->aov_launches = 0;
-    return CHUNKY_OK;
+    return r->aov_clock.take(total_ms, launches);
 }
 
 extern "C" int chunky_render_aov_kernel_info(chunky_render* r, int32_t out4[4]) {
@@ -2308,59 +1869,36 @@ static int adaptive_ensure(chunky_render* r) {
     const size_t bytes[5] = {np * 8, np * 4, np * 2, ((size_t)adaptive_tiles(r) * 2 + 1) * 4, np * 4};
     for (int i = 0; i < 5; i++) {  // each on its own: a call that failed half way left the others in place
         if (bufs[i]->p) continue;
-        HIP_TRY(hipMalloc(&bufs[i]->p, bytes[i]));
-        bufs[i]->bytes = bytes[i];
+        HIP_TRY(bufs[i]->alloc(bytes[i]));
     }
     if (!r->ad_total_host) HIP_TRY(hipHostMalloc((void**)&r->ad_total_host, sizeof(int32_t), hipHostMallocDefault));
     return CHUNKY_OK;
 }
 
-// a pair of timing events borrowed from the target's pool and handed back on every way out
-struct AdaptiveEvents {
-    chunky_render* r;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    explicit AdaptiveEvents(chunky_render* r_) : r(r_) {}
-    ~AdaptiveEvents() {
-        if (e0) r->free_events.push_back(e0);
-        if (e1) r->free_events.push_back(e1);
-    }
-};
-
 // what an adaptive call needs of the target: one device, the whole image, and render_pool for the scene and options as they are
 static int adaptive_state(const char* who, chunky_render* r, SceneView* S) {
     if (r->shard.world > 1) return fail(CHUNKY_E_STATE, "%s: this target holds rank %d of %d of the image, not all of it", who, r->shard.rank, r->shard.world);
     if (!r->have_camera) return fail(CHUNKY_E_STATE, "%s before set_camera", who);
-    if (!launch_render_stats || !launch_fold_stats || !launch_adaptive_check || !launch_adaptive_finish) return fail(CHUNKY_E_STATE, "%s: this build has no adaptive kernels (adaptive.hip)", who);
     if (int rc = scene_view(r->scene, S, r->opts.nee != 0)) return rc;
     S->bvh_cull = r->opts.bvh_cull;
-    const bool bvh = !S->world_bvh_empty || !S->actor_bvh_empty;
-    if (opts_extended(r->opts) && ((r->kernel_variant & (1 | 2 | 4 | 8)) || (bvh && !(S->bvh_rec && S->tri_rec && S->mat8)) || !S->wide))
-        return fail(CHUNKY_E_STATE, "%s: the extended light-transport options need the default kernel and an octree the wide re-layout takes", who);
+    if (int rc = check_extended_opts(who, r, *S)) return rc;
     if (!pool_kernel_applies(r->kernel_variant, *S, r->opts, r->work_counter.p != nullptr))
         return fail(CHUNKY_E_STATE, "%s: the scene or the options send this target to the fallback kernels, which stage no samples", who);
     return CHUNKY_OK;
 }
 
-// The most passes one launch over the pixel slots of T carries (as launch_pass_cap, sized from T and not from r->shard; at most
-// kMaxPassesPerLaunch: the seeds travel in the kernel-argument segment), and the staging array grown to hold a launch of
-// min(n, cap) passes — before the round's timing bracket opens, so that no allocation is timed.  It grows only: chunky_render_passes
-// reuses it, and r->launch_cap is not touched.
+// The most passes one launch over the pixel slots of T carries (launch_pass_cap of T, not of r->shard; at most kMaxPassesPerLaunch:
+// the seeds travel in the kernel-argument segment), and the staging array grown to hold a launch of min(n, cap) passes — before
+// the round's timing bracket opens, so that no allocation is timed.  It grows only: chunky_render_passes reuses it, and
+// r->launch_cap is not touched.
 static int adaptive_stage(chunky_render* r, const ShardView& T, int n, int* cap_out) {
-    const int64_t n_slots = (int64_t)(staging_floats(T, r->width, r->height, 1) / 3);  // padded tiles
-    *cap_out = kMaxPassesPerLaunch;
-    if (n_slots <= 0) return CHUNKY_OK;
-    int64_t cap = (int64_t)(kStagingBytes / 12) / n_slots;
-    const int64_t cap31 = ((int64_t)1 << 31) / n_slots - 1;
-    if (cap > cap31) cap = cap31;
-    if (cap > kMaxPassesPerLaunch) cap = kMaxPassesPerLaunch;
+    const int cap = launch_pass_cap(T, r->width, r->height, kStagingBytes, kMaxPassesPerLaunch);
     if (cap < 1) return fail(CHUNKY_E_INVALID, "adaptive: the image is too large to stage one pass");
-    *cap_out = (int)cap;
-    const size_t need = staging_floats(T, r->width, r->height, n < (int)cap ? n : (int)cap) * sizeof(float);
+    *cap_out = cap;
+    const size_t need = staging_floats(T, r->width, r->height, n < cap ? n : cap) * sizeof(float);
     if (r->staging.bytes < need) {
         HIP_TRY(hipStreamSynchronize(r->ctx->stream));
-        r->staging.release();
-        HIP_TRY(hipMalloc(&r->staging.p, need));
-        r->staging.bytes = need;
+        HIP_TRY(r->staging.alloc(need));
     }
     return CHUNKY_OK;
 }
@@ -2407,10 +1945,6 @@ extern "C" int chunky_render_adaptive(chunky_render* r, const int32_t* seeds, in
     const float t2 = p.threshold * p.threshold;
     chunky_adaptive_summary sum;
     memset(&sum, 0, sizeof sum);
-    AdaptiveEvents ev(r);
-    HIP_TRY(get_event(r, &ev.e0));
-    HIP_TRY(get_event(r, &ev.e1));
-    const hipEvent_t e0 = ev.e0, e1 = ev.e1;
     int done = 0, n_active = np;
     while (done < max_spp && n_active > 0) {
         const int left = max_spp - done;
@@ -2421,7 +1955,7 @@ extern "C" int chunky_render_adaptive(chunky_render* r, const int32_t* seeds, in
         if (n_active < np) T = ShardView{0, 2, 1, n_active, (const int*)r->ad_list.p, n_active};
         int cap = 0;
         if (int rc = adaptive_stage(r, T, round_n, &cap)) return rc;
-        HIP_TRY(hipEventRecord(e0, st));
+        if (int rc = r->ad_clock.open(st)) return rc;
         if (int rc = adaptive_launch(r, S, T, seeds + done, round_n, done, cap)) return rc;
         sum.samples += (int64_t)n_active * round_n;
         done += round_n;
@@ -2432,12 +1966,9 @@ extern "C" int chunky_render_adaptive(chunky_render* r, const int32_t* seeds, in
                                           tile_counts, tile_offsets, (int*)r->ad_list.p, total, st));
             HIP_TRY(hipMemcpyAsync(r->ad_total_host, total, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         }
-        HIP_TRY(hipEventRecord(e1, st));
+        if (int rc = r->ad_clock.close(st)) return rc;
         HIP_TRY(hipStreamSynchronize(st));  // once per round: the host loop needs the total
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        r->ad_ms += ms;
-        r->ad_rounds += 1;
+        if (int rc = r->ad_clock.collect()) return rc;  // (finished: its events go back to the pool for the next round)
         if (check) {
             n_active = *r->ad_total_host;
             if (n_active < 0 || n_active > np) return fail(CHUNKY_E_HIP, "render_adaptive: the compaction reported %d active pixels of %d", n_active, np);
@@ -2456,33 +1987,19 @@ extern "C" int chunky_render_adaptive(chunky_render* r, const int32_t* seeds, in
 extern "C" int chunky_render_adaptive_counts(chunky_render* r, int32_t* out, int64_t n) {
     if (r && !r->parts.empty()) return fail(CHUNKY_E_STATE, "render_adaptive_counts: a group's target has no adaptive run");
     LOCK_RENDER(r);
-    const int64_t need = (int64_t)r->width * r->height;
-    if (!out || n != need) return fail(CHUNKY_E_INVALID, "render_adaptive_counts: need %lld values, got %lld", (long long)need, (long long)n);
-    if (!r->ad_valid) return fail(CHUNKY_E_STATE, "render_adaptive_counts before any adaptive run");
-    HIP_TRY(hipMemcpyAsync(out, r->ad_count.p, (size_t)n * 4, hipMemcpyDeviceToHost, r->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
-    return CHUNKY_OK;
+    return read_floats("render_adaptive_counts", r, r->ad_valid ? r->ad_count.p : nullptr, out, n, (int64_t)r->width * r->height);  // (ints)
 }
 
 extern "C" int chunky_render_adaptive_noise(chunky_render* r, float* out, int64_t n_floats) {
     if (r && !r->parts.empty()) return fail(CHUNKY_E_STATE, "render_adaptive_noise: a group's target has no adaptive run");
     LOCK_RENDER(r);
-    const int64_t need = (int64_t)r->width * r->height * 2;
-    if (!out || n_floats != need) return fail(CHUNKY_E_INVALID, "render_adaptive_noise: need %lld floats, got %lld", (long long)need, (long long)n_floats);
-    if (!r->ad_valid) return fail(CHUNKY_E_STATE, "render_adaptive_noise before any adaptive run");
-    HIP_TRY(hipMemcpyAsync(out, r->ad_stat.p, (size_t)n_floats * 4, hipMemcpyDeviceToHost, r->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
-    return CHUNKY_OK;
+    return read_floats("render_adaptive_noise", r, r->ad_valid ? r->ad_stat.p : nullptr, out, n_floats, (int64_t)r->width * r->height * 2);
 }
 
 extern "C" int chunky_render_adaptive_kernel_time(chunky_render* r, float* total_ms, int* rounds) {
     if (r && !r->parts.empty()) return fail(CHUNKY_E_STATE, "render_adaptive_kernel_time: a group's target has no adaptive run");
     LOCK_RENDER(r);
-    if (total_ms) *total_ms = r->ad_ms;
-    if (rounds) *rounds = r->ad_rounds;
-    r->ad_ms = 0;
-    r->ad_rounds = 0;
-    return CHUNKY_OK;
+    return r->ad_clock.take(total_ms, rounds);
 }
 
 extern "C" int chunky_selftest_render_list(chunky_render* r, const int32_t* pixels, int n_pixels, const int32_t* seeds, int n) {
@@ -2507,21 +2024,13 @@ extern "C" int chunky_selftest_render_list(chunky_render* r, const int32_t* pixe
     HIP_TRY(hipMemcpyAsync(r->ad_list.p, pixels, (size_t)n_pixels * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));  // the caller may reuse its array on return
     const ShardView T{0, 2, 1, n_pixels, (const int*)r->ad_list.p, n_pixels};
-    AdaptiveEvents ev(r);
-    HIP_TRY(get_event(r, &ev.e0));
-    HIP_TRY(get_event(r, &ev.e1));
-    const hipEvent_t e0 = ev.e0, e1 = ev.e1;
     int cap = 0;
     if (int rc = adaptive_stage(r, T, n, &cap)) return rc;
-    HIP_TRY(hipEventRecord(e0, st));
+    if (int rc = r->ad_clock.open(st)) return rc;
     if (int rc = adaptive_launch(r, S, T, seeds, n, 0, cap)) return rc;
-    HIP_TRY(hipEventRecord(e1, st));
+    if (int rc = r->ad_clock.close(st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    r->ad_ms += ms;
-    r->ad_rounds += 1;
-    return CHUNKY_OK;
+    return r->ad_clock.collect();
 }
 
 // ------------------------------------------------------------------------------------ denoiser (denoise_spec.h, denoise.hip)
@@ -2635,7 +2144,6 @@ extern "C" int chunky_denoise_frame(chunky_ctx* ctx, int width, int height, cons
     int form = 0;
     if (int rc = denoise_params("denoise_frame", params, &K, &form)) return rc;
     if (int rc = denoise_images("denoise_frame", width, height, color, albedo, normal, out)) return rc;
-    if (!launch_denoise) return fail(CHUNKY_E_STATE, "denoise_frame: this build has no denoise kernels (denoise.hip)");
     std::lock_guard<std::recursive_mutex> guard(ctx->mu);
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)width * height * 12;
@@ -2643,8 +2151,7 @@ extern "C" int chunky_denoise_frame(chunky_ctx* ctx, int width, int height, cons
     HIP_TRY(c.upload(color, bytes, ctx->stream));
     HIP_TRY(a.upload(albedo, bytes, ctx->stream));
     HIP_TRY(n.upload(normal, bytes, ctx->stream));
-    HIP_TRY(hipMalloc(&o.p, bytes));
-    o.bytes = bytes;
+    HIP_TRY(o.alloc(bytes));
     work.bytes = denoise_work_bytes(width, height);
     HIP_TRY(hipMalloc(&work.p, work.bytes));
     HIP_TRY(launch_denoise(form, width, height, (const float*)c.p, (const float*)a.p, (const float*)n.p, K, (float*)o.p, work.p, work.bytes, ctx->stream, nullptr));
@@ -2653,49 +2160,25 @@ extern "C" int chunky_denoise_frame(chunky_ctx* ctx, int width, int height, cons
     return CHUNKY_OK;
 }
 
-static int collect_denoise_timing(chunky_render* r) {
-    for (size_t i = 0; i < r->dn_pending.size(); i++) {
-        float ms = 0;
-        HIP_TRY(hipEventSynchronize(r->dn_pending[i].second));
-        HIP_TRY(hipEventElapsedTime(&ms, r->dn_pending[i].first, r->dn_pending[i].second));
-        r->dn_ms += ms;
-        r->dn_launches += r->dn_pending_launches[i];
-        r->free_events.push_back(r->dn_pending[i].first);
-        r->free_events.push_back(r->dn_pending[i].second);
-    }
-    r->dn_pending.clear();
-    r->dn_pending_launches.clear();
-    return CHUNKY_OK;
-}
-
 // on one device: r's framebuffer holds the whole image (a single-device target, or member 0 of a group after the exchange)
 static int render_denoise(chunky_render* r, const DnCoeffs& K, int form, float* out) {
     LOCK_RENDER(r);
     if (!r->aov.p) return fail(CHUNKY_E_STATE, "render_denoise before any AOV pass");
-    if (!launch_denoise) return fail(CHUNKY_E_STATE, "render_denoise: this build has no denoise kernels (denoise.hip)");
     const size_t bytes = aov_image_bytes(r), need = denoise_work_bytes(r->width, r->height);
     if (!r->dn_work.p) {
-        HIP_TRY(hipMalloc(&r->dn_work.p, need));
-        r->dn_work.bytes = need;
-        HIP_TRY(hipMalloc(&r->dn_out.p, bytes));
-        r->dn_out.bytes = bytes;
+        HIP_TRY(r->dn_work.alloc(need));
+        HIP_TRY(r->dn_out.alloc(bytes));
     }
-    if (r->dn_pending.size() > 1024)
-        if (int rc = collect_denoise_timing(r)) return rc;
+    if (r->dn_clock.full())
+        if (int rc = r->dn_clock.collect()) return rc;
     const float* albedo = (const float*)r->aov.p;
     const float* normal = (const float*)((const char*)r->aov.p + bytes);
-    hipEvent_t e0, e1;
-    HIP_TRY(get_event(r, &e0));
-    HIP_TRY(get_event(r, &e1));
     int launches = 0;
-    HIP_TRY(hipEventRecord(e0, r->ctx->stream));
+    if (int rc = r->dn_clock.open(r->ctx->stream)) return rc;
     HIP_TRY(launch_denoise(form, r->width, r->height, r->fb, albedo, normal, K, (float*)r->dn_out.p, r->dn_work.p, r->dn_work.bytes, r->ctx->stream, &launches));
-    HIP_TRY(hipEventRecord(e1, r->ctx->stream));
-    r->dn_pending.emplace_back(e0, e1);
-    r->dn_pending_launches.push_back(launches);
-    HIP_TRY(hipMemcpyAsync(out, r->dn_out.p, bytes, hipMemcpyDeviceToHost, r->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
-    return CHUNKY_OK;
+    if (int rc = r->dn_clock.close(r->ctx->stream, launches)) return rc;
+    const int64_t n = (int64_t)(bytes / 4);  // (checked against the caller's count by chunky_render_denoise)
+    return read_floats("render_denoise", r, r->dn_out.p, out, n, n);
 }
 
 extern "C" int chunky_render_denoise(chunky_render* r, const chunky_denoise_params* params, float* out, int64_t n_floats) {
@@ -2718,12 +2201,7 @@ extern "C" int chunky_render_denoise(chunky_render* r, const chunky_denoise_para
 extern "C" int chunky_render_denoise_kernel_time(chunky_render* r, float* total_ms, int* launches) {
     if (r && !r->parts.empty()) return chunky_render_denoise_kernel_time(r->parts[0], total_ms, launches);
     LOCK_RENDER(r);
-    if (int rc = collect_denoise_timing(r)) return rc;
-    if (total_ms) *total_ms = r->dn_ms;
-    if (launches) *launches = r->dn_launches;
-    r->dn_ms = 0;
-    r->dn_launches = 0;
-    return CHUNKY_OK;
+    return r->dn_clock.take(total_ms, launches);
 }
 
 // ------------------------------------------------------------------------------------ host loop
@@ -2951,8 +2429,7 @@ extern "C" int chunky_filter_frame(chunky_ctx* ctx, int width, int height, doubl
     HIP_TRY(hipSetDevice(ctx->device));
     DevBuf in, out;
     HIP_TRY(in.upload(input, (size_t)n * 24, ctx->stream));
-    HIP_TRY(hipMalloc(&out.p, (size_t)n * 4));
-    out.bytes = (size_t)n * 4;
+    HIP_TRY(out.alloc((size_t)n * 4));
     const float* table = nullptr;
     if (int rc = device_gamma_table(ctx, &table)) return rc;
     HIP_TRY(launch_filter(n, (float)exposure, (const double*)in.p, (unsigned*)out.p, type, ctx->stream, table));
@@ -3014,7 +2491,6 @@ extern "C" int chunky_selftest_camera_rays(chunky_render* r, int32_t seed, float
     if (!r->have_camera || r->cam.projector_type <= 0) return fail(CHUNKY_E_STATE, "selftest_camera_rays: the target has no projected camera");
     const int64_t need = (int64_t)r->width * r->height * 6;
     if (!out || n_floats != need) return fail(CHUNKY_E_INVALID, "selftest_camera_rays: need %lld floats, got %lld", (long long)need, (long long)n_floats);
-    if (!launch_camera_rays_selftest) return fail(CHUNKY_E_STATE, "selftest_camera_rays: this build has no camera kernel (aux_kernels.hip)");
     DevBuf dout;
     HIP_TRY(hipMalloc(&dout.p, (size_t)need * 4));
     HIP_TRY(launch_camera_rays_selftest(r->cam, seed, (float*)dout.p, r->ctx->stream));

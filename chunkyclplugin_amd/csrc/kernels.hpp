@@ -1,5 +1,5 @@
 // kernels.hpp — host-visible launch interface of the kernel translation units (render_pool.hip, render_fallback.hip,
-// aux_kernels.hip, filter.hip, aov.hip, denoise.hip).
+// aux_kernels.hip, filter.hip, aov.hip, denoise.hip, adaptive.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -98,11 +98,10 @@ hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, c
                          KernelChoice* chosen = nullptr, float* staging = nullptr, const int* seeds_dev = nullptr);
 // launch_render with the launch's samples folded by fold_stats_kernel (adaptive.hip) in place of fold_kernel: fold_stats holds two
 // floats per pixel of the image, the luminance statistic that kernel updates beside the running mean.  render_pool only
-// (hipErrorNotSupported under the other kernels, which stage no samples); fold_stats == nullptr is launch_render.  Weak for the same
-// reason as launch_aov below.
-__attribute__((weak)) hipError_t launch_render_stats(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
-                                                     const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
-                                                     float* staging, const int* seeds_dev, float* fold_stats);
+// (hipErrorNotSupported under the other kernels, which stage no samples); fold_stats == nullptr is launch_render.
+hipError_t launch_render_stats(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
+                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
+                               float* staging, const int* seeds_dev, float* fold_stats);
 // the kernels behind render_pool (render_fallback.hip): render_waves, render_lanes
 hipError_t launch_fallback(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                            const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen);
@@ -123,33 +122,29 @@ struct AovChoice {
     int blocks;  // workgroups launched
 };
 // AOV passes (aov.hip): P.n <= kMaxPassesPerLaunch; albedo / normal are 3 * width * height floats each, folded in place over the
-// pixel slots of shard T; `counter` is one int of device memory the launch claims its work from.  Declared weak so that a host-only
-// build of capi.hip without the kernel translation units (tests/sanitize/capi_host_fuzz.cpp) still links; where aov.hip is not
-// linked in, chunky_render_aov_passes fails with CHUNKY_E_STATE instead of calling it.
-__attribute__((weak)) hipError_t launch_aov(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
+// pixel slots of shard T; `counter` is one int of device memory the launch claims its work from.
+hipError_t launch_aov(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
                       float* albedo, float* normal, int* counter, hipStream_t stream, AovChoice* chosen);
 // The À-Trous denoiser (denoise.hip; specification: denoise_spec.h).  color / albedo / normal / out: 3 * width * height floats on the
 // device (out may not alias an input); `work`: denoise_work_bytes of device memory, 16-byte aligned, the launch's own while it runs.
 // One launch per iteration plus the pack (or demodulation) pass, all on `stream`; *launches receives their number.  `form` picks how taps
-// are fetched (all bit-identical).  Weak for the same reason as launch_aov: where denoise.hip is not linked in, the device entry
-// points fail with CHUNKY_E_STATE.
+// are fetched (all bit-identical).
 constexpr int kDenoiseGather = 0;  // the images as they arrive, 3 floats per pixel (the default: the faster of the two)
 constexpr int kDenoisePacked = 1;  // 16-byte words per pixel, written by a pack pass
 inline size_t denoise_work_bytes(int width, int height) { return (size_t)width * height * 64; }  // enough for either form (packed: two colour planes + two guide planes of float4)
-__attribute__((weak)) hipError_t launch_denoise(int form, int width, int height, const float* color, const float* albedo, const float* normal, const ::DnCoeffs& K,
-                                                float* out, void* work, size_t work_bytes, hipStream_t stream, int* launches);
-// Adaptive sampling (adaptive.hip; specification: adaptive_spec.h).  Weak for the same reason as launch_aov: where adaptive.hip is not
-// linked in, the adaptive entry points fail with CHUNKY_E_STATE.
+hipError_t launch_denoise(int form, int width, int height, const float* color, const float* albedo, const float* normal, const ::DnCoeffs& K,
+                          float* out, void* work, size_t work_bytes, hipStream_t stream, int* launches);
+// Adaptive sampling (adaptive.hip; specification: adaptive_spec.h).
 // fold_kernel's running mean over the staged samples of n_tiles tiles of shard T, and the Welford update of stat (2 floats per pixel)
-__attribute__((weak)) hipError_t launch_fold_stats(const float* staging, float* res, float* stat, const ShardView& T, int width, int height, long long n_tiles,
-                                                   int n_passes, int first_spp, hipStream_t stream);
+hipError_t launch_fold_stats(const float* staging, float* res, float* stat, const ShardView& T, int width, int height, long long n_tiles,
+                             int n_passes, int first_spp, hipStream_t stream);
 // the check after n passes: unconverged flags (unconv), activity (active; pixels that leave get count = n), then the active pixels in
 // whole-image pool-slot order in `list` and their number in *total.  active / unconv: width * height bytes; count / list: width * height
 // ints; tile_counts / tile_offsets: one int per 16 x 16 tile; all on the device
-__attribute__((weak)) hipError_t launch_adaptive_check(int width, int height, const float* stat, unsigned char* active, unsigned char* unconv, int* count, int n,
-                                                       float t2, float floor_, int* tile_counts, int* tile_offsets, int* list, int* total, hipStream_t stream);
+hipError_t launch_adaptive_check(int width, int height, const float* stat, unsigned char* active, unsigned char* unconv, int* count, int n,
+                                 float t2, float floor_, int* tile_counts, int* tile_offsets, int* list, int* total, hipStream_t stream);
 // pixels still active record n
-__attribute__((weak)) hipError_t launch_adaptive_finish(int n_pixels, const unsigned char* active, int* count, int n, hipStream_t stream);
+hipError_t launch_adaptive_finish(int n_pixels, const unsigned char* active, int* count, int n, hipStream_t stream);
 // thresholds: 256 floats on the device (capi.hip gamma_thresholds) or null = evaluate pow per channel
 hipError_t launch_filter(long long n_pixels, float exposure, const double* in, unsigned* out, int type, hipStream_t stream,
                          const float* thresholds = nullptr);
@@ -161,7 +156,6 @@ hipError_t launch_gamma_scan(unsigned first, unsigned long long count, int curve
 hipError_t launch_helpers_selftest(const SceneView& S, int which, int tree, int n, const float* in, float* out, int* tree_used, hipStream_t stream);
 hipError_t launch_math_selftest(int which, int n, const float* a, const float* b, float* out, hipStream_t stream);
 // projected camera self test (aux_kernels.hip camera_rays_kernel): width * height * 6 floats, origin then direction per pixel.
-// Weak for the same reason as launch_aov: where it is not linked in, chunky_selftest_camera_rays fails with CHUNKY_E_STATE.
-__attribute__((weak)) hipError_t launch_camera_rays_selftest(const CameraView& C, int seed, float* out, hipStream_t stream);
+hipError_t launch_camera_rays_selftest(const CameraView& C, int seed, float* out, hipStream_t stream);
 
 }  // namespace chunky

@@ -624,7 +624,6 @@ static hipError_t launch_pool(int variant, const SceneView& S, const CameraView&
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (fold_stats) {  // adaptive sampling: the same running mean, and the pixels' luminance statistic from the same read
-        if (!launch_fold_stats) return hipErrorNotSupported;
         return launch_fold_stats(staging, res, fold_stats, T, C.width, C.height, n_tiles, P.n, P.first_spp, stream);
     }
     const long long threads = 3ll * n_tiles * kSampleTile;

@@ -88,7 +88,7 @@ struct SceneView {
     const int4* __restrict__ mat8;
     const int4* __restrict__ aabb_rec;
     const int4* __restrict__ quad_rec;
-    // Both entity BVHs re-laid out (capi.hip build_bvh_records), null when they could not be:
+    // Both entity BVHs re-laid out (scene_records.cpp build_bvh_records), null when they could not be:
     //   bvh_rec  per inner node four words {ref A, ref B, 0, 0} {A: xmin, xmax, ymin, ymax} {A: zmin, zmax, B: xmin, xmax}
     //            {B: ymin, ymax, zmin, zmax} — A is the child that follows the node (K/bvh.h:73), B the one it points at
     //   tri_rec  per triangle five words {e1, flags} {e2, material (mat8 index)} {o, t1.u} {n, t1.v} {t2.u, t2.v, t3.u, t3.v}

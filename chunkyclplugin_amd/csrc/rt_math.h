@@ -22,7 +22,7 @@
 #define CHUNKY_RT_MATH_H
 
 #if defined(__HIPCC__)
-#define RT_FN __host__ __device__ static __forceinline__
+#define RT_FN __host__ __device__ static inline __attribute__((always_inline))
 #else
 #define RT_FN static inline __attribute__((always_inline))
 #endif

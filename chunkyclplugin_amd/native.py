@@ -18,7 +18,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("CHUNKY_HIP_LIB") or os.path.join(PKG_DIR, "libchunky_hip.so")  # override: tuning builds (tools/variants.sh)
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
-SOURCES = ["render_pool.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "denoise.hip", "adaptive.hip", "capi.hip", "widetree.cpp"]
+SOURCES = ["render_pool.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "denoise.hip", "adaptive.hip",
+           "capi.hip", "scene_records.cpp", "widetree.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
 
 MAX_TRACES = 10
@@ -48,15 +49,18 @@ class ChunkyHipError(RuntimeError):
         self.code = code
 
 
-def _needs_build() -> bool:
-    if os.environ.get("CHUNKY_HIP_LIB"):
-        return False
-    if not os.path.exists(LIB_PATH):
+def _stale(lib_path: str) -> bool:
+    """The library is missing, or older than a source or the header."""
+    if not os.path.exists(lib_path):
         return True
-    t = os.path.getmtime(LIB_PATH)
+    t = os.path.getmtime(lib_path)
     # the sources (files only: csrc/build/ holds objects and tools that are written after the link)
     deps = [p for p in (os.path.join(CSRC, f) for f in os.listdir(CSRC)) if os.path.isfile(p)] + [HEADER]
     return any(os.path.getmtime(d) > t for d in deps)
+
+
+def _needs_build() -> bool:
+    return not os.environ.get("CHUNKY_HIP_LIB") and _stale(LIB_PATH)
 
 
 def build(force: bool = False, extra_flags=(), out: Optional[str] = None, objdir: Optional[str] = None) -> str:
@@ -84,7 +88,7 @@ def build(force: bool = False, extra_flags=(), out: Optional[str] = None, objdir
                 raise RuntimeError(f"hipcc failed on {src}:\n" + proc.stderr[-4000:])
             return obj
 
-        with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 4)) as pool:
+        with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 4, 16)) as pool:  # (more compile jobs than that gain nothing)
             objs = list(pool.map(compile_one, SOURCES))
         proc = subprocess.run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", out or LIB_PATH], capture_output=True, text=True)
         lock.close()  # (also released when an exception unwinds past here: the file object goes away)
@@ -101,12 +105,7 @@ def build_tuning(force: bool = False) -> str:
     (CHUNKY_WIDE_LEVELS, CHUNKY_WIDE_TOP_BITS, CHUNKY_DEBUG_WIDE_BITS, CHUNKY_BVH_LAYOUT, CHUNKY_GROUP_TRANSPORT,
     CHUNKY_GROUP_SELF_EXCHANGE, CHUNKY_GROUP_NO_PROBE, CHUNKY_GROUP_TIMEOUT_MS, CHUNKY_RCCL_TRY_SHARED).  The shipping
     library reads none of them; tests and tools that need one run a child process with CHUNKY_HIP_LIB pointing here."""
-    stale = not os.path.exists(TUNING_LIB_PATH)
-    if not stale:
-        t = os.path.getmtime(TUNING_LIB_PATH)
-        deps = [p for p in (os.path.join(CSRC, f) for f in os.listdir(CSRC)) if os.path.isfile(p)] + [HEADER]
-        stale = any(os.path.getmtime(d) > t for d in deps)
-    if force or stale:
+    if force or _stale(TUNING_LIB_PATH):
         build(force=True, extra_flags=["-DCHUNKY_TUNING"], out=TUNING_LIB_PATH, objdir=os.path.join(CSRC, "build", "tuning"))
     return TUNING_LIB_PATH
 

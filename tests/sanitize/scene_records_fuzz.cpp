@@ -1,29 +1,19 @@
-// tests/sanitize/capi_host_fuzz.cpp — TEST-ONLY: the host-side parsers of csrc/capi.hip that walk caller-supplied ints — derive_records
-// (block / material / AABB / quad palettes -> aligned records), build_quad_aux, build_bvh_records + bvh_leaves_sound (entity BVHs),
-// list_emitters and model_leaf_permille (octree + palettes) — under AddressSanitizer + UBSan on the CPU.  The translation unit is capi.hip itself, compiled for
-// the host only; nothing here touches a device (no HIP call is reached: the functions under test are the pure halves).
+// tests/sanitize/scene_records_fuzz.cpp — TEST-ONLY: the host-side parsers of csrc/scene_records.cpp that walk caller-supplied ints —
+// derive_records (block / material / AABB / quad palettes -> aligned records), build_quad_aux, bvh_links_height + build_bvh_records +
+// bvh_leaves_sound (entity BVHs), list_emitters and model_leaf_permille (octree + palettes) — under AddressSanitizer + UBSan on the CPU.
+// Plain C++: nothing here touches a device.
 //
 // Inputs: palettes and trees that are well formed, and the same with ints damaged at random (pointers outside their palettes, huge and
 // negative counts, cycles).  Required: no out-of-bounds access, no undefined arithmetic, termination; for sound inputs the derived records
 // have to be consistent with their sources (spot checks), and every block the derivation leaves on the packed path has to be one whose
 // packed reads stay inside the palettes — that is what keeps hostile scene data from faulting the GPU.   (tests/test_sanitize.py)
-#include "../../chunkyclplugin_amd/csrc/capi.hip"
-
+#include <cstdio>
+#include <cstdlib>
 #include <random>
 
-// the kernel launchers live in the other translation units; nothing under test reaches them
-namespace chunky {
-hipError_t launch_render(int, const SceneView&, const CameraView&, const RenderOpts&, const ShardView&, const PassSeeds&, float*, int*, hipStream_t, KernelChoice*, float*, const int*) { return hipErrorNotSupported; }
-bool pool_kernel_applies(int, const SceneView&, const RenderOpts&, bool) { return false; }
-hipError_t launch_gather(bool, const ShardView&, int, int, float*, float*, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_clear_foreign(const ShardView&, int, int, float*, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_trace_records(int, const SceneView&, const CameraView&, const RenderOpts&, int, const int*, int, HitRecord*, int*, float*, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_preview(int, const SceneView&, const CameraView&, const RenderOpts&, int*, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_filter(long long, float, const double*, unsigned*, int, hipStream_t, const float*) { return hipErrorNotSupported; }
-hipError_t launch_gamma_scan(unsigned, unsigned long long, int, const float*, unsigned long long*, float*, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_helpers_selftest(const SceneView&, int, int, int, const float*, float*, int*, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_math_selftest(int, int, const float*, const float*, float*, hipStream_t) { return hipErrorNotSupported; }
-}  // namespace chunky
+#include "../../chunkyclplugin_amd/csrc/scene_records.hpp"
+
+using namespace chunky;
 
 static std::mt19937 rng(7u);
 static int32_t fbits(float f) {
@@ -160,20 +150,6 @@ static void grow_bvh(std::vector<int32_t>& N, std::vector<int32_t>& T, int depth
     N[at] = (int32_t)N.size();
     grow_bvh(N, T, depth - 1, n_mats);
 }
-static bool links_sound(const std::vector<int32_t>& N) {  // chunky_scene_set_bvh's own check (links inside the array, no cycle, depth <= 63)
-    std::vector<std::pair<int64_t, int>> todo{{0, 0}};
-    int64_t visited = 0;
-    while (!todo.empty()) {
-        auto [at, d] = todo.back();
-        todo.pop_back();
-        if (at < 0 || at + 7 > (int64_t)N.size() || ++visited > (int64_t)N.size() || d > 63) return false;
-        if (N[(size_t)at] > 0) {
-            todo.emplace_back(at + 7, d + 1);
-            todo.emplace_back((int64_t)N[(size_t)at], d + 1);
-        }
-    }
-    return true;
-}
 
 // the tree the records describe, independent of where they sit: depth-first, an inner record's twelve box words then its two
 // subtrees, a leaf's count and triangle words
@@ -194,26 +170,25 @@ static void canonical(const std::vector<int32_t>& nodes, const std::vector<int32
 static int fuzz_bvh(int rounds) {
     long long built = 0, unfit = 0, refused = 0, relaid = 0;
     for (int r = 0; r < rounds; r++) {
-        chunky_scene s;
+        std::vector<int32_t> world, actor, trigs, mats;
         const int n_mats = 1 + (int)(rng() % 5);
-        s.host_materials.assign((size_t)n_mats * 6, 0);
-        s.host_trigs = {0};  // pointer 0: an empty leaf
-        grow_bvh(s.host_world_bvh, s.host_trigs, 1 + (int)(rng() % 6), n_mats);
-        grow_bvh(s.host_actor_bvh, s.host_trigs, (int)(rng() % 3), n_mats);
-        s.world_empty = s.actor_empty = false;
+        mats.assign((size_t)n_mats * 6, 0);
+        trigs = {0};  // pointer 0: an empty leaf
+        grow_bvh(world, trigs, 1 + (int)(rng() % 6), n_mats);
+        grow_bvh(actor, trigs, (int)(rng() % 3), n_mats);
         const bool hostile = r % 2;
         if (hostile) {
-            damage(s.host_world_bvh, (int)(rng() % 3));
-            damage(s.host_trigs, 1 + (int)(rng() % 3));
-            if (rng() % 6 == 0) s.host_materials.resize(s.host_materials.size() - 3);
+            damage(world, (int)(rng() % 3));
+            damage(trigs, 1 + (int)(rng() % 3));
+            if (rng() % 6 == 0) mats.resize(mats.size() - 3);
         }
-        if (!links_sound(s.host_world_bvh) || !links_sound(s.host_actor_bvh)) continue;  // chunky_scene_set_bvh refuses these
-        const bool sound = bvh_leaves_sound(s.host_world_bvh, false, s.host_trigs, s.host_materials) &&
-                           bvh_leaves_sound(s.host_actor_bvh, false, s.host_trigs, s.host_materials);
+        int height = 0;
+        if (!bvh_links_height(world, &height) || !bvh_links_height(actor, &height)) continue;  // chunky_scene_set_bvh refuses these
+        const bool sound = bvh_leaves_sound(world, false, trigs, mats) && bvh_leaves_sound(actor, false, trigs, mats);
         if (!hostile && !sound) return fprintf(stderr, "round %d: a sound BVH was refused\n", r), 1;
         std::vector<int32_t> nodes, tris;
         int wr = 0, ar = 0;
-        const bool ok = build_bvh_records(&s, &nodes, &tris, &wr, &ar);
+        const bool ok = build_bvh_records(world, false, actor, false, trigs, mats, 0, 0, &nodes, &tris, &wr, &ar);
         if (!sound) {
             refused++;  // scene_view fails the render call; the records (built or not) are never used
             continue;
@@ -234,16 +209,15 @@ static int fuzz_bvh(int rounds) {
             if (!ref_ok(nodes[(size_t)i * 16]) || !ref_ok(nodes[(size_t)i * 16 + 1])) return fprintf(stderr, "round %d: dangling reference\n", r), 1;
         if (!ref_ok(wr) || !ref_ok(ar)) return fprintf(stderr, "round %d: dangling root\n", r), 1;
         for (int64_t t = 0; t < n_tri; t++)
-            if (tris[(size_t)t * 20 + 7] < 0 || (size_t)tris[(size_t)t * 20 + 7] / 2 >= s.host_materials.size() / 6) return fprintf(stderr, "round %d: material index\n", r), 1;
+            if (tris[(size_t)t * 20 + 7] < 0 || (size_t)tris[(size_t)t * 20 + 7] / 2 >= mats.size() / 6) return fprintf(stderr, "round %d: material index\n", r), 1;
         // the same BVHs placed as a breadth-first top over treelets (relayout_bvh_records, tiny sizes so that every branch of
         // it runs on these small trees): references resolve, and the tree they describe is the same tree
         {
-            static const char* const layouts[] = {"3,4", "0,2", "1,1000", "1000,3", "2,1"};
-            setenv("CHUNKY_BVH_LAYOUT", layouts[r % 5], 1);
+            static const int layouts[5][2] = {{3, 4}, {0, 2}, {1, 1000}, {1000, 3}, {2, 1}};  // (top, treelet)
+            const int* lay = layouts[r % 5];
             std::vector<int32_t> nodes2, tris2;
             int wr2 = 0, ar2 = 0;
-            const bool ok2 = build_bvh_records(&s, &nodes2, &tris2, &wr2, &ar2);
-            unsetenv("CHUNKY_BVH_LAYOUT");
+            const bool ok2 = build_bvh_records(world, false, actor, false, trigs, mats, lay[0], lay[1], &nodes2, &tris2, &wr2, &ar2);
             if (!ok2 || nodes2.size() != nodes.size() || tris2.size() != tris.size()) return fprintf(stderr, "round %d: re-layout changed the record counts\n", r), 1;
             const int64_t n_tri2 = (int64_t)tris2.size() / 20;
             for (int64_t i = 0; i < n_inner; i++)
@@ -256,7 +230,7 @@ static int fuzz_bvh(int rounds) {
             canonical(nodes, tris, ar, &a);
             canonical(nodes2, tris2, wr2, &b);
             canonical(nodes2, tris2, ar2, &b);
-            if (a != b) return fprintf(stderr, "round %d: re-layout %s changed the tree\n", r, layouts[r % 5]), 1;
+            if (a != b) return fprintf(stderr, "round %d: re-layout %d,%d changed the tree\n", r, lay[0], lay[1]), 1;
             relaid++;
         }
     }
@@ -267,26 +241,24 @@ static int fuzz_bvh(int rounds) {
 static int fuzz_emitters(int rounds) {
     long long listed = 0;
     for (int r = 0; r < rounds; r++) {
-        chunky_scene s;
         Palettes p = make_palettes(3, 2);
-        s.host_blocks = p.B;
-        s.host_materials = p.M;
-        s.octree_depth = 1 + (int)(rng() % 5);
+        const int depth = 1 + (int)(rng() % 5);
         // a tree whose branch values stay inside the array (what chunky_scene_set_octree checks) but may form cycles and over-deep chains
         const size_t groups = 1 + rng() % 40;
-        s.host_octree.assign(1 + 8 * groups, 0);
-        for (auto& v : s.host_octree) {
+        std::vector<int32_t> tree(1 + 8 * groups, 0);
+        for (auto& v : tree) {
             if (rng() % 3 == 0)
                 v = (int32_t)(1 + 8 * (rng() % groups));
             else
                 v = -(int32_t)(rng() % (p.B.size() + 8));
         }
-        if (r % 2) damage(s.host_blocks, 2), damage(s.host_materials, 1);
+        std::vector<int32_t> blocks = p.B, mats = p.M;
+        if (r % 2) damage(blocks, 2), damage(mats, 1);
         std::vector<int32_t> out;
-        list_emitters(&s, &out);
-        if (out.size() % 4 != 0 || out.size() / 4 > s.host_octree.size()) return fprintf(stderr, "round %d: emitter list size\n", r), 1;
+        list_emitters(tree, depth, blocks, mats, &out);
+        if (out.size() % 4 != 0 || out.size() / 4 > tree.size()) return fprintf(stderr, "round %d: emitter list size\n", r), 1;
         // (the same walk of caller-supplied leaves: how common model blocks are, which picks render_pool's sorted block tests)
-        const int share = model_leaf_permille(s.host_octree, s.host_blocks);
+        const int share = model_leaf_permille(tree, blocks);
         if (share < 0 || share > 1000) return fprintf(stderr, "round %d: model share %d\n", r, share), 1;
         listed += (long long)out.size() / 4;
     }

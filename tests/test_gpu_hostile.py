@@ -1,7 +1,7 @@
 """Scene data that points outside its own arrays must not fault the GPU.  The reference follows such ints blindly (undefined behaviour);
 here a model block whose pointer, primitive count or material pointers leave their palettes never intersects, an octree leaf beyond the
 block palette is air, and an entity BVH whose leaves or triangle materials leave their palettes makes the render call fail with
-CHUNKY_E_INVALID (capi.hip derive_records / bvh_leaves_sound; the host parsers themselves run under AddressSanitizer in
+CHUNKY_E_INVALID (scene_records.cpp derive_records / bvh_leaves_sound; the host parsers themselves run under AddressSanitizer in
 tests/test_sanitize.py).  Each batch renders in a child process: a memory fault would abort it."""
 import json
 import os

@@ -225,7 +225,7 @@ def test_render_loop_options_match_oracle(gpu_instance, port, name, draw, depth,
 
 def test_sorted_block_tests_run_where_asked(gpu_instance, port):
     """render_pool tests full cubes and model blocks in phases of their own where model blocks are common (from 30 per thousand of a
-    world's leaves on: capi.hip model_leaf_permille — the timed city, tests/test_timed_goldens.py; the golden worlds hold 29 and 0);
+    world's leaves on: scene_records.cpp model_leaf_permille — the timed city, tests/test_timed_goldens.py; the golden worlds hold 29 and 0);
     CHUNKY_OPT_KERNEL bit 8 / bit 9 force it.  Every combination renders the oracle's image."""
     seeds = scenes.java_random_ints(3)
     for name in ("outdoor", "outdoor_nosun", "indoor_sun"):
@@ -524,7 +524,7 @@ def test_run_callbacks_of_an_older_host(gpu_instance, port):
 @pytest.mark.parametrize("layout", ["5,3", "0,2", "4096,32"])
 def test_entity_bvh_record_placement_is_invisible(layout):
     """Where the entity-BVH records sit in memory (CHUNKY_BVH_LAYOUT: a breadth-first top over depth-first treelets,
-    capi.hip relayout_bvh_records) changes addresses only: image and per-trace records stay the reference's.  The variable is
+    scene_records.cpp relayout_bvh_records) changes addresses only: image and per-trace records stay the reference's.  The variable is
     read by the -DCHUNKY_TUNING build only (the shipping library reads no tuning variable): a child process loads that build."""
     import json
     import subprocess

@@ -345,3 +345,24 @@ def test_million_triangle_world(gpu_instance, port):
     compare_rows(r, port, sc, seeds, row_gids(sc, (411, 799)), "10^6 triangles")
     r.close()
     loader.close()
+
+
+def test_launch_clock_drains_in_mid_stream(gpu_instance, port):
+    """A launch clock (capi.hip LaunchClock) holds at most kClockDrain brackets: the call that finds more collects them
+    first, while later launches are still queued.  kClockDrain + 4 one-pass launches without a wait in between cross that
+    point once: the clock has counted every launch, a second read finds it zeroed, and the image is the oracle's."""
+    import re
+    text = open(os.path.join(native.CSRC, "capi.hip")).read()
+    n = int(re.search(r"kClockDrain = (\d+);", text).group(1)) + 4
+    sc = scenes.tiny_scene(width=16, height=16)  # a single tile
+    seeds = native.java_random_ints(n)
+    loader, r = make(gpu_instance, sc)
+    assert r.kernel_time() == (0.0, 0)
+    for i in range(n):
+        r.render_passes(seeds[i:i + 1], first_buffer_spp=i, sync=False)
+    ms, launches = r.kernel_time()
+    assert launches == n and ms > 0.0
+    assert r.kernel_time() == (0.0, 0)
+    np.testing.assert_array_equal(bits(r.read()), bits(port.render_passes(sc, seeds, threads=THREADS)))
+    r.close()
+    loader.close()

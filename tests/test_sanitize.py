@@ -1,5 +1,5 @@
 """Host-side code that runs on caller-supplied ints, under AddressSanitizer + UBSan on the CPU (GPU sanitizers do not exist on this
-pool): the octree re-layout of every scene upload (csrc/widetree.cpp) on random well-formed trees — every cell's leaf value and level
+pool): the records every scene upload derives from its palettes, BVHs and octree (csrc/scene_records.cpp), and the octree re-layout (csrc/widetree.cpp) on random well-formed trees — every cell's leaf value and level
 equal to the reference descent (K/octree.h:81-89) — and on damaged ones (wild branches, cycles, branches below level 0, pointers that do
 not fit), which have to be refused or expressed without a single out-of-bounds access."""
 import json
@@ -24,10 +24,11 @@ def test_widetree_under_asan_ubsan(tmp_path):
 
 
 def test_capi_host_parsers_under_asan_ubsan(tmp_path):
-    """derive_records / build_quad_aux / build_bvh_records / bvh_leaves_sound / list_emitters of capi.hip, compiled for the host only"""
-    exe = str(tmp_path / "capi_host_fuzz")
-    cmd = ["hipcc", "-x", "hip", "--offload-host-only", "-fno-gpu-sanitize", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-ffp-contract=off", os.path.join(ROOT, "tests", "sanitize", "capi_host_fuzz.cpp"), os.path.join(native.CSRC, "widetree.cpp"), "-o", exe]
+    """derive_records / build_quad_aux / bvh_links_height / build_bvh_records / bvh_leaves_sound / list_emitters of csrc/scene_records.cpp"""
+    exe = str(tmp_path / "scene_records_fuzz")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Wextra", "-Werror",
+           "-ffp-contract=off", os.path.join(ROOT, "tests", "sanitize", "scene_records_fuzz.cpp"), os.path.join(native.CSRC, "scene_records.cpp"),
+           os.path.join(native.CSRC, "widetree.cpp"), "-o", exe]
     proc = subprocess.run(cmd, capture_output=True, text=True)
     assert proc.returncode == 0, proc.stderr[-3000:]
     proc = subprocess.run([exe, "3000"], capture_output=True, text=True, timeout=600)
