@@ -275,6 +275,42 @@ hipError_t launch_camera_rays_selftest(const CameraView& C, int seed, float* out
     return hipGetLastError();
 }
 
+// chunky_selftest_shard_map: the slot -> pixel functions every image-writing kernel goes through, one thread per slot, as the
+// kernels call them — slots at and beyond T.n_local included (the padding of a launch's last tile).  Nothing is indexed by a gid:
+// the five results of slot i go to out[5 * i ...].  shard_gid is evaluated where the kernels evaluate it (a run shard or one rank,
+// below n_local); -1 elsewhere.
+__global__ void __launch_bounds__(256) shard_map_kernel(ShardView T, int width, int height, int n, FastDiv by_bw, int* __restrict__ out) {
+    const int slot = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (slot >= n) return;
+    const SlotPixel px = pool_slot_pixel(T, width, height, slot, by_bw);
+    int* o = out + 5 * (size_t)slot;
+    o[0] = pool_slot_gid(T, width, height, slot);
+    o[1] = px.gid; o[2] = px.x; o[3] = px.y;
+    o[4] = (slot < T.n_local && (T.world == 1 || T.tile != 0)) ? shard_gid(T, slot) : -1;
+}
+// ... and the division by a launch constant: out[i] = fast_quotient(a, {m, s}) for the triples (a, m, s) of `in` — the pairs (m, s)
+// made on the host by fast_div, as a launch's are
+__global__ void __launch_bounds__(256) fast_quotient_kernel(int n, const unsigned* __restrict__ in, int* __restrict__ out) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= n) return;
+    const unsigned* t = in + 3 * (size_t)i;
+    out[i] = (int)fast_quotient(t[0], FastDiv{t[1], (int)t[2]});
+}
+hipError_t launch_shard_map_selftest(int mode, const ShardView& T, int width, int height, int n, const unsigned* in, int* out, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (mode == 0) {
+        ShardView V = T;
+        V.list = nullptr;  // (the block mapping and the run formula only: no list is read)
+        V.n_list = 0;
+        hipLaunchKernelGGL(shard_map_kernel, grid, block, 0, stream, V, width, height, n, fast_div((unsigned)((width + kTileEdge - 1) >> kTileLog)), out);
+        return hipGetLastError();
+    }
+    if (mode != 1 || !in) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fast_quotient_kernel, grid, block, 0, stream, n, in, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_math_selftest(int which, int n, const float* a, const float* b, float* out, hipStream_t stream) {
     hipLaunchKernelGGL(math_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, which, n, a, b, out);
     return hipGetLastError();

@@ -236,32 +236,6 @@ struct chunky_render {
 
 constexpr size_t kStagingBytes = (size_t)8 << 30;  // 8 GiB: 1920x1080 x 256 passes is 6.4 GB (of 288)
 
-// The pixels of a block shard (tile 0) in block order, padding left out: what launch_fallback's kernels render when
-// render_pool does not apply to a sharded target (same ownership rule as pool_slot_gid, so the gather finds every pixel).
-static std::vector<int32_t> block_pixel_list(int width, int height, const ShardView& t) {
-    std::vector<int32_t> out;
-    const int bw = (width + 15) / 16, bh = (height + 15) / 16;
-    for (int64_t b = t.rank; b < (int64_t)bw * bh; b += t.world) {
-        const int bx = (int)(b % bw) * 16, by = (int)(b / bw) * 16;
-        for (int y = by; y < by + 16 && y < height; y++)
-            for (int x = bx; x < bx + 16 && x < width; x++) out.push_back(y * width + x);
-    }
-    return out;
-}
-
-static int n_local_slots(int width, int height, const ShardView& t) {
-    const int n_pixels = width * height;
-    if (t.world == 1) return n_pixels;
-    if (t.tile == 0) {  // 16 x 16 blocks rank, rank + world, ... of the image, edge blocks padded
-        const int n_blocks = ((width + 15) / 16) * ((height + 15) / 16);
-        const int mine = (n_blocks - t.rank + t.world - 1) / t.world;
-        return mine > 0 ? mine * 256 : 0;
-    }
-    int n_tiles = (n_pixels + t.tile - 1) / t.tile;
-    int mine = (n_tiles - t.rank + t.world - 1) / t.world;  // tiles rank, rank+world, ...
-    return mine > 0 ? mine * t.tile : 0;
-}
-
 // bytes of one AOV image (3 floats per pixel)
 static size_t aov_image_bytes(const chunky_render* r) { return (size_t)r->width * r->height * 3 * sizeof(float); }
 
@@ -982,12 +956,22 @@ static int each_part(chunky_render* r, F call) {
 #define FAN_RENDER(r, expr) \
     if ((r) && !(r)->parts.empty()) return each_part((r), [&](chunky_render* m_) { return expr; })
 
-// member i of n renders rank + world * i of world * n of the image (rank / world: the caller's own share, chunky_render_set_shard:
-// its tiles are t = rank (mod world); dealing them round-robin to n members gives member i the tiles t = rank + world * i (mod world * n))
-static int group_apply_shards(chunky_render* r) {
+// every member takes its share of the caller's own share (shard_map.hpp member_shard).  All or nothing: a group whose world * members
+// does not fit an int, or one member of which would need more slots than an int holds, is refused before any member changes
+static int group_apply_shards(chunky_render* r, const ShardView& outer) {
     const int n = (int)r->parts.size();
+    std::vector<ShardView> share((size_t)n);
+    for (int i = 0; i < n; i++) {
+        ShardView& m = share[(size_t)i];
+        if (!member_shard(outer, i, n, &m))
+            return fail(CHUNKY_E_INVALID, "set_shard: world %d x %d group members does not fit an int", outer.world, n);
+        ShardView stored;
+        if (!make_shard_view(r->width, r->height, m.rank, m.world, m.tile, &stored))
+            return fail(CHUNKY_E_INVALID, "set_shard: rank %d of %d in 16 x 16 blocks of a %d x %d image needs more than 2^31 pixel slots", m.rank, m.world, r->width, r->height);
+    }
     for (int i = 0; i < n; i++)
-        if (int rc = chunky_render_set_shard(r->parts[(size_t)i], r->outer.rank + r->outer.world * i, r->outer.world * n, r->outer.tile)) return rc;
+        if (int rc = chunky_render_set_shard(r->parts[(size_t)i], share[(size_t)i].rank, share[(size_t)i].world, share[(size_t)i].tile)) return rc;
+    r->outer = outer;
     return CHUNKY_OK;
 }
 
@@ -1010,7 +994,7 @@ extern "C" int chunky_render_create(chunky_ctx* ctx, chunky_scene* scene, int wi
             rc = chunky_render_create(ctx->members[i], scene->replicas[i], width, height, &part);
             if (rc == CHUNKY_OK) r->parts.push_back(part);
         }
-        if (rc == CHUNKY_OK) rc = group_apply_shards(r.get());
+        if (rc == CHUNKY_OK) rc = group_apply_shards(r.get(), r->outer);
         if (rc != CHUNKY_OK) {
             for (chunky_render* part : r->parts) (void)chunky_render_destroy(part);
             return rc;
@@ -1180,13 +1164,16 @@ extern "C" int chunky_render_set_shard(chunky_render* r, int rank, int world, in
     if (r && !r->parts.empty()) {
         if (world < 1 || rank < 0 || rank >= world || tile < 0) return fail(CHUNKY_E_INVALID, "set_shard: rank %d / world %d / tile %d", rank, world, tile);
         std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
-        r->outer = ShardView{rank, world, tile, 0};
-        return group_apply_shards(r);
+        // (the run length clamped as on a single target below; n_local stays 0: the members hold the slots)
+        return group_apply_shards(r, ShardView{rank, world, clamp_tile(r->width, r->height, tile), 0});
     }
     LOCK_RENDER(r);
     if (world < 1 || rank < 0 || rank >= world || tile < 0) return fail(CHUNKY_E_INVALID, "set_shard: rank %d / world %d / tile %d", rank, world, tile);
-    ShardView t{rank, world, tile, 0};
-    t.n_local = n_local_slots(r->width, r->height, t);
+    // The view is stored with its run length clamped to the pixel count (shard_map.hpp make_shard_view): the device functions never
+    // see a larger one, which is what keeps shard_gid's products within an int.
+    ShardView t;
+    if (!make_shard_view(r->width, r->height, rank, world, tile, &t))
+        return fail(CHUNKY_E_INVALID, "set_shard: rank %d of %d in 16 x 16 blocks of a %d x %d image needs more than 2^31 pixel slots", rank, world, r->width, r->height);
     if (r->shard.list) HIP_TRY(hipStreamSynchronize(r->ctx->stream));  // queued launches may still read the old list
     r->block_list.release();
     r->shard = t;
@@ -1741,8 +1728,9 @@ extern "C" int chunky_render_aov_passes(chunky_render* r, const int32_t* seeds, 
     if (n < 0 || (n > 0 && !seeds) || first_buffer_spp < 0) return fail(CHUNKY_E_INVALID, "aov_passes: bad arguments");
     if (r && !r->parts.empty()) {
         std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
-        ShardView t = r->outer;  // the caller's share of the image, all of it on member 0
-        t.n_local = n_local_slots(r->width, r->height, t);
+        ShardView t;  // the caller's share of the image, all of it on member 0
+        if (!make_shard_view(r->width, r->height, r->outer.rank, r->outer.world, r->outer.tile, &t))
+            return fail(CHUNKY_E_INVALID, "aov_passes: the group's share needs more than 2^31 pixel slots");
         return aov_passes(r->parts[0], t, seeds, n, first_buffer_spp);
     }
     if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
@@ -2496,6 +2484,48 @@ extern "C" int chunky_selftest_camera_rays(chunky_render* r, int32_t seed, float
     HIP_TRY(launch_camera_rays_selftest(r->cam, seed, (float*)dout.p, r->ctx->stream));
     HIP_TRY(hipMemcpyAsync(out, dout.p, (size_t)need * 4, hipMemcpyDeviceToHost, r->ctx->stream));
     HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+// the view comes from make_shard_view, as chunky_render_set_shard's does: the test sees what a render would see
+extern "C" int chunky_selftest_shard_map(chunky_ctx* ctx, int mode, int width, int height, int rank, int world, int tile, int n,
+                                         const uint32_t* pairs, int32_t* out, int32_t view_out[4]) {
+    if (!ctx) return fail(CHUNKY_E_INVALID, "NULL context");
+    if (!ctx->members.empty()) ctx = ctx->members[0];
+    if (mode != 0 && mode != 1) return fail(CHUNKY_E_INVALID, "selftest_shard_map: mode %d", mode);
+    if (n < 0 || n > (1 << 24) || (n > 0 && !out) || (mode == 1 && n > 0 && !pairs)) return fail(CHUNKY_E_INVALID, "selftest_shard_map: bad arguments");
+    ShardView T{0, 1, 256, 0};
+    if (mode == 0) {
+        if (width <= 0 || height <= 0 || (int64_t)width * height > (1 << 30)) return fail(CHUNKY_E_INVALID, "bad image size %dx%d", width, height);
+        if (world < 1 || rank < 0 || rank >= world || tile < 0) return fail(CHUNKY_E_INVALID, "set_shard: rank %d / world %d / tile %d", rank, world, tile);
+        if (!make_shard_view(width, height, rank, world, tile, &T)) return fail(CHUNKY_E_INVALID, "selftest_shard_map: the share needs more than 2^31 pixel slots");
+        // a block share maps slot -> block (slot / 256) * world + rank before it looks at n_local: only slot counts that keep that an int
+        if (T.world != 1 && T.tile == 0 && n > 0 && (int64_t)((n - 1) >> 8) * T.world + T.rank > INT_MAX)
+            return fail(CHUNKY_E_INVALID, "selftest_shard_map: %d slots of a block share of %d ranks leave the range of an int", n, world);
+        if (view_out) {
+            view_out[0] = T.rank; view_out[1] = T.world; view_out[2] = T.tile; view_out[3] = T.n_local;
+        }
+    }
+    if (n == 0) return CHUNKY_OK;
+    std::lock_guard<std::recursive_mutex> g(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevBuf din, dout;
+    const size_t out_bytes = (size_t)n * (mode == 0 ? 5 : 1) * 4;
+    std::vector<uint32_t> triples;
+    if (mode == 1) {  // (a, d) -> (a, m, s): the pair of the divisor made here, on the host, as launch_pool makes a launch's
+        triples.resize((size_t)n * 3);
+        for (int i = 0; i < n; i++) {
+            const FastDiv f = fast_div(pairs[2 * (size_t)i + 1]);
+            triples[3 * (size_t)i] = pairs[2 * (size_t)i];
+            triples[3 * (size_t)i + 1] = f.m;
+            triples[3 * (size_t)i + 2] = (uint32_t)f.s;
+        }
+        HIP_TRY(din.upload(triples.data(), triples.size() * 4, ctx->stream));
+    }
+    HIP_TRY(hipMalloc(&dout.p, out_bytes));
+    HIP_TRY(launch_shard_map_selftest(mode, T, width, height, n, (const unsigned*)din.p, (int*)dout.p, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, dout.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return CHUNKY_OK;
 }
 

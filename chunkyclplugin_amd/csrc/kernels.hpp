@@ -6,6 +6,8 @@
 
 #include <atomic>
 
+#include "shard_map.hpp"  // ShardView, FastDiv: the host arithmetic of the shard-to-pixel map
+
 struct DnCoeffs;  // denoise_spec.h
 
 namespace chunky {
@@ -16,16 +18,6 @@ struct RenderOpts;
 
 constexpr int kMaxTraces = 10;        // 5 path segments x (main + shadow trace)
 constexpr int kBvhStackEntries = 64;  // K/bvh.h:38
-
-// Image-tile ownership of this process: tiles of `tile` consecutive pixel
-// indices dealt round-robin over `world` ranks; n_local = pixel slots owned by `rank`.
-struct ShardView {
-    int rank, world, tile, n_local;
-    // block shards (tile 0) under a kernel that cannot map 16 x 16 blocks itself (launch_fallback): the rank's pixels, in
-    // block order, as an explicit list on the device (capi.hip block_pixel_list); null otherwise
-    const int* list = nullptr;
-    int n_list = 0;
-};
 
 // Layout shared with include/chunky_hip.h (chunky_hit_record) and oracle/oracle_scene.h.
 struct HitRecord {
@@ -157,5 +149,8 @@ hipError_t launch_helpers_selftest(const SceneView& S, int which, int tree, int 
 hipError_t launch_math_selftest(int which, int n, const float* a, const float* b, float* out, hipStream_t stream);
 // projected camera self test (aux_kernels.hip camera_rays_kernel): width * height * 6 floats, origin then direction per pixel.
 hipError_t launch_camera_rays_selftest(const CameraView& C, int seed, float* out, hipStream_t stream);
+// the shard-to-pixel map (aux_kernels.hip shard_map_kernel).  mode 0: 5 ints per slot 0 .. n - 1 of shard T — pool_slot_gid, the gid /
+// x / y of pool_slot_pixel, shard_gid (-1 where it does not apply); mode 1: fast_quotient(a, {m, s}) for n triples (a, m, s) of `in`
+hipError_t launch_shard_map_selftest(int mode, const ShardView& T, int width, int height, int n, const unsigned* in, int* out, hipStream_t stream);
 
 }  // namespace chunky

@@ -205,6 +205,8 @@ DEV int shard_gid(const ShardView& T, int local) {
     // local pixel slot -> global pixel index: tiles of T.tile consecutive gids dealt round-robin
     if (T.world == 1) return local;
     if (T.list) return T.list[local];  // block shards under a kernel without the block mapping: the rank's pixels listed
+    // (within an int by construction: T.tile is at most the pixel count — shard_map.hpp make_shard_view clamps it — and for
+    // local < T.n_local run t * world + rank is one of the image's runs, so the sum is below pixel count + tile <= 2^31)
     int t = local / T.tile, w = local - t * T.tile;
     return (t * T.world + T.rank) * T.tile + w;
 }
@@ -239,19 +241,7 @@ DEV int pool_slot_gid(const ShardView& T, int width, int height, int slot) {
               y = (by << kTileLog) + (sb / (kTileEdge / kSubW)) * kSubH + px / kSubW;
     return (x < width && y < height) ? y * width + x : width * height;
 }
-// Exact n / d for n < 2^31 by one multiply-high and one shift (d fixed for a launch, the pair made on the host): with 2^s < d <= 2^(s+1)
-// and m = ceil(2^(32+s) / d) — a 32-bit number — the error term m * d - 2^(32+s) is below d, and n * d < 2^(32+s) keeps the quotient exact.
-struct FastDiv {
-    unsigned m;  // 0: d == 1
-    int s;
-};
-inline FastDiv fast_div(unsigned d) {
-    if (d <= 1) return FastDiv{0u, 0};
-    int s = 0;
-    while ((2u << s) < d) s++;  // 2^s < d <= 2^(s+1)
-    const unsigned long long m = (((unsigned long long)1 << (32 + s)) + d - 1) / d;
-    return FastDiv{(unsigned)m, s};
-}
+// Exact n / d for n < 2^31 by one multiply-high and one shift: the pair comes from the host (shard_map.hpp fast_div, where the proof is)
 DEV unsigned fast_quotient(unsigned n, FastDiv f) { return f.m ? __umulhi(n, f.m) >> f.s : n; }
 
 // pool_slot_gid with the pixel's column and row, and the division by the tile row length as a multiply (render_pool's new samples)

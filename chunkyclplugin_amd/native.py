@@ -227,6 +227,7 @@ def lib() -> C.CDLL:
             "chunky_selftest_helpers": [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(i32)],
             "chunky_selftest_gamma_scan": [vp, C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(f32)],
             "chunky_selftest_camera_rays": [vp, i32, vp, i64],
+            "chunky_selftest_shard_map": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp],
             "chunky_camera_rays": [C.c_int, vp, i64, C.c_int, C.c_int, i32, vp],
             "chunky_filter_frame": [vp, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int],
             "chunky_filter_gamma_thresholds": [vp],

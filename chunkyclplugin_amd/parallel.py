@@ -18,13 +18,15 @@ import numpy as np
 
 def local_slots(n_pixels: int, rank: int, world: int, tile: int, width: int = 0) -> int:
     """Pixel slots (whole tiles, padding included) owned by `rank` — ShardView.n_local on the device.
-    tile = 0: 16 x 16 blocks of an image `width` pixels wide; tile > 0: runs of `tile` pixel indices."""
+    tile = 0: 16 x 16 blocks of an image `width` pixels wide; tile > 0: runs of `tile` pixel indices (a tile at or above the pixel
+    count is the pixel count: csrc/shard_map.hpp clamp_tile)."""
     if world == 1:
         return n_pixels
     if tile == 0:
         assert width > 0 and n_pixels % width == 0, "block shards need the image width"
         n_blocks = ((width + 15) // 16) * ((n_pixels // width + 15) // 16)
         return max((n_blocks - rank + world - 1) // world, 0) * 256
+    tile = min(tile, n_pixels)
     n_tiles = (n_pixels + tile - 1) // tile
     mine = (n_tiles - rank + world - 1) // world
     return max(mine, 0) * tile
@@ -38,9 +40,11 @@ def owned_gids(n_pixels: int, rank: int, world: int, tile: int = 256, width: int
     if tile == 0:
         height, bw = n_pixels // width, (width + 15) // 16
         b = (slots // 256) * world + rank
-        x, y = (b % bw) * 16 + (slots % 16), (b // bw) * 16 + (slots % 256) // 16
+        sb, px = (slots % 256) // 4, slots % 4  # 2 x 2 sub-blocks row-major over the block, row-major inside (pool_slot_gid)
+        x, y = (b % bw) * 16 + (sb % 8) * 2 + px % 2, (b // bw) * 16 + (sb // 8) * 2 + px // 2
         ok = (x < width) & (y < height)
         return (y * width + x)[ok].astype(np.int32)
+    tile = min(tile, n_pixels)
     t, w = slots // tile, slots % tile
     gid = (t * world + rank) * tile + w
     return gid[gid < n_pixels].astype(np.int32)

@@ -117,6 +117,21 @@ class RendererInstance:
         check(native.lib().chunky_selftest_math(self._h, which, a.size, ptr(a), ptr(b), ptr(out)))
         return out
 
+    def selftest_shard_map(self, width: int, height: int, rank: int, world: int, tile: int, n_slots: int):
+        """chunky_selftest_shard_map, mode 0: the device's slot -> pixel functions on the view set_shard would store.  Returns
+        (rows (n_slots, 5) int32 = pool_slot_gid, pool_slot_pixel gid / x / y, shard_gid or -1; view = (rank, world, clamped tile, n_local))."""
+        out = np.zeros((int(n_slots), 5), np.int32)
+        view = np.zeros(4, np.int32)
+        check(native.lib().chunky_selftest_shard_map(self._h, 0, width, height, rank, world, tile, int(n_slots), None, ptr(out), ptr(view)))
+        return out, tuple(int(v) for v in view)
+
+    def selftest_fast_quotient(self, n, d) -> np.ndarray:
+        """chunky_selftest_shard_map, mode 1: n // d as the kernels divide by a launch constant (n < 2^31, d >= 1)."""
+        pairs = np.ascontiguousarray(np.stack([np.asarray(n, np.uint32), np.asarray(d, np.uint32)], axis=1))
+        out = np.zeros(len(pairs), np.int32)
+        check(native.lib().chunky_selftest_shard_map(self._h, 1, 0, 0, 0, 1, 0, len(pairs), ptr(pairs), ptr(out), None))
+        return out
+
     def selftest_gamma_scan(self, curve: int, first_bits: int, count: int):
         """(values whose tone-map byte differs from the threshold table's, worst stray of the estimate) over `count` float bit patterns."""
         bad, worst = C.c_uint64(0), C.c_float(0)

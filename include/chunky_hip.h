@@ -240,9 +240,15 @@ int chunky_render_set_option(chunky_render* r, int option, int32_t value);
  * runs as fast per pixel as the whole image (other kernels refuse it); tile > 0: pixel indices are
  * cut into runs of `tile` consecutive gids, run t belongs to rank t % world (every kernel).
  * A rank renders only its tiles; every other pixel of its buffer stays 0, so a SUM reduce over
- * ranks (one RCCL collective per read-back) reproduces the 1-GPU image bit for bit. */
+ * ranks (one RCCL collective per read-back) reproduces the 1-GPU image bit for bit.
+ * Any tile >= 0 and any 0 <= rank < world <= INT_MAX are taken.  A tile at or above the pixel count acts exactly as
+ * tile = width * height (it is stored clamped): rank 0 owns every pixel, every other rank none.  A rank at or beyond the number of
+ * tiles or blocks owns nothing: render, AOV, read and gather calls on it return CHUNKY_OK having done nothing.  CHUNKY_E_INVALID
+ * for the one share whose slots do not fit an int: 16 x 16 blocks (256 slots each) of an image so thin that a rank's blocks hold
+ * more than 2^31 slots (e.g. 1 x 2^30 pixels over 2 ranks). */
 int chunky_render_set_shard(chunky_render* r, int rank, int world, int tile);
-/* (On a group's render target the members split the caller's share again: member i of n renders as rank + world * i of world * n.) */
+/* (On a group's render target the members split the caller's share again: member i of n renders as rank + world * i of world * n;
+ * CHUNKY_E_INVALID, with no member changed, when world * n does not fit an int or a member's share is the one refused above.) */
 /* Use a caller-owned device buffer (3*width*height floats) as the framebuffer, e.g. a torch tensor
  * that torch.distributed reduces over RCCL.  NULL returns to the internal buffer.
  * Ordering contract: the library runs on its own non-blocking stream and only synchronises THAT stream here.  The caller
@@ -579,6 +585,17 @@ int chunky_selftest_helpers(chunky_scene* scene, int which, int tree, int n, con
  * target's camera for `seed`; out receives width*height*6 floats (n_floats must be that), as chunky_camera_rays lays them out.
  * CHUNKY_E_STATE unless the target has a projected camera. */
 int chunky_selftest_camera_rays(chunky_render* r, int32_t seed, float* out, int64_t n_floats);
+
+/* ---- self test of the shard-to-pixel map (no reference counterpart): the device functions every image-writing kernel takes its
+ * pixels from, on the view chunky_render_set_shard would store for (rank, world, tile) on a width x height image (view_out, if not
+ * NULL, receives it: rank, world, the clamped tile, the rank's pixel slots n_local).  mode 0: for slots 0 .. n - 1 — slots at and
+ * beyond n_local are part of the domain — out receives 5 ints per slot: the slot's pixel index (width * height for a padding
+ * slot), the pixel index / column / row as the pool kernel derives them for a new sample, and the run formula's pixel index where
+ * it applies (one rank or tile > 0, slot < n_local; -1 elsewhere).  mode 1: `pairs` holds n pairs (a, d) of uint32 with
+ * a < 2^31, d >= 1; out receives the n quotients a / d as the kernels compute them (one multiply-high and one shift by a pair
+ * made on the host); width .. tile are ignored.  n <= 2^24. */
+int chunky_selftest_shard_map(chunky_ctx* ctx, int mode, int width, int height, int rank, int world, int tile, int n,
+                              const uint32_t* pairs, int32_t* out, int32_t view_out[4]);
 
 /* ---- self test of the tone map's byte estimate (no reference counterpart): `count` consecutive float bit patterns from
  * first_bits through the fast path of the GAMMA (curve 0) or ACES (curve 2) filter (hardware log2 / exp2 / reciprocal

@@ -359,15 +359,16 @@ def test_shards_sum_to_full_image(gpu_instance, world, tile):
     r.render_passes(seeds)
     full = r.read()
     total = np.zeros_like(full)
-    owned = np.zeros(full.size // 3, np.int32)
+    owner = (np.arange(full.size // 3) // tile) % world  # run t of `tile` pixel indices belongs to rank t % world
     for rank in range(world):
         r.set_shard(rank, world, tile)
         r.reset()
         r.render_passes(seeds)
         part = r.read()
-        owned += (part.reshape(-1, 3) != 0).any(axis=1)
+        # the one-rank image inside the rank's own runs and exactly zero outside: a black pixel rendered by the wrong rank fails too
+        want = np.where((owner == rank)[:, None], full.reshape(-1, 3), np.float32(0))
+        np.testing.assert_array_equal(bits(part.reshape(-1, 3)), bits(want))
         total += part                                    # what the RCCL SUM reduce does
-    assert owned.max() <= 1
     np.testing.assert_array_equal(bits(total), bits(full))
     r.close()
     loader.close()
