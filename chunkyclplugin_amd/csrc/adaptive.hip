@@ -12,6 +12,8 @@
 //                          2 x 2 block: the 256 samples a wave of render_pool claims stay coherent rays)
 //   adaptive_scan_kernel   exclusive scan over the tile counts (one workgroup: a 1920 x 1080 image has 8 160 tiles) and the total
 //   adaptive_finish_kernel pixels still active at the end record the passes rendered
+//   adaptive_count_kernel  the tile counts of an activity map that is already final (a restored state): with the scan and the scatter
+//                          it rebuilds the list
 //
 // Compiled with -ffp-contract=off (see rt_device.hpp).
 #include <hip/hip_runtime.h>
@@ -96,6 +98,22 @@ __global__ void __launch_bounds__(256) adaptive_tile_kernel(int width, int heigh
     }
 }
 
+// The counting half of adaptive_tile_kernel<false> for an activity map that is already final (chunky_render_adaptive_restore): a
+// tile's active slots, nothing tested and nothing written to the maps.  Followed by adaptive_scan_kernel and
+// adaptive_tile_kernel<true> it rebuilds the list a run held after the check that left this map, entry for entry.
+__global__ void __launch_bounds__(256) adaptive_count_kernel(int width, int height, const unsigned char* __restrict__ active, int* __restrict__ tile_counts) {
+    __shared__ int wave_count[4];
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    const int slot = (int)(blockIdx.x * 256 + threadIdx.x);
+    const ShardView whole{0, 1, 256, width * height};
+    const int gid = pool_slot_gid(whole, width, height, slot);
+    const bool a = gid < width * height && active[gid] != 0;
+    const unsigned long long mask = __ballot(a);
+    if (lane == 0) wave_count[wave] = (int)__builtin_popcountll(mask);
+    __syncthreads();
+    if (threadIdx.x == 0) tile_counts[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+}
+
 __global__ void __launch_bounds__(1024) adaptive_scan_kernel(const int* __restrict__ counts, int* __restrict__ offsets, int n_tiles, int* __restrict__ total) {
     __shared__ int wave_sum[16];
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -148,6 +166,17 @@ hipError_t launch_adaptive_check(int width, int height, const float* stat, unsig
     hipLaunchKernelGGL(adaptive_scan_kernel, dim3(1), dim3(1024), 0, stream, (const int*)tile_counts, tile_offsets, n_tiles, total);
     hipLaunchKernelGGL(adaptive_tile_kernel<true>, dim3((unsigned)n_tiles), dim3(256), 0, stream, width, height, (const unsigned char*)unconv,
                        active, count, n, tile_counts, (const int*)tile_offsets, list);
+    return hipGetLastError();
+}
+
+hipError_t launch_adaptive_rebuild(int width, int height, unsigned char* active, int* tile_counts, int* tile_offsets, int* list, int* total,
+                                   hipStream_t stream) {
+    const int n_tiles = ((width + kTileEdge - 1) >> kTileLog) * ((height + kTileEdge - 1) >> kTileLog);
+    hipLaunchKernelGGL(adaptive_count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, stream, width, height, (const unsigned char*)active, tile_counts);
+    hipLaunchKernelGGL(adaptive_scan_kernel, dim3(1), dim3(1024), 0, stream, (const int*)tile_counts, tile_offsets, n_tiles, total);
+    // (the scatter reads neither unconv nor count, and writes only the list)
+    hipLaunchKernelGGL(adaptive_tile_kernel<true>, dim3((unsigned)n_tiles), dim3(256), 0, stream, width, height, (const unsigned char*)nullptr, active,
+                       (int*)nullptr, 0, tile_counts, (const int*)tile_offsets, list);
     return hipGetLastError();
 }
 

@@ -36,3 +36,38 @@ RT_FN int ad_unconverged(float m, float M2, int n, float t2, float floor_) {
 RT_FN int ad_check_due(int n, int min_spp, int check_interval, int max_spp) {
     return n >= min_spp && n < max_spp && (n - min_spp) % check_interval == 0;
 }
+
+/* ---- continuing a run (include/chunky_hip.h, "adaptive sampling that stops and continues").  The check points are the grid
+ * min_spp + j * check_interval, j >= 0. */
+
+/* the largest grid point <= n, 0 when there is none */
+RT_FN int ad_grid_floor(int n, int min_spp, int check_interval) {
+    return n < min_spp ? 0 : n - (n - min_spp) % check_interval;
+}
+
+/* the grid point before the grid point g, 0 when g is the first */
+RT_FN int ad_grid_before(int g, int min_spp, int check_interval) { return g - check_interval >= min_spp ? g - check_interval : 0; }
+
+/* 1 when n is a grid point */
+RT_FN int ad_on_grid(int n, int min_spp, int check_interval) { return n >= min_spp && (n - min_spp) % check_interval == 0; }
+
+/* One step of the loop, for a state of `passes` passes whose last check ran at `last_check` (0 = none yet), towards max_spp:
+ *   check_first  1 when the check at `passes` is due under this max_spp and has not been run — the run that stopped here ended on its
+ *                own max_spp, where no check is made.  The caller runs it, sets last_check = passes and asks again.
+ *   round        otherwise the passes of the next round: up to the next grid point or to max_spp, whichever comes first (a state off
+ *                the grid takes a short round); 0 when passes >= max_spp.  The round's check is due iff ad_check_due(passes + round).
+ * From the empty state (0, 0) this is the loop of a single run: min_spp passes, then check_interval at a time. */
+typedef struct ad_step_t {
+    int check_first, round;
+} ad_step_t;
+
+RT_FN ad_step_t ad_step(int passes, int last_check, int min_spp, int check_interval, int max_spp) {
+    ad_step_t s;
+    s.check_first = ad_check_due(passes, min_spp, check_interval, max_spp) && last_check != passes;
+    s.round = 0;
+    if (s.check_first || passes >= max_spp) return s;
+    const int left = max_spp - passes; /* (distances, not end points: no sum here can pass INT_MAX) */
+    const int to_grid = passes < min_spp ? min_spp - passes : check_interval - (passes - min_spp) % check_interval;
+    s.round = to_grid < left ? to_grid : left;
+    return s;
+}

@@ -223,6 +223,12 @@ struct chunky_render {
     DevBuf ad_stat, ad_count, ad_flags, ad_tiles, ad_list;
     int32_t* ad_total_host = nullptr;
     bool ad_valid = false;  // an adaptive run has finished: the maps can be read
+    // The state chunky_render_adaptive_resume continues (header; the arrays are fb, ad_count, ad_stat and the first half of ad_flags,
+    // and ad_list holds the active pixels whenever fewer than all are active).  ad_resumable: the framebuffer, the maps and what a pass
+    // renders are as the run that wrote ad_state left them — cleared by every call that writes the framebuffer or changes the
+    // camera, the options, the shard or the buffer
+    chunky_adaptive_state ad_state{};
+    bool ad_resumable = false;
     LaunchClock ad_clock{&free_events};  // one bracket per round
     ~chunky_render() {
         if (ad_total_host) (void)hipHostFree(ad_total_host);
@@ -1103,6 +1109,7 @@ extern "C" int chunky_render_set_camera(chunky_render* r, int projector_type, co
         int64_t need = (int64_t)r->width * r->height * 6;
         if (n != need) return fail(CHUNKY_E_INVALID, "set_camera: pre-generated rays need %lld floats, got %lld", (long long)need, (long long)n);
         HIP_TRY(hipStreamSynchronize(r->ctx->stream));  // rays may still be read by queued passes
+        r->ad_resumable = false;  // (before the table changes: an upload that fails half way has changed it too)
         HIP_TRY(r->rays.upload(settings, (size_t)n * 4, r->ctx->stream));
         c.rays = (const float*)r->rays.p;
     } else if (projector_type >= CHUNKY_PROJ_PARALLEL && projector_type <= CHUNKY_PROJ_STEREOGRAPHIC) {
@@ -1118,6 +1125,7 @@ extern "C" int chunky_render_set_camera(chunky_render* r, int projector_type, co
     }
     c.projector_type = projector_type;
     r->have_camera = true;
+    r->ad_resumable = false;  // what a pass renders changes: an adaptive run cannot continue across it
     return CHUNKY_OK;
 }
 
@@ -1157,6 +1165,7 @@ extern "C" int chunky_render_set_option(chunky_render* r, int option, int32_t va
             break;
         default: return fail(CHUNKY_E_INVALID, "unknown option %d", option);
     }
+    r->ad_resumable = false;  // (an option was set: a refused call ends nothing)
     return CHUNKY_OK;
 }
 
@@ -1177,6 +1186,7 @@ extern "C" int chunky_render_set_shard(chunky_render* r, int rank, int world, in
     if (r->shard.list) HIP_TRY(hipStreamSynchronize(r->ctx->stream));  // queued launches may still read the old list
     r->block_list.release();
     r->shard = t;
+    r->ad_resumable = false;
     r->launch_cap = 0;  // the share changed: so does what a launch can stage
     return CHUNKY_OK;
 }
@@ -1184,6 +1194,7 @@ extern "C" int chunky_render_set_shard(chunky_render* r, int rank, int world, in
 extern "C" int chunky_render_set_device_buffer(chunky_render* r, void* device_ptr) {
     if (r && !r->parts.empty()) return chunky_render_set_device_buffer(r->parts[0], device_ptr);  // the image lives on member 0
     LOCK_RENDER(r);
+    r->ad_resumable = false;  // the image an adaptive run would continue stays in the other buffer
     HIP_TRY(hipStreamSynchronize(r->ctx->stream));
     r->fb = device_ptr ? (float*)device_ptr : (float*)r->own_fb.p;
     return CHUNKY_OK;
@@ -1200,6 +1211,7 @@ extern "C" int chunky_render_device_buffer(chunky_render* r, void** device_ptr) 
 extern "C" int chunky_render_reset(chunky_render* r) {
     FAN_RENDER(r, chunky_render_reset(m_));
     LOCK_RENDER(r);
+    r->ad_resumable = false;
     HIP_TRY(hipMemsetAsync(r->fb, 0, (size_t)r->width * r->height * 3 * sizeof(float), r->ctx->stream));
     return CHUNKY_OK;
 }
@@ -1303,6 +1315,7 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
     if (int rc = scene_view(r->scene, &S, r->opts.nee != 0)) return rc;
     S.bvh_cull = r->opts.bvh_cull;
     if (int rc = check_extended_opts("render_passes", r, S)) return rc;
+    r->ad_resumable = false;  // the call is accepted: it writes the framebuffer (chunky_render_run / _run_ex end it here and in chunky_render_reset)
     if (r->clock.full())
         if (int rc = r->clock.collect()) return rc;
     if (r->shard.n_local <= 0) return CHUNKY_OK;  // this rank (or group member) owns no tile of so small an image: nothing to render
@@ -1849,6 +1862,137 @@ extern "C" int chunky_adaptive_host(int width, int height, const float* samples,
     return CHUNKY_OK;
 }
 
+// ---- the state of a run and its continuation on the host (include/chunky_hip.h, "adaptive sampling that stops and continues")
+constexpr size_t kAdaptiveStateFirst = offsetof(chunky_adaptive_state, summary) + sizeof(chunky_adaptive_summary);  // the first version of the struct
+
+static void adaptive_empty_state(int width, int height, const chunky_adaptive_params& p, chunky_adaptive_state* s) {
+    memset(s, 0, sizeof *s);
+    s->size = sizeof *s;
+    s->width = width;
+    s->height = height;
+    s->active = width * height;
+    s->params = p;
+}
+
+static int adaptive_dims(const char* who, int width, int height) {
+    if (width <= 0 || height <= 0 || (int64_t)width * height > INT32_MAX / 16) return fail(CHUNKY_E_INVALID, "%s: bad size %dx%d", who, width, height);
+    return CHUNKY_OK;
+}
+
+// chunky_adaptive_state_check; *s receives the state as far as this library knows the caller's struct, its params checked
+static int adaptive_state_valid(const char* who, const chunky_adaptive_state* st, const int32_t* count, const uint8_t* active, chunky_adaptive_state* s) {
+    if (!st || !count || !active) return fail(CHUNKY_E_INVALID, "%s: NULL argument", who);
+    if (st->size < kAdaptiveStateFirst) return fail(CHUNKY_E_INVALID, "%s: state.size %zu is smaller than the struct (%zu)", who, st->size, kAdaptiveStateFirst);
+    memset(s, 0, sizeof *s);
+    memcpy(s, st, st->size < sizeof *s ? st->size : sizeof *s);
+    if (int rc = adaptive_dims(who, s->width, s->height)) return rc;
+    chunky_adaptive_params p;
+    if (int rc = adaptive_params(who, &s->params, INT32_MAX, &p)) return rc;
+    s->params = p;
+    if (s->passes < 0) return fail(CHUNKY_E_INVALID, "%s: %d passes", who, s->passes);
+    const int g = ad_grid_floor(s->passes, p.min_spp, p.check_interval);
+    const int before = g == s->passes ? ad_grid_before(g, p.min_spp, p.check_interval) : g;  // (no grid point <= passes: g = 0 = before)
+    if (s->last_check != g && s->last_check != before)
+        return fail(CHUNKY_E_INVALID, "%s: last_check %d after %d passes (min_spp %d, check_interval %d: %d%s%d)", who, s->last_check, s->passes, p.min_spp,
+                    p.check_interval, g, g == before ? " = " : " or ", before);
+    const size_t np = (size_t)s->width * s->height;
+    int64_t ones = 0, samples = 0;
+    for (size_t i = 0; i < np; i++) {
+        if (active[i] > 1) return fail(CHUNKY_E_INVALID, "%s: active[%zu] is %d, not 0 or 1", who, i, (int)active[i]);
+        if (active[i]) {
+            if (count[i] != s->passes) return fail(CHUNKY_E_INVALID, "%s: pixel %zu is active with count %d after %d passes", who, i, count[i], s->passes);
+            ones += 1;
+        } else if (!ad_on_grid(count[i], p.min_spp, p.check_interval) || count[i] > s->last_check) {
+            return fail(CHUNKY_E_INVALID, "%s: pixel %zu is inactive with count %d, which is no check point up to the last check (%d)", who, i, count[i], s->last_check);
+        }
+        samples += count[i];
+    }
+    if (ones != s->active) return fail(CHUNKY_E_INVALID, "%s: state.active is %d, the map holds %lld active pixels", who, s->active, (long long)ones);
+    if (s->summary.passes != s->passes) return fail(CHUNKY_E_INVALID, "%s: summary.passes %d, passes %d", who, s->summary.passes, s->passes);
+    if (s->summary.samples != samples) return fail(CHUNKY_E_INVALID, "%s: summary.samples %lld, the counts add up to %lld", who, (long long)s->summary.samples, (long long)samples);
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_adaptive_state_check(const chunky_adaptive_state* st, const int32_t* count, const uint8_t* active) {
+    chunky_adaptive_state s;
+    return adaptive_state_valid("adaptive_state_check", st, count, active, &s);
+}
+
+extern "C" int chunky_adaptive_host_begin(int width, int height, const chunky_adaptive_params* params, chunky_adaptive_state* st, int32_t* count,
+                                          float* mean, float* stat, uint8_t* active) {
+    chunky_adaptive_params p;
+    if (int rc = adaptive_params("adaptive_host_begin", params, INT32_MAX, &p)) return rc;
+    if (int rc = adaptive_dims("adaptive_host_begin", width, height)) return rc;
+    if (!st || !count || !mean || !stat || !active) return fail(CHUNKY_E_INVALID, "adaptive_host_begin: NULL argument");
+    if (st->size < kAdaptiveStateFirst)
+        return fail(CHUNKY_E_INVALID, "adaptive_host_begin: st->size %zu is smaller than the struct (%zu): set it to sizeof(chunky_adaptive_state)", st->size, kAdaptiveStateFirst);
+    const size_t np = (size_t)width * height, size = st->size;
+    chunky_adaptive_state s;
+    adaptive_empty_state(width, height, p, &s);
+    memcpy(st, &s, size < sizeof s ? size : sizeof s);
+    st->size = size;
+    memset(count, 0, np * sizeof(int32_t));
+    memset(mean, 0, 3 * np * sizeof(float));
+    memset(stat, 0, 2 * np * sizeof(float));
+    memset(active, 1, np);
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_adaptive_host_resume(chunky_adaptive_state* st, const float* samples, int n, int32_t* count, float* mean, float* stat,
+                                           uint8_t* active) {
+    chunky_adaptive_state s;
+    if (int rc = adaptive_state_valid("adaptive_host_resume", st, count, active, &s)) return rc;
+    if (!mean || !stat) return fail(CHUNKY_E_INVALID, "adaptive_host_resume: NULL argument");
+    if (n < 0 || (n > 0 && !samples) || n > INT32_MAX - s.passes) return fail(CHUNKY_E_INVALID, "adaptive_host_resume: %d more passes after %d", n, s.passes);
+    const chunky_adaptive_params& p = s.params;
+    const int width = s.width, height = s.height, first = s.passes, max_spp = s.passes + n;
+    const size_t np = (size_t)width * height;
+    const float t2 = p.threshold * p.threshold;
+    std::vector<unsigned char> unconv(np, 0);
+    while (s.passes < max_spp && s.active > 0) {
+        const ad_step_t step = ad_step(s.passes, s.last_check, p.min_spp, p.check_interval, max_spp);
+        // (The fold and the check below are written out a second time on purpose: chunky_adaptive_host above stays as it was, the
+        // independent single run that P1 and P2 hold this loop to.)
+        for (int k = 0; k < step.round; k++) {  // (no pass when the step is the check the earlier run did not make)
+            const int spp = s.passes + k;
+            const float* c = samples + 3 * np * (size_t)(spp - first);
+            for (size_t i = 0; i < np; i++) {
+                if (!active[i]) continue;
+                for (int ch = 0; ch < 3; ch++) mean[3 * i + ch] = ad_mean(mean[3 * i + ch], c[3 * i + ch], spp);
+                ad_welford(ad_luma(c[3 * i], c[3 * i + 1], c[3 * i + 2]), spp, &stat[2 * i], &stat[2 * i + 1]);
+            }
+        }
+        s.summary.samples += (int64_t)s.active * step.round;
+        s.passes += step.round;
+        if (step.round > 0) s.summary.rounds += 1;
+        if (!step.check_first && !ad_check_due(s.passes, p.min_spp, p.check_interval, max_spp)) continue;
+        for (size_t i = 0; i < np; i++) unconv[i] = (unsigned char)(active[i] && ad_unconverged(stat[2 * i], stat[2 * i + 1], s.passes, t2, p.floor));
+        for (int y = 0; y < height; y++)
+            for (int x = 0; x < width; x++) {
+                const size_t i = (size_t)y * width + x;
+                if (!active[i]) continue;
+                int any = 0;
+                for (int yy = y > 0 ? y - 1 : y; yy <= (y < height - 1 ? y + 1 : y); yy++)
+                    for (int xx = x > 0 ? x - 1 : x; xx <= (x < width - 1 ? x + 1 : x); xx++) any |= unconv[(size_t)yy * width + xx];
+                if (!any) {
+                    active[i] = 0;
+                    count[i] = s.passes;
+                    s.active -= 1;
+                }
+            }
+        s.last_check = s.passes;
+        if (s.summary.checks < CHUNKY_ADAPTIVE_MAX_CHECKS) s.summary.active[s.summary.checks] = s.active;
+        s.summary.checks += 1;
+    }
+    for (size_t i = 0; i < np; i++)
+        if (active[i]) count[i] = s.passes;
+    s.summary.passes = s.passes;
+    const size_t size = st->size;
+    memcpy(st, &s, size < sizeof s ? size : sizeof s);
+    st->size = size;
+    return CHUNKY_OK;
+}
+
 static int adaptive_tiles(const chunky_render* r) { return ((r->width + 15) / 16) * ((r->height + 15) / 16); }
 
 static int adaptive_ensure(chunky_render* r) {
@@ -1907,17 +2051,21 @@ static int adaptive_launch(chunky_render* r, const SceneView& S, const ShardView
     return CHUNKY_OK;
 }
 
-extern "C" int chunky_render_adaptive(chunky_render* r, const int32_t* seeds, int max_spp, const chunky_adaptive_params* params,
-                                      chunky_adaptive_summary* summary_out) {
-    if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
-    chunky_adaptive_params p;
-    if (int rc = adaptive_params("render_adaptive", params, max_spp, &p)) return rc;
-    if (!seeds) return fail(CHUNKY_E_INVALID, "render_adaptive: NULL seeds");
-    if (!r->parts.empty()) return fail(CHUNKY_E_STATE, "render_adaptive: a group's target (the active list lives on one device)");
-    LOCK_RENDER(r);
-    SceneView S;
-    if (int rc = adaptive_state("render_adaptive", r, &S)) return rc;
-    if (int rc = adaptive_ensure(r)) return rc;
+// the caller's hooks, as far as its struct holds them (as chunky_render_run_ex reads chunky_run_callbacks)
+static int adaptive_callbacks(const char* who, const chunky_adaptive_callbacks* callbacks, chunky_adaptive_callbacks* cb) {
+    memset(cb, 0, sizeof *cb);
+    if (!callbacks) return CHUNKY_OK;
+    const size_t have = callbacks->struct_size;
+    if (have < offsetof(chunky_adaptive_callbacks, round_done) || have % sizeof(void*) != 0)
+        return fail(CHUNKY_E_INVALID, "%s: callbacks->struct_size %zu (set it to sizeof(chunky_adaptive_callbacks))", who, have);
+    memcpy(cb, callbacks, have < sizeof *cb ? have : sizeof *cb);
+    return CHUNKY_OK;
+}
+
+// The loop of the specification (adaptive_spec.h ad_step; chunky_adaptive_host_resume is its host twin) on the state r->ad_state
+// towards max_spp.  The state is not resumable while it runs; it is again when the loop ends by itself or at a stop.
+static int adaptive_run(chunky_render* r, const char* who, const SceneView& S, const int32_t* seeds, int max_spp, const chunky_adaptive_callbacks& cb,
+                        chunky_adaptive_summary* summary_out) {
     hipStream_t st = r->ctx->stream;
     const int np = r->width * r->height, n_tiles = adaptive_tiles(r);
     unsigned char* active = (unsigned char*)r->ad_flags.p;
@@ -1925,50 +2073,189 @@ extern "C" int chunky_render_adaptive(chunky_render* r, const int32_t* seeds, in
     int* tile_counts = (int*)r->ad_tiles.p;
     int* tile_offsets = tile_counts + n_tiles;
     int* total = tile_offsets + n_tiles;
-    r->ad_valid = false;
-    HIP_TRY(hipMemsetAsync(r->fb, 0, (size_t)np * 3 * sizeof(float), st));
-    HIP_TRY(hipMemsetAsync(r->ad_stat.p, 0, r->ad_stat.bytes, st));
-    HIP_TRY(hipMemsetAsync(r->ad_count.p, 0, r->ad_count.bytes, st));
-    HIP_TRY(hipMemsetAsync(active, 1, (size_t)np, st));
+    chunky_adaptive_state& s = r->ad_state;
+    const chunky_adaptive_params& p = s.params;
     const float t2 = p.threshold * p.threshold;
-    chunky_adaptive_summary sum;
-    memset(&sum, 0, sizeof sum);
-    int done = 0, n_active = np;
-    while (done < max_spp && n_active > 0) {
-        const int left = max_spp - done;
-        const int round_n = done == 0 ? p.min_spp : (p.check_interval < left ? p.check_interval : left);
+    r->ad_valid = false;
+    r->ad_resumable = false;
+    bool stop = false;
+    while (!stop && s.passes < max_spp && s.active > 0) {
+        const ad_step_t step = ad_step(s.passes, s.last_check, p.min_spp, p.check_interval, max_spp);
         // every pixel still active: the ordinary block mapping; else the active pixels from the list of the last check (a temporary
         // view with world != 1 and tile != 0, the route of shard_gid through T.list)
         ShardView T = r->shard;
-        if (n_active < np) T = ShardView{0, 2, 1, n_active, (const int*)r->ad_list.p, n_active};
-        int cap = 0;
-        if (int rc = adaptive_stage(r, T, round_n, &cap)) return rc;
-        if (int rc = r->ad_clock.open(st)) return rc;
-        if (int rc = adaptive_launch(r, S, T, seeds + done, round_n, done, cap)) return rc;
-        sum.samples += (int64_t)n_active * round_n;
-        done += round_n;
-        sum.rounds += 1;
-        const bool check = ad_check_due(done, p.min_spp, p.check_interval, max_spp) != 0;
+        if (s.active < np) T = ShardView{0, 2, 1, s.active, (const int*)r->ad_list.p, s.active};
+        int launched = 0;
+        bool opened = false;
+        if (!step.check_first) {
+            int cap = 0;
+            if (int rc = adaptive_stage(r, T, step.round, &cap)) return rc;
+            while (launched < step.round) {  // a round longer than the launch cap is several launches, with a poll before each
+                if (cb.post_render && cb.post_render(cb.user)) {
+                    stop = true;
+                    break;
+                }
+                if (!opened) {
+                    if (int rc = r->ad_clock.open(st)) return rc;
+                    opened = true;
+                }
+                const int n = step.round - launched < cap ? step.round - launched : cap;
+                if (int rc = adaptive_launch(r, S, T, seeds + s.passes + launched, n, s.passes + launched, cap)) return rc;
+                launched += n;
+            }
+            s.summary.samples += (int64_t)s.active * launched;
+            s.passes += launched;
+            if (launched > 0) s.summary.rounds += 1;
+        } else {  // the check the run that stopped here did not make (it ended on its own max_spp): a bracket that counts as no round
+            if (int rc = r->ad_clock.open(st)) return rc;
+            opened = true;
+        }
+        const bool check = step.check_first || (launched == step.round && ad_check_due(s.passes, p.min_spp, p.check_interval, max_spp) != 0);
         if (check) {
-            HIP_TRY(launch_adaptive_check(r->width, r->height, (const float*)r->ad_stat.p, active, unconv, (int*)r->ad_count.p, done, t2, p.floor,
+            HIP_TRY(launch_adaptive_check(r->width, r->height, (const float*)r->ad_stat.p, active, unconv, (int*)r->ad_count.p, s.passes, t2, p.floor,
                                           tile_counts, tile_offsets, (int*)r->ad_list.p, total, st));
             HIP_TRY(hipMemcpyAsync(r->ad_total_host, total, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         }
-        if (int rc = r->ad_clock.close(st)) return rc;
-        HIP_TRY(hipStreamSynchronize(st));  // once per round: the host loop needs the total
-        if (int rc = r->ad_clock.collect()) return rc;  // (finished: its events go back to the pool for the next round)
-        if (check) {
-            n_active = *r->ad_total_host;
-            if (n_active < 0 || n_active > np) return fail(CHUNKY_E_HIP, "render_adaptive: the compaction reported %d active pixels of %d", n_active, np);
-            if (sum.checks < CHUNKY_ADAPTIVE_MAX_CHECKS) sum.active[sum.checks] = n_active;
-            sum.checks += 1;
+        if (opened) {
+            if (int rc = r->ad_clock.close(st, step.check_first ? 0 : 1)) return rc;
+            HIP_TRY(hipStreamSynchronize(st));  // once per round: the host loop needs the total
+            if (int rc = r->ad_clock.collect()) return rc;  // (finished: its events go back to the pool for the next round)
         }
+        if (check) {
+            const int n_active = *r->ad_total_host;
+            if (n_active < 0 || n_active > s.active) return fail(CHUNKY_E_HIP, "%s: the compaction reported %d active pixels of %d", who, n_active, s.active);
+            s.active = n_active;
+            s.last_check = s.passes;
+            if (s.summary.checks < CHUNKY_ADAPTIVE_MAX_CHECKS) s.summary.active[s.summary.checks] = n_active;
+            s.summary.checks += 1;
+        }
+        if (!stop && !step.check_first && cb.round_done) cb.round_done(cb.user, s.passes, s.active);
+        if (check && !stop && cb.post_render && cb.post_render(cb.user)) stop = true;
     }
-    HIP_TRY(launch_adaptive_finish(np, active, (int*)r->ad_count.p, done, st));
+    HIP_TRY(launch_adaptive_finish(np, active, (int*)r->ad_count.p, s.passes, st));
     HIP_TRY(hipStreamSynchronize(st));
-    sum.passes = done;
+    s.summary.passes = s.passes;
     r->ad_valid = true;
-    if (summary_out) *summary_out = sum;
+    r->ad_resumable = true;
+    if (summary_out) *summary_out = s.summary;
+    if (stop) return fail(CHUNKY_E_ABORTED, "%s: stopped by post_render after %d passes", who, s.passes);
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_adaptive_ex(chunky_render* r, const int32_t* seeds, int max_spp, const chunky_adaptive_params* params,
+                                         const chunky_adaptive_callbacks* callbacks, chunky_adaptive_summary* summary_out) {
+    if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
+    chunky_adaptive_params p;
+    if (int rc = adaptive_params("render_adaptive", params, max_spp, &p)) return rc;
+    chunky_adaptive_callbacks cb;
+    if (int rc = adaptive_callbacks("render_adaptive_ex", callbacks, &cb)) return rc;
+    if (!seeds) return fail(CHUNKY_E_INVALID, "render_adaptive: NULL seeds");
+    if (!r->parts.empty()) return fail(CHUNKY_E_STATE, "render_adaptive: a group's target (the active list lives on one device)");
+    LOCK_RENDER(r);
+    SceneView S;
+    if (int rc = adaptive_state("render_adaptive", r, &S)) return rc;
+    if (int rc = adaptive_ensure(r)) return rc;
+    hipStream_t st = r->ctx->stream;
+    const int np = r->width * r->height;
+    r->ad_valid = false;
+    r->ad_resumable = false;
+    HIP_TRY(hipMemsetAsync(r->fb, 0, (size_t)np * 3 * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(r->ad_stat.p, 0, r->ad_stat.bytes, st));
+    HIP_TRY(hipMemsetAsync(r->ad_count.p, 0, r->ad_count.bytes, st));
+    HIP_TRY(hipMemsetAsync(r->ad_flags.p, 1, (size_t)np, st));
+    adaptive_empty_state(r->width, r->height, p, &r->ad_state);
+    return adaptive_run(r, "render_adaptive", S, seeds, max_spp, cb, summary_out);
+}
+
+extern "C" int chunky_render_adaptive(chunky_render* r, const int32_t* seeds, int max_spp, const chunky_adaptive_params* params,
+                                      chunky_adaptive_summary* summary_out) {
+    return chunky_render_adaptive_ex(r, seeds, max_spp, params, nullptr, summary_out);
+}
+
+static bool same_adaptive_params(const chunky_adaptive_params& a, const chunky_adaptive_params& b) {
+    return a.threshold == b.threshold && a.floor == b.floor && a.min_spp == b.min_spp && a.check_interval == b.check_interval;
+}
+
+extern "C" int chunky_render_adaptive_resume(chunky_render* r, const int32_t* seeds, int max_spp, const chunky_adaptive_params* params,
+                                             const chunky_adaptive_callbacks* callbacks, chunky_adaptive_summary* summary_out) {
+    if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
+    chunky_adaptive_params p;
+    if (int rc = adaptive_params("render_adaptive_resume", params, INT32_MAX, &p)) return rc;  // (a state stopped before min_spp goes on too)
+    chunky_adaptive_callbacks cb;
+    if (int rc = adaptive_callbacks("render_adaptive_resume", callbacks, &cb)) return rc;
+    if (!r->parts.empty()) return fail(CHUNKY_E_STATE, "render_adaptive_resume: a group's target (the active list lives on one device)");
+    LOCK_RENDER(r);
+    SceneView S;
+    if (int rc = adaptive_state("render_adaptive_resume", r, &S)) return rc;
+    if (!r->ad_resumable)
+        return fail(CHUNKY_E_STATE, "render_adaptive_resume: the target holds no adaptive state to continue (none was left, or the framebuffer, the camera, "
+                                    "the options, the shard or the buffer changed since)");
+    const chunky_adaptive_state& s = r->ad_state;
+    if (!same_adaptive_params(p, s.params))
+        return fail(CHUNKY_E_STATE, "render_adaptive_resume: the parameters differ from those of the state (threshold %g, floor %g, min_spp %d, check_interval %d)",
+                    (double)s.params.threshold, (double)s.params.floor, s.params.min_spp, s.params.check_interval);
+    if (max_spp < s.passes) return fail(CHUNKY_E_INVALID, "render_adaptive_resume: max_spp %d is below the %d passes the state holds", max_spp, s.passes);
+    if (max_spp == s.passes || s.active == 0) {  // nothing to render
+        if (summary_out) *summary_out = s.summary;
+        return CHUNKY_OK;
+    }
+    if (!seeds) return fail(CHUNKY_E_INVALID, "render_adaptive_resume: NULL seeds");
+    if (int rc = adaptive_ensure(r)) return rc;
+    return adaptive_run(r, "render_adaptive_resume", S, seeds, max_spp, cb, summary_out);
+}
+
+extern "C" int chunky_render_adaptive_state(chunky_render* r, chunky_adaptive_state* out, uint8_t* active_out, int64_t n) {
+    if (r && !r->parts.empty()) return fail(CHUNKY_E_STATE, "render_adaptive_state: a group's target has no adaptive run");
+    LOCK_RENDER(r);
+    if (!r->ad_resumable) return fail(CHUNKY_E_STATE, "render_adaptive_state: the target holds no adaptive state to continue");
+    if (!out) return fail(CHUNKY_E_INVALID, "render_adaptive_state: NULL output");
+    if (out->size < kAdaptiveStateFirst)
+        return fail(CHUNKY_E_INVALID, "render_adaptive_state: out->size %zu is smaller than the struct (%zu): set it to sizeof(chunky_adaptive_state)", out->size, kAdaptiveStateFirst);
+    if (active_out) {
+        if (n != (int64_t)r->width * r->height) return fail(CHUNKY_E_INVALID, "render_adaptive_state: the map has %lld bytes, got %lld", (long long)r->width * r->height, (long long)n);
+        HIP_TRY(hipMemcpyAsync(active_out, r->ad_flags.p, (size_t)n, hipMemcpyDeviceToHost, r->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    }
+    const size_t size = out->size;
+    memcpy(out, &r->ad_state, size < sizeof *out ? size : sizeof *out);
+    out->size = size;
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_adaptive_restore(chunky_render* r, const chunky_adaptive_state* st, const float* mean, const int32_t* count,
+                                              const float* stat, const uint8_t* active) {
+    if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
+    if (!st || !mean || !count || !stat || !active) return fail(CHUNKY_E_INVALID, "render_adaptive_restore: NULL argument");
+    if (!r->parts.empty()) return fail(CHUNKY_E_STATE, "render_adaptive_restore: a group's target (the active list lives on one device)");
+    LOCK_RENDER(r);
+    SceneView S;
+    if (int rc = adaptive_state("render_adaptive_restore", r, &S)) return rc;
+    chunky_adaptive_state s;
+    if (int rc = adaptive_state_valid("render_adaptive_restore", st, count, active, &s)) return rc;
+    if (s.width != r->width || s.height != r->height)
+        return fail(CHUNKY_E_INVALID, "render_adaptive_restore: a state of %d x %d on a target of %d x %d", s.width, s.height, r->width, r->height);
+    if (int rc = adaptive_ensure(r)) return rc;
+    hipStream_t stream = r->ctx->stream;
+    const size_t np = (size_t)r->width * r->height;
+    const int n_tiles = adaptive_tiles(r);
+    int* tile_counts = (int*)r->ad_tiles.p;
+    int* tile_offsets = tile_counts + n_tiles;
+    int* total = tile_offsets + n_tiles;
+    r->ad_valid = false;
+    r->ad_resumable = false;
+    HIP_TRY(hipMemcpyAsync(r->fb, mean, np * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(r->ad_count.p, count, np * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(r->ad_stat.p, stat, np * 2 * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(r->ad_flags.p, active, np, hipMemcpyHostToDevice, stream));
+    // the list of the active pixels, in the order the run that left this map held it: counted, scanned and scattered on the device
+    HIP_TRY(launch_adaptive_rebuild(r->width, r->height, (unsigned char*)r->ad_flags.p, tile_counts, tile_offsets, (int*)r->ad_list.p, total, stream));
+    HIP_TRY(hipMemcpyAsync(r->ad_total_host, total, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));  // the caller may reuse its arrays on return (not timed: chunky_render_adaptive_kernel_time is about rounds)
+    if (*r->ad_total_host != s.active)
+        return fail(CHUNKY_E_HIP, "render_adaptive_restore: the device counted %d active pixels, the state holds %d", *r->ad_total_host, s.active);
+    r->ad_state = s;
+    r->ad_valid = true;
+    r->ad_resumable = true;
     return CHUNKY_OK;
 }
 
@@ -2008,6 +2295,7 @@ extern "C" int chunky_selftest_render_list(chunky_render* r, const int32_t* pixe
     if (n == 0 || n_pixels == 0) return CHUNKY_OK;
     hipStream_t st = r->ctx->stream;
     r->ad_valid = false;  // the statistic and the list are overwritten
+    r->ad_resumable = false;
     HIP_TRY(hipMemsetAsync(r->ad_stat.p, 0, r->ad_stat.bytes, st));
     HIP_TRY(hipMemcpyAsync(r->ad_list.p, pixels, (size_t)n_pixels * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));  // the caller may reuse its array on return

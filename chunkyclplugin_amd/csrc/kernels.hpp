@@ -135,6 +135,10 @@ hipError_t launch_fold_stats(const float* staging, float* res, float* stat, cons
 // ints; tile_counts / tile_offsets: one int per 16 x 16 tile; all on the device
 hipError_t launch_adaptive_check(int width, int height, const float* stat, unsigned char* active, unsigned char* unconv, int* count, int n,
                                  float t2, float floor_, int* tile_counts, int* tile_offsets, int* list, int* total, hipStream_t stream);
+// the list and *total of an activity map that is already final (a restored state): the tiles' active slots counted
+// (adaptive_count_kernel), then the scan and the scatter of launch_adaptive_check — the same list, entry for entry; the maps are only read
+hipError_t launch_adaptive_rebuild(int width, int height, unsigned char* active, int* tile_counts, int* tile_offsets, int* list, int* total,
+                                   hipStream_t stream);
 // pixels still active record n
 hipError_t launch_adaptive_finish(int n_pixels, const unsigned char* active, int* count, int n, hipStream_t stream);
 // thresholds: 256 floats on the device (capi.hip gamma_thresholds) or null = evaluate pow per channel

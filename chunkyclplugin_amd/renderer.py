@@ -380,9 +380,59 @@ class HipPathTracingRenderer:
         summ = native.AdaptiveSummary()
         check(native.lib().chunky_render_adaptive(self._h, ptr(s), s.size, C.byref(p), C.byref(summ)))
         image = self.read().reshape(self.height, self.width, 3)
-        summary = {"rounds": summ.rounds, "checks": summ.checks, "passes": summ.passes, "samples": summ.samples,
-                   "active": [int(a) for a in summ.active[:min(summ.checks, native.ADAPTIVE_MAX_CHECKS)]]}
+        summary = native.adaptive_summary_dict(summ)
         return image, self.adaptive_counts(), self.adaptive_noise(), summary
+
+    def _adaptive_callbacks(self, post_render, round_done):
+        """(struct or None, the ctypes thunks to keep alive during the call)"""
+        if post_render is None and round_done is None:
+            return None, ()
+        cb = native.AdaptiveCallbacks()
+        cb.struct_size = C.sizeof(native.AdaptiveCallbacks)
+        keep = []
+        if post_render is not None:
+            keep.append(native.POST_RENDER_FN(lambda _u: 1 if post_render() else 0))
+            cb.post_render = keep[-1]
+        if round_done is not None:
+            keep.append(native.ROUND_DONE_FN(lambda _u, passes, active: round_done(int(passes), int(active))))
+            cb.round_done = keep[-1]
+        return cb, keep
+
+    def _adaptive_call(self, fn, seeds, params, post_render, round_done):
+        s = np.ascontiguousarray(seeds, np.int32)
+        p = params if params is not None else native.adaptive_params()
+        summ = native.AdaptiveSummary()
+        cb, keep = self._adaptive_callbacks(post_render, round_done)
+        rc = fn(self._h, ptr(s), s.size, C.byref(p), C.byref(cb) if cb is not None else None, C.byref(summ))
+        del keep
+        if rc not in (0, native.E_ABORTED):
+            check(rc)
+        return rc == 0, native.adaptive_summary_dict(summ)
+
+    def render_adaptive_ex(self, seeds, params=None, post_render=None, round_done=None):
+        """chunky_render_adaptive_ex: render_adaptive from pass 0 with the hooks.  post_render() -> truthy stops the run at the next
+        launch boundary; round_done(passes, active) is told of every round.  Neither may call into this instance's targets.  Returns
+        (finished, summary): finished is False when post_render stopped the run — the target then holds a state that resume_adaptive
+        continues, and read / adaptive_counts / adaptive_noise show the passes done."""
+        return self._adaptive_call(native.lib().chunky_render_adaptive_ex, seeds, params, post_render, round_done)
+
+    def resume_adaptive(self, seeds, params=None, post_render=None, round_done=None):
+        """chunky_render_adaptive_resume: continues the target's adaptive state to len(seeds) passes.  `seeds` is the whole stream
+        from pass 0 (the passes already done are skipped), `params` the parameters of the run being continued.  Returns (finished,
+        summary), the summary counted from pass 0."""
+        return self._adaptive_call(native.lib().chunky_render_adaptive_resume, seeds, params, post_render, round_done)
+
+    def adaptive_state(self) -> "native.AdaptiveRun":
+        """The target's whole adaptive state on the host (chunky_render_adaptive_state plus the readers): what restore_adaptive takes."""
+        st = native.AdaptiveState()
+        st.size = C.sizeof(native.AdaptiveState)
+        active = np.empty((self.height, self.width), np.uint8)
+        check(native.lib().chunky_render_adaptive_state(self._h, C.byref(st), ptr(active), active.size))
+        return native.AdaptiveRun(st, self.read(), self.adaptive_counts(), self.adaptive_noise(), active)
+
+    def restore_adaptive(self, run: "native.AdaptiveRun") -> None:
+        """chunky_render_adaptive_restore: takes a state (of this target's size) onto the target; resume_adaptive continues it."""
+        check(native.lib().chunky_render_adaptive_restore(self._h, C.byref(run.state), ptr(run.mean), ptr(run.count), ptr(run.stat), ptr(run.active)))
 
     def adaptive_counts(self) -> np.ndarray:
         out = np.empty((self.height, self.width), np.int32)

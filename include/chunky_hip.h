@@ -479,13 +479,101 @@ int chunky_render_adaptive(chunky_render* r, const int32_t* seeds, int max_spp, 
 int chunky_render_adaptive_counts(chunky_render* r, int32_t* out, int64_t n);
 int chunky_render_adaptive_noise(chunky_render* r, float* out, int64_t n_floats);
 /* Device time of the adaptive runs since the last call — their render launches, folds, checks and compactions — and the number of
- * rounds; apart from chunky_render_kernel_time, which does not see them. */
+ * rounds; apart from chunky_render_kernel_time, which does not see them.  A check that chunky_render_adaptive_resume makes before its
+ * first round (the one the earlier run left out) is in total_ms and counts as no round; chunky_render_adaptive_restore is not timed. */
 int chunky_render_adaptive_kernel_time(chunky_render* r, float* total_ms, int* rounds);
 /* ---- self test of the list route: renders n passes (seeds[k], bufferSpp k) on the listed pixels only, through the launch the later
  * rounds of chunky_render_adaptive use (the staged-sample kernel over a device-resident list of pixel indices), folding into the
  * framebuffer as it is.  pixels: n_pixels distinct indices y * width + x in any order.  Blocking.  Same state errors as
  * chunky_render_adaptive. */
 int chunky_selftest_render_list(chunky_render* r, const int32_t* pixels, int n_pixels, const int32_t* seeds, int n);
+
+/* ---- adaptive sampling that stops and continues: pause, a raised SPP target, a render dump reloaded after a restart ----
+ * A run is described by its state after `passes` passes; every active pixel has seen exactly those passes.  Beside this header the
+ * state has four arrays: mean (3 * W * H floats, the image), count (W * H ints), stat (2 * W * H floats, (m, M2)) and active (W * H
+ * bytes, each 0 or 1).  The map cannot be derived from the rest: a pixel that left at a check at `passes` and a pixel that is still
+ * active both have count == passes.
+ *
+ * The check points are the grid min_spp + j * check_interval (j >= 0).  Continuing a state to max_spp > passes (adaptive_spec.h
+ * ad_step): first, when a check at `passes` is due under the new max_spp (passes on the grid, passes < max_spp) and last_check !=
+ * passes, that check is run — the earlier run ended there on its own max_spp, where none is made.  Then rounds up to the next grid
+ * point or to max_spp, whichever comes first (a state off the grid — stopped inside a round, or ended on an off-grid max_spp — takes a
+ * short round first), each followed by its check when one is due.  chunky_render_adaptive is this loop from the empty state.
+ *
+ * Two properties, both bit for bit in image, counts and (m, M2):
+ *   P1  stop = shorter run: for d >= min_spp the state after d passes is the result of chunky_adaptive_host(samples[0 .. d), n = d),
+ *       whether or not the check at d has been run (who leaves at d and who stays both record d).
+ *   P2  resume = fresh: the start state continued over any split 0 < d1 < ... < B of the passes equals chunky_adaptive_host(samples, B);
+ *       summary.checks, .active[], .samples and .passes equal the single run's (.rounds may differ: a split can cut a round in two). */
+typedef struct chunky_adaptive_state {
+    size_t size;          /* sizeof(chunky_adaptive_state) as the caller was compiled; members may be appended */
+    int32_t width, height;
+    int32_t passes;       /* passes folded into every still-active pixel */
+    int32_t last_check;   /* pass count at which the last check ran, 0 = none yet */
+    int32_t active;       /* number of active pixels */
+    int32_t reserved;
+    chunky_adaptive_params params;
+    chunky_adaptive_summary summary; /* cumulative from pass 0 */
+} chunky_adaptive_state;
+
+/* The host side of it: no context and no device.  _begin writes the start state (passes 0, every pixel active, everything else 0;
+ * params as chunky_adaptive_host takes them, without the n >= min_spp rule) into st and the four arrays.  _resume continues st and the
+ * arrays in place with `samples`, n images [n][height][width][3]: the samples of passes st->passes .. st->passes + n - 1; the target is
+ * max_spp = st->passes + n.  n may be smaller than min_spp (nothing is checked before min_spp; every count is then the pass count); n
+ * == 0, or a state with no active pixel, changes nothing.  _resume validates the state with chunky_adaptive_state_check first. */
+int chunky_adaptive_host_begin(int width, int height, const chunky_adaptive_params* params, chunky_adaptive_state* st, int32_t* count,
+                               float* mean, float* stat, uint8_t* active);
+int chunky_adaptive_host_resume(chunky_adaptive_state* st, const float* samples, int n, int32_t* count, float* mean, float* stat,
+                                uint8_t* active);
+/* CHUNKY_OK for a state a run can have left, CHUNKY_E_INVALID (with the rule in the message) otherwise: size at least this struct's;
+ * width, height > 0 and small enough for chunky_adaptive_host; params valid by its rules; passes >= 0; last_check is 0 when no grid
+ * point is <= passes, else the largest grid point g <= passes or — only when g == passes — the grid point before it (0 if none);
+ * active[p] is 0 or 1; an active pixel has count == passes; an inactive pixel's count is on the grid and <= last_check; st->active is
+ * the number of ones in the map; summary.passes == passes; summary.samples == the sum of count.  mean and stat are not inspected
+ * (non-finite values are legal there: see the convergence test above). */
+int chunky_adaptive_state_check(const chunky_adaptive_state* st, const int32_t* count, const uint8_t* active);
+
+/* Hooks of an adaptive run (any pointer may be NULL; struct_size as chunky_run_callbacks::struct_size):
+ *   post_render  polled before every render launch (a round longer than the launch cap is several launches) and after every round's
+ *                check; non-zero ends the call with CHUNKY_E_ABORTED.  The target is then at a launch boundary: the pixels still
+ *                active have recorded the passes done, image, counts and noise are readable and equal P1 for those passes, and the
+ *                state continues with chunky_render_adaptive_resume.
+ *   round_done   after every round (and its check): the pass count and the number of active pixels.
+ * Both run with the context locked: they must not call into the library on that context (another thread that does waits for the run). */
+typedef struct chunky_adaptive_callbacks {
+    size_t struct_size;
+    int (*post_render)(void* user);
+    void (*round_done)(void* user, int32_t passes, int32_t active);
+    void* user;
+} chunky_adaptive_callbacks;
+
+/* chunky_render_adaptive with the hooks: from pass 0, resetting the framebuffer and the adaptive state.  chunky_render_adaptive is
+ * this call with callbacks == NULL.  summary_out receives the summary so far on CHUNKY_OK and on CHUNKY_E_ABORTED. */
+int chunky_render_adaptive_ex(chunky_render* r, const int32_t* seeds, int max_spp, const chunky_adaptive_params* params,
+                              const chunky_adaptive_callbacks* callbacks, chunky_adaptive_summary* summary_out);
+/* Continues from the state the target holds — left by chunky_render_adaptive, _ex or _resume (finished or aborted) or by _restore —
+ * to max_spp passes, pass k with seeds[k]: `seeds` is the SAME stream from pass 0 (max_spp values; a contract, not checked), of
+ * which seeds[passes ..) are used.  The result obeys P2; the summary is cumulative from pass 0.  params must equal the state's
+ * (threshold, floor, min_spp, check_interval), else CHUNKY_E_STATE: continuing under other parameters is not supported (an inactive
+ * pixel never becomes active again).  max_spp == passes, or no active pixel: CHUNKY_OK, nothing rendered.  max_spp < passes:
+ * CHUNKY_E_INVALID.  CHUNKY_E_STATE when the target holds no state to continue: none was ever left, or a call that writes the
+ * framebuffer or changes what a pass renders came since (one that was refused with an error before it changed anything ends nothing) — chunky_render_passes, chunky_render_run / _run_ex, chunky_render_reset,
+ * chunky_selftest_render_list, chunky_render_set_device_buffer, _set_camera, _set_option, _set_shard.  The AOV and denoise calls do
+ * not end it (chunky_render_adaptive_counts / _noise stay readable through all of these, as before).  Scene uploads between the two
+ * calls are the caller's contract, as they are between two chunky_render_passes calls: the passes to come render the scene as it is
+ * then.  Other state errors as chunky_render_adaptive. */
+int chunky_render_adaptive_resume(chunky_render* r, const int32_t* seeds, int max_spp, const chunky_adaptive_params* params,
+                                  const chunky_adaptive_callbacks* callbacks, chunky_adaptive_summary* summary_out);
+/* The header of the target's state and its activity map (n must be width * height; active_out may be NULL); image, counts and noise
+ * come from chunky_render_read, chunky_render_adaptive_counts and _noise.  CHUNKY_E_STATE as chunky_render_adaptive_resume. */
+int chunky_render_adaptive_state(chunky_render* r, chunky_adaptive_state* out, uint8_t* active_out, int64_t n);
+/* Takes a state onto a target of the same width and height that chunky_render_adaptive accepts (no group, no shard of world > 1, a
+ * scene and options render_pool takes): validates it with chunky_adaptive_state_check, uploads mean into the framebuffer (the
+ * caller-owned device buffer when one is set), count, stat and the map, and rebuilds the active list on the device in the order the
+ * original run held it.  The target then continues with chunky_render_adaptive_resume.  CHUNKY_E_INVALID (a NULL array, a size
+ * mismatch, an invalid state) and CHUNKY_E_STATE leave the target as it was. */
+int chunky_render_adaptive_restore(chunky_render* r, const chunky_adaptive_state* st, const float* mean, const int32_t* count,
+                                   const float* stat, const uint8_t* active);
 
 /* ---- host pass loop (replaces OpenClPathTracingRenderer.render, J/opencl/OpenClPathTracingRenderer.java:54-191):
  * seeds from java.util.Random(0).nextInt(), bufferSpp restarting at 0 after each read-back, merge
