@@ -1,5 +1,5 @@
 /* adaptive_spec.h — the arithmetic of adaptive sampling (include/chunky_hip.h, "adaptive sampling"), compiled
- * by the kernels (adaptive.hip) and by the host (capi.hip chunky_adaptive_host) from this one text.
+ * by the kernels (adaptive.hip) and by the host (adaptive_host.cpp chunky_adaptive_host) from this one text.
  *
  * Every operation below is one exactly rounded float operation (+, -, *, /, a conversion of a small integer, a comparison); the
  * translation units that include this header are compiled with -ffp-contract=off, so no multiply-add pair is fused, and the

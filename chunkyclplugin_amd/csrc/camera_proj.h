@@ -1,6 +1,6 @@
 /* camera_proj.h — the projected cameras (CHUNKY_PROJ_PARALLEL .. CHUNKY_PROJ_STEREOGRAPHIC, include/chunky_hip.h, DESIGN.md
  * section 11): the primary ray of one sample, computed from the pass seed.  One definition for both sides: the kernels call it
- * through primary_ray (rt_device.hpp) and chunky_camera_rays (capi.hip) runs it on the host to build the equivalent table of
+ * through primary_ray (rt_device.hpp) and chunky_camera_rays (capi_host.cpp) runs it on the host to build the equivalent table of
  * projector type -1.  Float arithmetic with the rt_math.h functions only, in the order written, built with -ffp-contract=off, so
  * the two sides agree bit for bit.
  *

@@ -1,0 +1,87 @@
+// capi_aov.hip — albedo and normal images for denoisers (aov.hip).
+#include "capi_internal.hpp"
+
+// On a group's render target member 0 renders the caller's whole share (as chunky_render_preview does): the images are then the
+// one-context images without an exchange, and every AOV entry point below forwards to member 0.
+static int aov_ensure(chunky_render* r) {
+    if (r->aov.p) return CHUNKY_OK;
+    const size_t bytes = aov_image_bytes(r) * 2 + 256;  // albedo, normal, the claim counter
+    HIP_TRY(r->aov.alloc(bytes));
+    HIP_TRY(hipMemsetAsync(r->aov.p, 0, bytes, r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+// n passes over the pixel slots of shard T (a single-device target: its own share; member 0 of a group: the caller's share)
+static int aov_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n, int first_buffer_spp) {
+    LOCK_RENDER(r);
+    if (!r->have_camera) return fail(CHUNKY_E_STATE, "aov_passes before set_camera");
+    if (int rc = aov_ensure(r)) return rc;
+    r->aov_last_launches = 0;
+    if (n == 0 || T.n_local <= 0) return CHUNKY_OK;
+    SceneView S;
+    if (int rc = scene_view(r->scene, &S)) return rc;
+    S.bvh_cull = r->opts.bvh_cull;
+    if (r->aov_clock.full())
+        if (int rc = r->aov_clock.collect()) return rc;
+    float* albedo = (float*)r->aov.p;
+    float* normal = (float*)((char*)r->aov.p + aov_image_bytes(r));
+    int* counter = (int*)((char*)r->aov.p + 2 * aov_image_bytes(r));
+    for (int done = 0; done < n;) {  // launches of at most kMaxPassesPerLaunch: each continues the running mean where the last left it
+        PassSeeds ps;
+        ps.n = (n - done) < kMaxPassesPerLaunch ? (n - done) : kMaxPassesPerLaunch;
+        ps.first_spp = first_buffer_spp + done;
+        memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
+        if (int rc = r->aov_clock.open(r->ctx->stream)) return rc;
+        HIP_TRY(launch_aov(r->kernel_variant, S, r->cam, r->opts, T, ps, albedo, normal, counter, r->ctx->stream, &r->aov_choice));
+        if (int rc = r->aov_clock.close(r->ctx->stream)) return rc;
+        r->aov_last_launches += 1;
+        done += ps.n;
+    }
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_aov_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp) {
+    if (n < 0 || (n > 0 && !seeds) || first_buffer_spp < 0) return fail(CHUNKY_E_INVALID, "aov_passes: bad arguments");
+    if (r && !r->parts.empty()) {
+        std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
+        ShardView t;  // the caller's share of the image, all of it on member 0
+        if (!make_shard_view(r->width, r->height, r->outer.rank, r->outer.world, r->outer.tile, &t))
+            return fail(CHUNKY_E_INVALID, "aov_passes: the group's share needs more than 2^31 pixel slots");
+        return aov_passes(r->parts[0], t, seeds, n, first_buffer_spp);
+    }
+    if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
+    std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
+    return aov_passes(r, r->shard, seeds, n, first_buffer_spp);
+}
+
+extern "C" int chunky_render_aov_read(chunky_render* r, int which, float* out, int64_t n) {
+    if (r && !r->parts.empty()) return chunky_render_aov_read(r->parts[0], which, out, n);
+    LOCK_RENDER(r);
+    if (which != CHUNKY_AOV_ALBEDO && which != CHUNKY_AOV_NORMAL) return fail(CHUNKY_E_INVALID, "aov_read: unknown image %d", which);
+    const char* src = r->aov.p ? (const char*)r->aov.p + (which == CHUNKY_AOV_NORMAL ? aov_image_bytes(r) : 0) : nullptr;  // null before any AOV pass
+    return read_floats("aov_read", r, src, out, n, (int64_t)r->width * r->height * 3);
+}
+
+extern "C" int chunky_render_aov_reset(chunky_render* r) {
+    if (r && !r->parts.empty()) return chunky_render_aov_reset(r->parts[0]);
+    LOCK_RENDER(r);
+    if (r->aov.p) HIP_TRY(hipMemsetAsync(r->aov.p, 0, 2 * aov_image_bytes(r), r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_aov_kernel_time(chunky_render* r, float* total_ms, int* launches) {
+    if (r && !r->parts.empty()) return chunky_render_aov_kernel_time(r->parts[0], total_ms, launches);
+    LOCK_RENDER(r);
+    return r->aov_clock.take(total_ms, launches);
+}
+
+extern "C" int chunky_render_aov_kernel_info(chunky_render* r, int32_t out4[4]) {
+    if (r && !r->parts.empty()) return chunky_render_aov_kernel_info(r->parts[0], out4);
+    LOCK_RENDER(r);
+    if (!out4) return fail(CHUNKY_E_INVALID, "aov_kernel_info: NULL output");
+    out4[0] = r->aov_choice.tree;
+    out4[1] = r->aov_choice.bvh;
+    out4[2] = r->aov_choice.blocks;
+    out4[3] = r->aov_last_launches;
+    return CHUNKY_OK;
+}

@@ -1,0 +1,525 @@
+// capi_render.hip — the render target: camera, options, shard, buffer, the pass launcher and its clock, read-back, timing, preview, records.
+#include "capi_internal.hpp"
+
+static_assert(sizeof(chunky_hit_record) == sizeof(HitRecord), "record layouts must agree");
+static_assert(CHUNKY_MAX_TRACES == kMaxTraces, "trace capacity must agree");
+
+// every member takes its share of the caller's own share (shard_map.hpp member_shard).  All or nothing: a group whose world * members
+// does not fit an int, or one member of which would need more slots than an int holds, is refused before any member changes
+static int group_apply_shards(chunky_render* r, const ShardView& outer) {
+    const int n = (int)r->parts.size();
+    std::vector<ShardView> share((size_t)n);
+    for (int i = 0; i < n; i++) {
+        ShardView& m = share[(size_t)i];
+        if (!member_shard(outer, i, n, &m))
+            return fail(CHUNKY_E_INVALID, "set_shard: world %d x %d group members does not fit an int", outer.world, n);
+        ShardView stored;
+        if (!make_shard_view(r->width, r->height, m.rank, m.world, m.tile, &stored))
+            return fail(CHUNKY_E_INVALID, "set_shard: rank %d of %d in 16 x 16 blocks of a %d x %d image needs more than 2^31 pixel slots", m.rank, m.world, r->width, r->height);
+    }
+    for (int i = 0; i < n; i++)
+        if (int rc = chunky_render_set_shard(r->parts[(size_t)i], share[(size_t)i].rank, share[(size_t)i].world, share[(size_t)i].tile)) return rc;
+    r->outer = outer;
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_create(chunky_ctx* ctx, chunky_scene* scene, int width, int height, chunky_render** out) {
+    if (!ctx || !scene || !out) return fail(CHUNKY_E_INVALID, "chunky_render_create: NULL argument");
+    if (scene->ctx != ctx) return fail(CHUNKY_E_INVALID, "scene belongs to another context");
+    if (width <= 0 || height <= 0 || (int64_t)width * height > (1 << 30))
+        return fail(CHUNKY_E_INVALID, "bad image size %dx%d", width, height);
+    if (!ctx->members.empty()) {
+        std::lock_guard<std::recursive_mutex> g(ctx->mu);
+        if (scene->replicas.size() != ctx->members.size()) return fail(CHUNKY_E_STATE, "chunky_render_create: the scene has been destroyed");
+        std::unique_ptr<chunky_render> r(new chunky_render);
+        r->ctx = ctx;
+        r->scene = scene;
+        r->width = width;
+        r->height = height;
+        int rc = CHUNKY_OK;
+        for (size_t i = 0; i < ctx->members.size() && rc == CHUNKY_OK; i++) {
+            chunky_render* part = nullptr;
+            rc = chunky_render_create(ctx->members[i], scene->replicas[i], width, height, &part);
+            if (rc == CHUNKY_OK) r->parts.push_back(part);
+        }
+        if (rc == CHUNKY_OK) rc = group_apply_shards(r.get(), r->outer);
+        if (rc != CHUNKY_OK) {
+            for (chunky_render* part : r->parts) (void)chunky_render_destroy(part);
+            return rc;
+        }
+        r->gather_send.resize(ctx->members.size());
+        r->gather_recv.resize(ctx->members.size());
+        scene->refs++;
+        *out = r.release();
+        return CHUNKY_OK;
+    }
+    std::lock_guard<std::recursive_mutex> g(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::unique_ptr<chunky_render> r(new chunky_render);
+    r->ctx = ctx;
+    r->scene = scene;
+    r->width = width;
+    r->height = height;
+    size_t bytes = (size_t)width * height * 3 * sizeof(float);
+    HIP_TRY(r->own_fb.alloc(bytes));
+    r->fb = (float*)r->own_fb.p;
+    HIP_TRY(hipMemsetAsync(r->fb, 0, bytes, ctx->stream));
+    // [0] the sample / pixel queue, [2..49] the phase profile, [64..127] render_pool's range counters (render_pool.hip xcd_claim)
+    HIP_TRY(r->work_counter.alloc(512));
+    HIP_TRY(hipMemsetAsync(r->work_counter.p, 0, 512, ctx->stream));
+    r->shard = ShardView{0, 1, 256, width * height};
+    scene->refs++;
+    *out = r.release();
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_destroy(chunky_render* r) {
+    if (r && !r->parts.empty()) {
+        int rc = each_part(r, [&](chunky_render* m_) { return chunky_render_destroy(m_); });
+        {
+            std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
+            for (size_t i = 0; i < r->gather_send.size(); i++) {  // each buffer is freed on the device it lives on
+                (void)hipSetDevice(r->ctx->members[i]->device);
+                r->gather_send[i].release();
+                (void)hipSetDevice(r->ctx->members[0]->device);
+                r->gather_recv[i].release();
+            }
+            scene_unref(r->scene);
+        }
+        delete r;
+        return rc;
+    }
+    LOCK_RENDER(r);
+    (void)hipStreamSynchronize(r->ctx->stream);
+    scene_unref(r->scene);
+    delete r;
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_set_camera(chunky_render* r, int projector_type, const float* settings, int64_t n) {
+    FAN_RENDER(r, chunky_render_set_camera(m_, projector_type, settings, n));
+    LOCK_RENDER(r);
+    if (!settings) return fail(CHUNKY_E_INVALID, "set_camera: NULL settings");
+    CameraView& c = r->cam;
+    c.width = r->width;
+    c.height = r->height;
+    c.half_width = (float)(r->width / (2.0 * r->height));  // K/rayTracer.cl:66
+    c.inv_height = (float)(1.0 / r->height);               // K/rayTracer.cl:67
+    if (projector_type == 0) {
+        if (n != 15) return fail(CHUNKY_E_INVALID, "set_camera: pinhole needs 15 floats, got %lld", (long long)n);
+        memcpy(c.pos, settings, 12);
+        memcpy(c.m, settings + 3, 36);
+        c.aperture = settings[12];
+        c.subject_distance = settings[13];
+        c.fov_tan = settings[14];
+        c.rays = nullptr;
+    } else if (projector_type == -1) {
+        int64_t need = (int64_t)r->width * r->height * 6;
+        if (n != need) return fail(CHUNKY_E_INVALID, "set_camera: pre-generated rays need %lld floats, got %lld", (long long)need, (long long)n);
+        HIP_TRY(hipStreamSynchronize(r->ctx->stream));  // rays may still be read by queued passes
+        r->ad_resumable = false;  // (before the table changes: an upload that fails half way has changed it too)
+        HIP_TRY(r->rays.upload(settings, (size_t)n * 4, r->ctx->stream));
+        c.rays = (const float*)r->rays.p;
+    } else if (projector_type >= CHUNKY_PROJ_PARALLEL && projector_type <= CHUNKY_PROJ_STEREOGRAPHIC) {
+        if (int rc = check_projected("set_camera", projector_type, settings, n)) return rc;
+        memcpy(c.pos, settings, 12);
+        memcpy(c.m, settings + 3, 36);
+        c.aperture = 0.0f;
+        c.subject_distance = settings[13];  // (CameraView: settings[13] / [14] of a projected camera)
+        c.fov_tan = settings[14];
+        c.rays = nullptr;
+    } else {
+        return fail(CHUNKY_E_INVALID, "set_camera: projector type %d is not supported (-1 to 5)", projector_type);
+    }
+    c.projector_type = projector_type;
+    r->have_camera = true;
+    r->ad_resumable = false;  // what a pass renders changes: an adaptive run cannot continue across it
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_set_option(chunky_render* r, int option, int32_t value) {
+    FAN_RENDER(r, chunky_render_set_option(m_, option, value));
+    LOCK_RENDER(r);
+    switch (option) {
+        case CHUNKY_OPT_DRAW_DEPTH:
+            if (value < 0) return fail(CHUNKY_E_INVALID, "draw depth must be >= 0");
+            r->opts.draw_depth = value;
+            break;
+        case CHUNKY_OPT_MAX_DEPTH:
+            if (value < 1 || value > 255) return fail(CHUNKY_E_INVALID, "max depth must be in 1..255");
+            r->opts.max_depth = value;
+            break;
+        case CHUNKY_OPT_EMITTER_SCALE: r->opts.emitter_scale = bits_to_float(value); break;
+        case CHUNKY_OPT_KERNEL: r->kernel_variant = value; break;
+        case CHUNKY_OPT_SUN_SAMPLING:
+            if (value < -1 || value > 1) return fail(CHUNKY_E_INVALID, "sun sampling: -1 (as the reference), 0 or 1");
+            r->opts.sun_sampling = value;
+            break;
+        case CHUNKY_OPT_EMITTERS:
+            if (value != 0 && value != 1) return fail(CHUNKY_E_INVALID, "emitters: 0 or 1");
+            r->opts.emitters = value;
+            break;
+        case CHUNKY_OPT_BSDF:
+            if (value != 0 && value != 1) return fail(CHUNKY_E_INVALID, "bsdf: 0 or 1");
+            r->opts.bsdf = value;
+            break;
+        case CHUNKY_OPT_EMITTER_NEE:
+            if (value != 0 && value != 1) return fail(CHUNKY_E_INVALID, "emitter NEE: 0 or 1");
+            r->opts.nee = value;
+            break;
+        case CHUNKY_OPT_BVH_CULL_BEHIND:
+            if (value != 0 && value != 1) return fail(CHUNKY_E_INVALID, "BVH cull: 0 or 1");
+            r->opts.bvh_cull = value;
+            break;
+        default: return fail(CHUNKY_E_INVALID, "unknown option %d", option);
+    }
+    r->ad_resumable = false;  // (an option was set: a refused call ends nothing)
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_set_shard(chunky_render* r, int rank, int world, int tile) {
+    if (r && !r->parts.empty()) {
+        if (world < 1 || rank < 0 || rank >= world || tile < 0) return fail(CHUNKY_E_INVALID, "set_shard: rank %d / world %d / tile %d", rank, world, tile);
+        std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
+        // (the run length clamped as on a single target below; n_local stays 0: the members hold the slots)
+        return group_apply_shards(r, ShardView{rank, world, clamp_tile(r->width, r->height, tile), 0});
+    }
+    LOCK_RENDER(r);
+    if (world < 1 || rank < 0 || rank >= world || tile < 0) return fail(CHUNKY_E_INVALID, "set_shard: rank %d / world %d / tile %d", rank, world, tile);
+    // The view is stored with its run length clamped to the pixel count (shard_map.hpp make_shard_view): the device functions never
+    // see a larger one, which is what keeps shard_gid's products within an int.
+    ShardView t;
+    if (!make_shard_view(r->width, r->height, rank, world, tile, &t))
+        return fail(CHUNKY_E_INVALID, "set_shard: rank %d of %d in 16 x 16 blocks of a %d x %d image needs more than 2^31 pixel slots", rank, world, r->width, r->height);
+    if (r->shard.list) HIP_TRY(hipStreamSynchronize(r->ctx->stream));  // queued launches may still read the old list
+    r->block_list.release();
+    r->shard = t;
+    r->ad_resumable = false;
+    r->launch_cap = 0;  // the share changed: so does what a launch can stage
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_set_device_buffer(chunky_render* r, void* device_ptr) {
+    if (r && !r->parts.empty()) return chunky_render_set_device_buffer(r->parts[0], device_ptr);  // the image lives on member 0
+    LOCK_RENDER(r);
+    r->ad_resumable = false;  // the image an adaptive run would continue stays in the other buffer
+    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    r->fb = device_ptr ? (float*)device_ptr : (float*)r->own_fb.p;
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_device_buffer(chunky_render* r, void** device_ptr) {
+    if (r && !r->parts.empty()) return chunky_render_device_buffer(r->parts[0], device_ptr);
+    LOCK_RENDER(r);
+    if (!device_ptr) return fail(CHUNKY_E_INVALID, "NULL out pointer");
+    *device_ptr = r->fb;
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_reset(chunky_render* r) {
+    FAN_RENDER(r, chunky_render_reset(m_));
+    LOCK_RENDER(r);
+    r->ad_resumable = false;
+    HIP_TRY(hipMemsetAsync(r->fb, 0, (size_t)r->width * r->height * 3 * sizeof(float), r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+LaunchClock::~LaunchClock() {
+    for (Bracket& b : pending) {
+        (void)hipEventDestroy(b.e0);
+        (void)hipEventDestroy(b.e1);
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+}
+
+int LaunchClock::open(hipStream_t stream) {
+    for (hipEvent_t* e : {&e0, &e1}) {
+        if (*e) continue;  // left by a bracket that was never closed
+        if (pool->empty()) {
+            HIP_TRY(hipEventCreate(e));
+        } else {
+            *e = pool->back();
+            pool->pop_back();
+        }
+    }
+    HIP_TRY(hipEventRecord(e0, stream));
+    return CHUNKY_OK;
+}
+
+int LaunchClock::close(hipStream_t stream, int weight) {
+    HIP_TRY(hipEventRecord(e1, stream));
+    pending.push_back(Bracket{e0, e1, weight});
+    e0 = e1 = nullptr;
+    return CHUNKY_OK;
+}
+
+int LaunchClock::collect() {
+    for (Bracket& b : pending) {
+        float t = 0;
+        HIP_TRY(hipEventSynchronize(b.e1));
+        HIP_TRY(hipEventElapsedTime(&t, b.e0, b.e1));
+        ms += t;
+        count += b.weight;
+        pool->push_back(b.e0);
+        pool->push_back(b.e1);
+    }
+    pending.clear();
+    return CHUNKY_OK;
+}
+
+int LaunchClock::take(float* ms_out, int* count_out) {
+    if (int rc = collect()) return rc;
+    if (ms_out) *ms_out = ms;
+    if (count_out) *count_out = count;
+    ms = 0;
+    count = 0;
+    return CHUNKY_OK;
+}
+
+// The most passes one launch over the pixel slots of T carries: render_pool stages every sample of a launch (12 bytes each) — at
+// most `budget` bytes of it, fewer than 2^31 samples, at most `most` passes (kMaxPassesPerLaunch: the seeds fit the kernel-argument
+// segment; kMaxPoolPasses for render_pool, which reads longer launches' seeds from device memory — a share of the image on several
+// GPUs then pays the end-of-launch tail once per 1024 passes instead of four times).  Below 1 when not even one pass fits.
+int launch_pass_cap(const ShardView& T, int width, int height, size_t budget, int most) {
+    const int64_t n_slots = (int64_t)(staging_floats(T, width, height, 1) / 3);  // padded tiles
+    if (n_slots <= 0) return most;
+    int64_t cap = (int64_t)(budget / 12) / n_slots;
+    const int64_t cap31 = ((int64_t)1 << 31) / n_slots - 1;
+    if (cap > cap31) cap = cap31;
+    return (int)(cap > most ? most : cap);
+}
+
+// the extended light-transport options exist in render_pool's default instantiations only: CHUNKY_E_STATE where r's kernel
+// option, scene or max depth would send it elsewhere
+int check_extended_opts(const char* who, const chunky_render* r, const SceneView& S) {
+    if (!opts_extended(r->opts)) return CHUNKY_OK;
+    const bool bvh = !S.world_bvh_empty || !S.actor_bvh_empty;
+    if ((r->kernel_variant & (1 | 2 | 4 | 8)) || (bvh && !(S.bvh_rec && S.tri_rec && S.mat8)))
+        return fail(CHUNKY_E_STATE, "%s: the extended light-transport options need the default kernel (CHUNKY_OPT_KERNEL 0)", who);
+    if (!S.wide)  // their instantiations walk the re-laid-out tree only (an octree deeper than 15 levels has none)
+        return fail(CHUNKY_E_STATE, "%s: the extended light-transport options need an octree the wide re-layout takes (depth <= 15)", who);
+    // the fallback kernels never read these options: a set render_pool refuses (max depth 255) would render the reference's transport
+    if (!pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr))
+        return fail(CHUNKY_E_STATE, "%s: the extended light-transport options need max depth <= 254 (CHUNKY_OPT_MAX_DEPTH)", who);
+    return CHUNKY_OK;
+}
+
+// a device-to-host read-back of exactly `need` 4-byte values on r's stream; src == nullptr: nothing has been rendered into it yet
+int read_floats(const char* who, chunky_render* r, const void* src, void* out, int64_t n, int64_t need) {
+    if (!out || n != need) return fail(CHUNKY_E_INVALID, "%s: need %lld floats, got %lld", who, (long long)need, (long long)n);
+    if (!src) return fail(CHUNKY_E_STATE, "%s before anything was rendered into it", who);
+    HIP_TRY(hipMemcpyAsync(out, src, (size_t)n * 4, hipMemcpyDeviceToHost, r->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp) {
+    FAN_RENDER(r, chunky_render_passes(m_, seeds, n, first_buffer_spp));  // asynchronous on every member: the shares run side by side
+    LOCK_RENDER(r);
+    if (n < 0 || (n > 0 && !seeds) || first_buffer_spp < 0) return fail(CHUNKY_E_INVALID, "render_passes: bad arguments");
+    if (!r->have_camera) return fail(CHUNKY_E_STATE, "render_passes before set_camera");
+    SceneView S;
+    if (int rc = scene_view(r->scene, &S, r->opts.nee != 0)) return rc;
+    S.bvh_cull = r->opts.bvh_cull;
+    if (int rc = check_extended_opts("render_passes", r, S)) return rc;
+    r->ad_resumable = false;  // the call is accepted: it writes the framebuffer (chunky_render_run / _run_ex end it here and in chunky_render_reset)
+    if (r->clock.full())
+        if (int rc = r->clock.collect()) return rc;
+    if (r->shard.n_local <= 0) return CHUNKY_OK;  // this rank (or group member) owns no tile of so small an image: nothing to render
+    if (r->shard.world != 1 && r->shard.tile == 0 && !r->shard.list &&
+        !pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr)) {
+        // a share of 16 x 16 blocks (every group member has one) and a scene / option set render_pool does not take: the
+        // fallback kernels render the same pixels from a list
+        const std::vector<int32_t> px = block_pixel_list(r->width, r->height, r->shard);
+        if (px.empty()) return CHUNKY_OK;
+        HIP_TRY(r->block_list.upload(px.data(), px.size() * 4, r->ctx->stream));
+        r->shard.list = (const int*)r->block_list.p;
+        r->shard.n_list = (int)px.size();
+    }
+    // render_pool takes up to kMaxPoolPasses per launch, the other kernels what the kernel-argument segment holds
+    const int most = pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr) ? kMaxPoolPasses : kMaxPassesPerLaunch;
+    if (r->launch_cap <= 0 || r->launch_cap_most != most) {
+        r->launch_cap = std::max(1, launch_pass_cap(r->shard, r->width, r->height, kStagingBytes, most));  // sized by the tiles THIS rank renders
+        r->launch_cap_most = most;
+    }
+    for (int done = 0; done < n;) {
+        PassSeeds ps;
+        ps.n = (n - done) < r->launch_cap ? (n - done) : r->launch_cap;
+        size_t need = staging_floats(r->shard, r->width, r->height, ps.n) * sizeof(float);
+        if (r->staging.bytes < need) {  // grows to the largest launch seen; launches on the stream are ordered, so it is reused
+            HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+            r->staging.release();
+            // chunky_render_run_ex climbs 1, 8, 64 ... passes per launch: one allocation for where it is going, not four
+            int ahead = r->reserve_passes < r->launch_cap ? r->reserve_passes : r->launch_cap;
+            if (ahead > kMaxPassesPerLaunch) ahead = kMaxPassesPerLaunch;  // (the pass loop's own launches stop there)
+            if (ahead > ps.n) {
+                size_t want = staging_floats(r->shard, r->width, r->height, ahead) * sizeof(float);
+                size_t free_b = 0, total_b = 0;  // never more than half of what the device has left: other targets and members live there too
+                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b / 2) want = 0;
+                (void)hipGetLastError();
+                if (want >= need && hipMalloc(&r->staging.p, want) == hipSuccess) {
+                    r->staging.bytes = want;
+                } else {
+                    (void)hipGetLastError();
+                    r->staging.p = nullptr;
+                }
+            }
+        }
+        if (r->staging.bytes < need) {
+            // memory is short: shorter launches instead of a failed render (each halving halves the array)
+            while (hipMalloc(&r->staging.p, need) != hipSuccess) {
+                (void)hipGetLastError();
+                r->staging.p = nullptr;
+                if (ps.n == 1) return fail(CHUNKY_E_HIP, "render_passes: cannot allocate %zu bytes for one pass of staged samples", need);
+                ps.n = (ps.n + 1) / 2;
+                r->launch_cap = ps.n;
+                need = staging_floats(r->shard, r->width, r->height, ps.n) * sizeof(float);
+            }
+            r->staging.bytes = need;
+        }
+        ps.first_spp = first_buffer_spp + done;
+        const int* seeds_dev = nullptr;
+        if (ps.n <= kMaxPassesPerLaunch) {
+            memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
+        } else {  // a long launch: its seeds go to device memory, in stream order behind the launch that read the buffer last
+            if (!r->seed_buf.p) {
+                HIP_TRY(r->seed_buf.alloc((size_t)kMaxPoolPasses * 4));
+            }
+            // from a pinned slot of the target's own (the caller may reuse or free `seeds` as soon as this call returns — the JNI
+            // glue releases the Java array — and a copy out of pageable memory is only safe if the runtime happens to stage it)
+            chunky_render::SeedSlot& slot = r->seed_ring[r->seed_next++ % chunky_render::kSeedSlots];
+            if (!slot.host) {  // the event first: a slot is only ever seen with both or with neither
+                if (!slot.copied) HIP_TRY(hipEventCreateWithFlags(&slot.copied, hipEventDisableTiming));
+                HIP_TRY(hipHostMalloc((void**)&slot.host, (size_t)kMaxPoolPasses * 4, hipHostMallocDefault));
+            } else {
+                HIP_TRY(hipEventSynchronize(slot.copied));  // the copy that read this slot last (kSeedSlots launches ago)
+            }
+            memcpy(slot.host, seeds + done, (size_t)ps.n * 4);
+            HIP_TRY(hipMemcpyAsync(r->seed_buf.p, slot.host, (size_t)ps.n * 4, hipMemcpyHostToDevice, r->ctx->stream));
+            HIP_TRY(hipEventRecord(slot.copied, r->ctx->stream));
+            seeds_dev = (const int*)r->seed_buf.p;
+        }
+        if (int rc = r->clock.open(r->ctx->stream)) return rc;
+        HIP_TRY(launch_render(r->kernel_variant, S, r->cam, r->opts, r->shard, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream,
+                              &r->last_choice, (float*)r->staging.p, seeds_dev));
+        if (int rc = r->clock.close(r->ctx->stream)) return rc;
+        done += ps.n;
+    }
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_sync(chunky_render* r) {
+    FAN_RENDER(r, chunky_render_sync(m_));
+    LOCK_RENDER(r);
+    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_read(chunky_render* r, float* out, int64_t n) {
+    if (r && !r->parts.empty()) {
+        std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
+        const int64_t need = (int64_t)r->width * r->height * 3;
+        if (!out || n != need) return fail(CHUNKY_E_INVALID, "render_read: need %lld floats, got %lld", (long long)need, (long long)n);
+        if (int rc = group_gather(r)) return rc;
+        return chunky_render_read(r->parts[0], out, n);
+    }
+    LOCK_RENDER(r);
+    return read_floats("render_read", r, r->fb, out, n, (int64_t)r->width * r->height * 3);
+}
+
+extern "C" int chunky_render_kernel_time(chunky_render* r, float* total_ms, int* launches) {
+    if (r && !r->parts.empty()) {  // the members run side by side: the slowest one's total, member 0's launch count
+        std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
+        float worst = 0;
+        for (size_t i = 0; i < r->parts.size(); i++) {
+            float ms = 0;
+            int n = 0;
+            if (int rc = chunky_render_kernel_time(r->parts[i], &ms, &n)) return rc;
+            if (ms > worst) worst = ms;
+            if (i == 0 && launches) *launches = n;
+        }
+        if (total_ms) *total_ms = worst;
+        return CHUNKY_OK;
+    }
+    LOCK_RENDER(r);
+    return r->clock.take(total_ms, launches);
+}
+
+extern "C" int chunky_render_kernel_info(chunky_render* r, int32_t out8[8]) {
+    if (r && !r->parts.empty()) return chunky_render_kernel_info(r->parts[0], out8);
+    LOCK_RENDER(r);
+    if (!out8) return fail(CHUNKY_E_INVALID, "kernel_info: NULL output");
+    memset(out8, 0, 8 * sizeof(int32_t));
+    out8[0] = r->last_choice.tree;
+    out8[1] = r->last_choice.group;
+    out8[2] = r->last_choice.bvh;
+    out8[3] = r->last_choice.blocks;
+    out8[4] = r->last_choice.pool;
+    out8[5] = r->last_choice.ext;
+    out8[7] = r->last_choice.sorted;
+    if (r->launch_cap > 0) {
+        out8[6] = r->launch_cap;  // (of the kernel family that ran last)
+    } else {  // before the first launch: what chunky_render_passes is going to decide for this scene and option set
+        SceneView S;
+        int most = kMaxPassesPerLaunch;
+        if (scene_view(r->scene, &S, false) == CHUNKY_OK && pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr)) most = kMaxPoolPasses;
+        out8[6] = std::max(1, launch_pass_cap(r->shard, r->width, r->height, kStagingBytes, most));
+    }
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_phase_stats(chunky_render* r, uint64_t* out24, int reset) {
+    if (r && !r->parts.empty()) return chunky_render_phase_stats(r->parts[0], out24, reset);
+    LOCK_RENDER(r);
+    if (!out24) return fail(CHUNKY_E_INVALID, "phase_stats: NULL output");
+    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    HIP_TRY(hipMemcpy(out24, (char*)r->work_counter.p + 8, 192, hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(hipMemset((char*)r->work_counter.p + 8, 0, 192));
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_preview(chunky_render* r, int32_t* argb_out) {
+    if (r && !r->parts.empty()) return chunky_render_preview(r->parts[0], argb_out);  // one first-hit pass of the whole image: member 0
+    LOCK_RENDER(r);
+    if (!argb_out) return fail(CHUNKY_E_INVALID, "preview: NULL output");
+    if (!r->have_camera) return fail(CHUNKY_E_STATE, "preview before set_camera");
+    SceneView S;
+    if (int rc = scene_view(r->scene, &S)) return rc;
+    S.bvh_cull = r->opts.bvh_cull;
+    DevBuf out;
+    size_t bytes = (size_t)r->width * r->height * 4;
+    HIP_TRY(out.alloc(bytes));
+    HIP_TRY(launch_preview(r->kernel_variant, S, r->cam, r->opts, (int*)out.p, r->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(argb_out, out.p, bytes, hipMemcpyDeviceToHost, r->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_trace_records(chunky_render* r, int32_t seed, const int32_t* gids, int n,
+                                           chunky_hit_record* records, int32_t* counts, float* radiance) {
+    if (r && !r->parts.empty()) return chunky_render_trace_records(r->parts[0], seed, gids, n, records, counts, radiance);
+    LOCK_RENDER(r);
+    if (n < 0 || (n > 0 && (!gids || !records || !counts || !radiance))) return fail(CHUNKY_E_INVALID, "trace_records: bad arguments");
+    if (!r->have_camera) return fail(CHUNKY_E_STATE, "trace_records before set_camera");
+    if (2 * r->opts.max_depth > kMaxTraces) return fail(CHUNKY_E_STATE, "trace_records holds %d traces per sample: max depth must be <= %d", kMaxTraces, kMaxTraces / 2);
+    if (n == 0) return CHUNKY_OK;
+    for (int i = 0; i < n; i++)
+        if (gids[i] < 0 || gids[i] >= r->width * r->height) return fail(CHUNKY_E_INVALID, "trace_records: gid %d outside the image", gids[i]);
+    SceneView S;
+    if (int rc = scene_view(r->scene, &S)) return rc;
+    S.bvh_cull = r->opts.bvh_cull;
+    DevBuf dg, dr, dc, dq;
+    hipStream_t st = r->ctx->stream;
+    HIP_TRY(dg.upload(gids, (size_t)n * 4, st));
+    HIP_TRY(hipMalloc(&dr.p, (size_t)n * kMaxTraces * sizeof(HitRecord)));
+    HIP_TRY(hipMalloc(&dc.p, (size_t)n * 4));
+    HIP_TRY(hipMalloc(&dq.p, (size_t)n * 12));
+    HIP_TRY(hipMemsetAsync(dr.p, 0, (size_t)n * kMaxTraces * sizeof(HitRecord), st));
+    HIP_TRY(launch_trace_records(r->kernel_variant, S, r->cam, r->opts, seed, (const int*)dg.p, n, (HitRecord*)dr.p, (int*)dc.p, (float*)dq.p, st));
+    HIP_TRY(hipMemcpyAsync(records, dr.p, (size_t)n * kMaxTraces * sizeof(HitRecord), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(counts, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(radiance, dq.p, (size_t)n * 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CHUNKY_OK;
+}

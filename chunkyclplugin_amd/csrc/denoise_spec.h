@@ -1,5 +1,5 @@
 /* denoise_spec.h — the per-pixel arithmetic of the edge-avoiding À-Trous denoiser (Dammertz et al. 2010), defined once for the
- * host loop (capi.hip chunky_denoise_host) and the kernels (denoise.hip), in the role camera_proj.h plays for the cameras.
+ * host loop (denoise_host.cpp chunky_denoise_host) and the kernels (denoise.hip), in the role camera_proj.h plays for the cameras.
  *
  * Everything here is made of exactly rounded binary32 operations (+ - * / rint, fma only where written as rt_fma), compiled with
  * -ffp-contract=off on both sides, so a pixel has the same bits wherever it is evaluated and however its taps are fetched.

@@ -46,7 +46,7 @@ DEV unsigned filter_pack(float r, float g, float b) {
 
 // GAMMA and ACES end in pow(c, 1/2.2) -> c * 255 + 0.5 -> (uint) -> clamp to 255 (post_processing_filter.cl:24-27,33-38,
 // rgba.h:9-14): a monotone step function of the float c with at most 255 steps.  Its thresholds (kT[k] = the smallest float
-// whose byte is >= k, found on the host by bisection with the same rt_pow: capi.hip gamma_thresholds; monotonicity is checked
+// whose byte is >= k, found on the host by bisection with the same rt_pow: capi_host.cpp gamma_thresholds; monotonicity is checked
 // exhaustively by tests/test_filter.py) replace the six binary64 rt_pow per lane that made these two curves issue-bound.
 // The byte is estimated with the hardware log2 / exp2 (v = 2^(log2(c) / 2.2) * 255 + 0.5, measured: off by at most 2.3e-5, and
 // by less below), and only an estimate that falls within kGammaGuard of a step can be wrong, by one: those — one value in

@@ -141,7 +141,7 @@ hipError_t launch_adaptive_rebuild(int width, int height, unsigned char* active,
                                    hipStream_t stream);
 // pixels still active record n
 hipError_t launch_adaptive_finish(int n_pixels, const unsigned char* active, int* count, int n, hipStream_t stream);
-// thresholds: 256 floats on the device (capi.hip gamma_thresholds) or null = evaluate pow per channel
+// thresholds: 256 floats on the device (capi_host.cpp gamma_thresholds) or null = evaluate pow per channel
 hipError_t launch_filter(long long n_pixels, float exposure, const double* in, unsigned* out, int type, hipStream_t stream,
                          const float* thresholds = nullptr);
 // tone map self test: gamma_bytes3 (curve 0) / aces_bytes3 (curve 2) against the reference's arithmetic and a search of the

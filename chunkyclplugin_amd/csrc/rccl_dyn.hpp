@@ -1,4 +1,4 @@
-// rccl_dyn.hpp — RCCL, bound at run time.  The read-back exchange of a multi-GPU group (capi.hip group_gather) is one grouped
+// rccl_dyn.hpp — RCCL, bound at run time.  The read-back exchange of a multi-GPU group (capi_group.hip group_gather) is one grouped
 // RCCL operation over xGMI when the collective library is there; the library is NOT a link-time dependency of
 // libchunky_hip.so: a JVM (or a 1-GPU box) without librccl still loads this library and renders, and a process that already
 // holds an RCCL (PyTorch ships its own, same soname) gets that one instead of a second copy.  Nothing of RCCL is needed to

@@ -481,7 +481,7 @@ __global__ void __launch_bounds__(256) fold_kernel(const float* __restrict__ sta
     res[3 * (size_t)gid + c] = mean;
 }
 
-// Read-back exchange of a multi-GPU group (capi.hip group_gather): the pixels of the slots of shard T, 3 floats per slot
+// Read-back exchange of a multi-GPU group (capi_group.hip group_gather): the pixels of the slots of shard T, 3 floats per slot
 // in slot order, out of the image (PACK) or back into one.  Slot -> pixel is pool_slot_gid, as in the kernels that rendered
 // them; padding slots carry nothing.
 template <bool PACK>
@@ -498,7 +498,7 @@ __global__ void __launch_bounds__(256) gather_kernel(ShardView T, int width, int
         a[0] = b[0]; a[1] = b[1]; a[2] = b[2];
     }
 }
-// The exchange by ncclReduce (capi.hip group_gather_reduce) sums zero-padded framebuffers: this clears the pixels shard T does
+// The exchange by ncclReduce (capi_group.hip group_gather_reduce) sums zero-padded framebuffers: this clears the pixels shard T does
 // not own — same ownership rule as shard_gid / pool_slot_gid (runs of T.tile pixel indices, or 16 x 16 blocks, dealt round-robin).
 __global__ void __launch_bounds__(256) clear_foreign_kernel(ShardView T, int width, int height, float* __restrict__ fb) {
     const int gid = (int)(blockIdx.x * 256 + threadIdx.x);
@@ -540,7 +540,7 @@ static hipError_t launch_pool(int variant, const SceneView& S, const CameraView&
     const bool proj = C.projector_type > 0;  // a projected camera: proj::render_pool, same template arguments
     const bool ext = opts_extended(O);  // EXPERIMENTAL light-transport options: their own instantiations
     // Block tests sorted by kind (full cubes / model blocks in phases of their own): for scenes in which model blocks are common
-    // (S.sort_blocks, capi.hip scene_view) — the city gains 2 – 3 %, a scene with hardly any pays 1 % for the bookkeeping; variant bit 8
+    // (S.sort_blocks, capi_scene.hip scene_view) — the city gains 2 – 3 %, a scene with hardly any pays 1 % for the bookkeeping; variant bit 8
     // forces it on, bit 9 off (tests and A/B runs); the plain kernel at its full pool only
     const bool sorted = ((variant & 256) || S.sort_blocks) && !(variant & 512) && !bvh && !ext && tree != 0 && S.block_info != nullptr;
     bool sorted_ran = false;

@@ -75,12 +75,12 @@ struct SceneView {
     // full cube (K/material.h:31-40), 0} — the block-palette and material-palette reads of
     // K/block.h:36-49 as ONE 32-byte load; built at upload, null when a palette is missing
     const int4* __restrict__ block_info;
-    int sort_blocks;   // model blocks are common in this world: render_pool tests full cubes and model blocks in phases of their own (capi.hip scene_view)
+    int sort_blocks;   // model blocks are common in this world: render_pool tests full cubes and model blocks in phases of their own (capi_scene.hip scene_view)
     int n_block_ints;  // ints in the block palette: a leaf whose block pointer lies beyond it never intersects (the wide tree marks such leaves at upload)
     // per quad, at the quad's own int offset in `quads`: {normal xyz, dot(normal, origin), |xv|^2, |yv|^2} — the
     // ray-independent part of K/primitives.h:262-276, evaluated once at upload with this same rt_math.h; null = compute
     const float* __restrict__ quad_aux;
-    // 16-byte-aligned re-layouts built at upload (capi.hip rebuild_derived); block_info word 7 of a model block =
+    // 16-byte-aligned re-layouts built at upload (capi_scene.hip rebuild_derived); block_info word 7 of a model block =
     // first record << 8 | primitive count, 0 = none (the packed palettes are read as they are):
     //   mat8      per material two words {flags, tint, textureSize, color} {normal_emittance, word 5, 0, 0}
     //   aabb_rec  per box three words {xmin, xmax, ymin, ymax} {zmin, zmax, flags, E} {S, W, T, B} (materials = mat8 indices)
@@ -431,7 +431,7 @@ DEV float quad_model_hit_rec(const SceneView& S, int rec, f3 no, f3 dir, Hit& h)
 // blocks (render_pool, by the model bit of the re-laid-out tree's leaf entries — widetree.cpp annotate_wide_tree — and tests them in
 // phases of their own): the other kind's code is not part of that instantiation, a block of the other kind (there is none: the
 // entries are annotated from the same palette; block_info marks a malformed block as a type that never hits) does not hit.  Both
-// need block_info (capi.hip builds it for every scene).
+// need block_info (capi_scene.hip builds it for every scene).
 enum : int { kBlockAny = 0, kBlockCubes = 1, kBlockModels = 2 };
 template <int KINDS = kBlockAny>
 DEV float block_hit(const SceneView& S, int block, int bx, int by, int bz, f3 pos, f3 dir, f3 inv, Hit& h) {

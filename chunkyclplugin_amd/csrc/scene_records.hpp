@@ -1,6 +1,6 @@
 // scene_records.hpp — everything a scene upload derives on the host from caller-supplied ints (palettes, entity BVHs, the octree):
 // plain C++17 over vectors and scalars, no device call.  This is the part hostile scene data reaches first, so
-// tests/sanitize/scene_records_fuzz.cpp runs it under AddressSanitizer + UBSan; capi.hip uploads what it returns.
+// tests/sanitize/scene_records_fuzz.cpp runs it under AddressSanitizer + UBSan; capi_scene.hip uploads what it returns.
 #pragma once
 #include <cstdint>
 #include <cstring>

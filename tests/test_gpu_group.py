@@ -169,7 +169,7 @@ def test_members_without_a_block_render_nothing(port):
 def test_group_when_the_pool_kernel_does_not_apply(group3, gpu_instance, port, case):
     """Every member of a group holds a share of 16 x 16 blocks, which render_pool maps itself.  Scenes / options it does not take
     (variant bit 3 = round 1's kernel, bit 0 with entities = the packed BVH walk, a draw depth beyond its 16-bit step counter,
-    bit 1 = one lane per path) run the fallback kernels on the same pixels from a list (capi.hip block_pixel_list): the image
+    bit 1 = one lane per path) run the fallback kernels on the same pixels from a list (capi_render.hip block_pixel_list): the image
     is still the one-context image and the oracle's."""
     from oracle.binding import PortOptions
     if case == "variant1_entities":

@@ -348,11 +348,11 @@ def test_million_triangle_world(gpu_instance, port):
 
 
 def test_launch_clock_drains_in_mid_stream(gpu_instance, port):
-    """A launch clock (capi.hip LaunchClock) holds at most kClockDrain brackets: the call that finds more collects them
+    """A launch clock (capi_internal.hpp LaunchClock) holds at most kClockDrain brackets: the call that finds more collects them
     first, while later launches are still queued.  kClockDrain + 4 one-pass launches without a wait in between cross that
     point once: the clock has counted every launch, a second read finds it zeroed, and the image is the oracle's."""
     import re
-    text = open(os.path.join(native.CSRC, "capi.hip")).read()
+    text = open(os.path.join(native.CSRC, "capi_internal.hpp")).read()
     n = int(re.search(r"kClockDrain = (\d+);", text).group(1)) + 4
     sc = scenes.tiny_scene(width=16, height=16)  # a single tile
     seeds = native.java_random_ints(n)
