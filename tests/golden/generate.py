@@ -15,6 +15,7 @@ timed_camera_rows.npz (`... generate.py cameras`): rows of the camera / tint / a
 helpers.npz (`... generate.py helpers`): known answers of the reference's exported helper functions (write_helpers).
 deep.npz (`... generate.py deep`): the golden worlds inside octrees of depth 11 - 16 (write_deep).
 timed_big_rows.npz (`... generate.py timed` writes it beside timed_rows.npz): eight rows of the beyond-cache view (write_timed_big).
+routes.npz (`... generate.py routes`): the exhibits of tests/route_scenes.py — the routes no other fixture reaches (write_routes).
 libm_platform.npz (`... generate.py libm`): images of the reference object on a second platform layer (glibc libm): write_libm.
 """
 import os
@@ -109,7 +110,8 @@ def write_deep(ref):
 
 def write_cameras(ref):
     """timed_camera_rows.npz: the same as timed_rows.npz for golden_scenes.CAMERA_VIEWS — depth of field, pre-generated rays (a
-    ragged 1917 x 1075 view among them), a camera outside the world, the biome-water tint, textures over four atlas layers, sun
+    ragged 1917 x 1075 view among them), a camera outside the world, a flooded world (whose water, tint type 3, 4 of the rows' 400 726 traces
+    reach: the tint's fixture is routes.npz), textures over four atlas layers, sun
     draws in the room, the city with depth of field, and pre-generated rays into the entity world — eight rows each
     (golden_scenes.camera_rows), TIMED_PASSES passes of the java.util.Random(0) seed stream."""
     seeds = scenes.java_random_ints(gs.TIMED_PASSES)
@@ -151,6 +153,41 @@ def write_helpers(ref):
         ok = out[f"out{which}"]
         print("helper", which, rows.shape, "finite first column:", float(np.isfinite(ok[:, 0]).mean()), flush=True)
     np.savez_compressed(os.path.join(HERE, "helpers.npz"), **out)
+
+
+def write_routes(ref):
+    """routes.npz: the scenes of tests/route_scenes.py (the exhibits at depth 6, embedded at depths 7, 11 and 16, and the four
+    entity variants), outputs of the reference build only: the radiance after route_scenes.N_PASSES passes of the java.util.Random(0)
+    seed stream, the preview, the trace records of seed[0] at every 7th pixel (the valid records of all pixels one after the other,
+    for the scenes of RECORD_SCENES), the reference's own helpers 4 and 12 on rows drawn from the exhibits' palettes, input digests."""
+    import route_scenes as rs
+    seeds = scenes.java_random_ints(rs.N_PASSES)
+    out = {"seeds": seeds}
+    for name in rs.NAMES:
+        sc = rs.make(name)
+        h = binding.SceneHandle(sc)
+        out[name + "_digest"] = gs.input_digest(sc)
+        out[name + "_res"] = ref.render_passes(h, seeds)
+        out[name + "_preview"] = ref.preview(h)
+        if name in rs.RECORD_SCENES:
+            recs, cnt, rad = [], [], []
+            for g in rs.RECORD_GIDS:
+                r, c = ref.trace_records(h, int(seeds[0]), int(g))
+                recs.append(r.copy())
+                cnt.append(len(r))
+                rad.append(c.copy())
+            out[name + "_records"] = np.concatenate(recs)
+            out[name + "_counts"] = np.array(cnt, np.int32)
+            out[name + "_radiance"] = np.array(rad, np.float32)
+        print(name, "res mean", float(np.nanmean(out[name + "_res"])), flush=True)
+    base = rs.make("routes")
+    for which in rs.HELPER_KINDS:
+        rows = rs.helper_rows(which)
+        out[f"in{which}_sha256"] = gs.rows_digest(rows)
+        out[f"out{which}"] = ref.helpers(base, which, rows)
+    path = os.path.join(HERE, "routes.npz")
+    savez_lzma(path, **out)
+    print("routes written", os.path.getsize(path), "bytes")
 
 
 LIBM_SPP = 32
@@ -207,6 +244,8 @@ def main():
         return write_cameras(ref)
     if "libm" in sys.argv[1:]:
         return write_libm()
+    if "routes" in sys.argv[1:]:
+        return write_routes(ref)
     seeds = scenes.java_random_ints(gs.N_PASSES)
     for name in gs.NAMES:
         sc = gs.make(name)
@@ -244,6 +283,7 @@ def main():
     write_deep(ref)
     write_cameras(ref)
     write_helpers(ref)
+    write_routes(ref)
     write_libm()
 
 

@@ -45,7 +45,8 @@ def make(name: str, chunks: int = 2) -> scenes.PackedScene:
     if name == "atlas_layers":   # thirteen textures over four 32x32 atlas layers (quirk B#7: the 19-bit layer mask)
         return scenes.outdoor_world(chunks=chunks, height=48, seed=101, width=W, img_height=H, aabb_frac=0.08, quad_frac=0.05,
                                     emitters=0.02, atlas_tiles=(2, 2))
-    if name == "water":          # tint type 3 (biome water, K/material.h:61-72) beside types 1, 2 and 0xFF
+    if name == "water":          # a world that HOLDS water cubes (tint type 3, K/material.h:61-72) beside tint types 1, 2 and 0xFF: no ray of
+        # this fixture lands on them (5 leaves at depth 6, 54 at depth 7; profiles/route_census.json) — tint 3 is compared in route_scenes.py
         return scenes.outdoor_world(chunks=chunks, height=48, seed=101, width=W, img_height=H, aabb_frac=0.08, quad_frac=0.05,
                                     emitters=0.02, water=True)
     if name == "indoor":
@@ -185,9 +186,10 @@ def pregen_rays(sc: scenes.PackedScene, width: int, height: int, seed: int, aim=
 
 
 def camera_view(name: str) -> scenes.PackedScene:
-    """The camera kinds (depth of field, pre-generated rays, a camera outside the world), the biome-water tint, textures over
+    """The camera kinds (depth of field, pre-generated rays, a camera outside the world), a flooded world, textures over
     several atlas layers and sun draws indoors, on the timed worlds at the timed sizes — the scenes of timed_view with one thing
-    changed, so that they run the instantiations bench.py times (CAMERA_KERNEL)."""
+    changed, so that they run the instantiations bench.py times (CAMERA_KERNEL).  The flooded world ("water") hardly tests the
+    biome-water tint: 4 of the 400 726 traces of its eight rows land on water (profiles/route_census.json); tests/route_scenes.py does."""
     if name == "outdoor_dof":
         return with_dof(timed_view("outdoor"), 0.4, 60.0)
     if name == "outdoor_pregen":   # ragged: 1917 x 1075 pads the last 16 x 16 tile column and row

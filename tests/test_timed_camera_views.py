@@ -1,6 +1,8 @@
 """The camera kinds, tints and atlas layers on the kernels that are timed.  Every golden world has octree depth 6 (render_pool<16, ...>)
-and the timed rows hold pinhole views only, so depth of field, pre-generated rays, a camera outside the world, the biome-water tint,
+and the timed rows hold pinhole views only, so depth of field, pre-generated rays, a camera outside the world, a flooded world,
 textures over several atlas layers, sun draws indoors and the extended integrator never ran on render_pool<17, ...> in a test.
+(The flooded world does not stand for the biome-water tint: 4 of the 400 726 traces of its rows land on water, and none of the small
+`water` goldens' — profiles/route_census.json.  tests/test_gpu_routes.py compares tint 3, on render_pool<17, ...> too.)
 tests/golden/timed_camera_rows.npz holds rows of such views at the timed sizes (golden_scenes.camera_view), rendered by the REFERENCE
 build (tests/golden/generate.py cameras).  The C restatement must reproduce them (CPU), and so must the HIP kernels (GPU), in the
 instantiation golden_scenes.CAMERA_KERNEL names, in the other block-test order, in block shards and in launches longer than the
