@@ -429,11 +429,35 @@ DEV void march_step(const SceneView& S, const RenderOpts& O, LaneState& L, LaneM
     live_out = live;
 }
 
-template <int TREE, int END, bool FARREG = true, int KINDS = kBlockAny>
+// SHARE (render_pool's six-word record, render_pool.hip pool_pack): a hit's colour and emittance live in the registers of 1/d and the
+// distance marched from the block test that ends the trace until SHADE.  During a trace both are dead as fields of the record — a hit
+// rewrites them before SHADE reads them, and they are written only when the test accepts (material_eval), which is when it reports a
+// hit — so the test works on a record of its own whose colour and emittance are never copied in, and a hit hands them straight to
+// L.inv / L.dist_march: no copy of the record going in, no predicated copy back, no move between the two sets of registers afterwards.
+template <int TREE, int END, bool FARREG = true, int KINDS = kBlockAny, bool SHARE = false>
 DEV int block_phase(const SceneView& S, LaneState& L) {
     f3 pos = L.o + L.d * L.dist_march;
     f3 po = pos + L.d * kOffset;
     int bx = (int)rt_floor(po.x), by = (int)rt_floor(po.y), bz = (int)rt_floor(po.z);
+    if (SHARE) {
+        Hit t;
+        t.normal = L.h.normal;
+        const float dist = block_hit<KINDS>(S, L.cand_data, bx, by, bz, pos, L.d, L.inv, t);
+        if (!L.shadow) L.h.normal = t.normal;  // a rejected cube has already overwritten the normal (K/block.h:59-60)
+        if (dist == dist) {
+            if (!L.shadow) {
+                L.h.distance = L.dist_march + dist;
+                L.h.material = L.cand_data;
+            }
+            // (after a shadow ray's hit what arrives here is read by nobody)
+            L.inv = mk3(t.color.x, t.color.y, t.color.z);
+            L.dist_march = t.emittance;
+            L.oct_hit = true;
+            return END;
+        }
+        leaf_exit<TREE, FARREG>(S, L, po, bx, by, bz, L.cand_level);
+        return ST_MARCH;
+    }
     Hit t = L.h;
     float dist = block_hit<KINDS>(S, L.cand_data, bx, by, bz, pos, L.d, L.inv, t);
     if (!L.shadow) {  // a rejected cube has already overwritten the normal (K/block.h:59-60)

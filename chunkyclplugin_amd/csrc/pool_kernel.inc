@@ -134,6 +134,12 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
             parts.t[PT_HANDOUT] += X == 0 ? 1 : 0;
         }
         int n_exec = 0;
+        // The phases are consecutive ifs, not one if / else-if chain, and X is made opaque between them (CHUNKY_PHASE_END): each phase
+        // then updates the path state where it lives.  As alternatives of one chain the phases' results met in a join behind them, and
+        // because the compiler lays the alternatives out one after the other — every later one reachable, as far as it can tell, from
+        // the ones before — the state a later phase reads had to stay intact while an earlier one ran: SHADE and BLOCK copied the state
+        // out of the loop's registers on entry (20 and 16 v_mov_b32), worked on the copies, and a block behind them moved all of it
+        // back (28) — tools/isa_copies.py.  Exactly one of the ifs runs per iteration, as before.
         if (X == 0) {
             WaveArgPtr A = fresh_args();
             const SceneView Sm = arg_copy(&A->S);
@@ -187,24 +193,28 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
                 prof[0] -= 1;
                 prof[1] -= (unsigned long long)n_exec;
             }
-        } else if (X == 1) {
+        }
+        CHUNKY_PHASE_END(X, "march");
+        if (X == 1) {
             n_exec = count_lanes(st == ST_BLOCK);
             const SceneView S = arg_copy(&fresh_args()->S);
             if (st == ST_BLOCK) {
-                st = block_phase<TREE, END, false, SPLIT ? kBlockCubes : kBlockAny>(S, L);
-                if (WORDS == 6 && st == END) hit_to_march_registers(L);
+                st = block_phase<TREE, END, false, SPLIT ? kBlockCubes : kBlockAny, WORDS == 6>(S, L);
             }
-        } else if (SPLIT && X == ST_MODEL) {
+        }
+        CHUNKY_PHASE_END(X, "block");
+        if (SPLIT && X == ST_MODEL) {
             n_exec = count_lanes(st == ST_MODEL);
             if (STATS) parts.t[8] += (unsigned long long)n_exec + (1ull << 40);  // value 22 of the profile: lanes, and executions in bits 40 up
             const SceneView S = arg_copy(&fresh_args()->S);
             asm volatile("; chunky-mark models");  // (comments in the compiled kernel: tools/isa_scratch.py finds the model blocks' phase by them)
             if (st == ST_MODEL) {
-                st = block_phase<TREE, END, false, kBlockModels>(S, L);
-                if (WORDS == 6 && st == END) hit_to_march_registers(L);
+                st = block_phase<TREE, END, false, kBlockModels, WORDS == 6>(S, L);
             }
             asm volatile("; chunky-mark models-end");
-        } else if (BVH && X == 5) {
+        }
+        CHUNKY_PHASE_END(X, "model-blocks");
+        if (BVH && X == 5) {
             // The walk: inner-node visits and triangle tests are one step function (rwalk_step: the same four 16-byte reads
             // from one array or the other), so a walker is ST_BVH throughout and the loop below counts that one state.  The
             // wave stays while enough walkers remain, or until enough lanes are free for a refill from parked walkers.
@@ -234,7 +244,9 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
                 prof[3] -= 1;
                 prof[4] -= (unsigned long long)n_exec;
             }
-        } else {
+        }
+        CHUNKY_PHASE_END(X, "walk");
+        if (X == 2) {
             n_exec = count_lanes(st == ST_SHADE);
             WaveArgPtr A = fresh_args();
             const SceneView S = arg_copy(&A->S);
@@ -318,6 +330,7 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
             if (st == ST_SETUP) st = trace_setup<END, false>(S, L);
             part_end<STATS>(&parts, PT_SETUP);
         }
+        CHUNKY_PHASE_END(X, "shade");
         if (STATS) {
             const unsigned long long dt = __builtin_amdgcn_s_memtime() - t0;
 #pragma unroll

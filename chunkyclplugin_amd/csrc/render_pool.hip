@@ -194,8 +194,8 @@ DEV void pool_pack(const LaneState& L, uint4 (&v)[WORDS]) {
         // start of a trace to its end colour and emittance are dead (a hit rewrites them before SHADE reads them; a shadow ray's
         // emittance, |dot(sun direction, normal)|, is evaluated by shade_phase where it is read), from the end of a trace to the start of
         // the next one 1/d and the distance marched are dead (trace_setup sets both) — so the kernel keeps a hit's colour and emittance
-        // in the registers of 1/d and the distance marched between the block test that hit and SHADE (hit_to_march_registers /
-        // march_registers_to_hit), and a parked path has no word for them.
+        // in the registers of 1/d and the distance marched between the block test that hit and SHADE (block_phase<SHARE> writes them
+        // there, march_registers_to_hit names them for SHADE), and a parked path has no word for them.
         v[4] = make_uint4(__float_as_uint(L.inv.x), __float_as_uint(L.inv.y), __float_as_uint(L.inv.z), __float_as_uint(L.dist_march));
         v[5] = make_uint4(__float_as_uint(L.h.distance), __float_as_uint(L.h.normal.x), __float_as_uint(L.h.normal.y), __float_as_uint(L.h.normal.z));
         return;
@@ -242,13 +242,9 @@ DEV void pool_unpack(LaneState& L, const uint4 (&v)[WORDS]) {
     L.h.emittance = __uint_as_float(v[H + 1].w);
 }
 
-// The six-word record's register sharing (pool_pack): a block test that ended the trace leaves the hit's colour and emittance where
-// 1/d and the distance marched were, SHADE takes them back.  (After a shadow ray's hit, or a trace that ended in the march, what moves
-// is dead on both sides.)
-DEV void hit_to_march_registers(LaneState& L) {
-    L.inv = mk3(L.h.color.x, L.h.color.y, L.h.color.z);
-    L.dist_march = L.h.emittance;
-}
+// The six-word record's register sharing (pool_pack): a block test that ended the trace has left the hit's colour and emittance where
+// 1/d and the distance marched were (path_state.hpp block_phase<SHARE>), SHADE reads them from there.  (After a shadow ray's hit, or a
+// trace that ended in the march, what it finds there is read by nobody.)
 DEV void march_registers_to_hit(LaneState& L) {
     L.h.color = f4{L.inv.x, L.inv.y, L.inv.z, 0.0f};
     L.h.emittance = L.dist_march;
@@ -441,6 +437,11 @@ DEV void march_loop(const SceneView& Sm, const RenderOpts& Om, LaneState& L, Lan
         nm = __popcll(marching);
     } while (nm >= stay);
 }
+
+// Between two phases of the kernel's loop: the phase chosen, as a value the optimiser cannot see through (no instruction) — it cannot
+// tell any more that the phases exclude each other, so it does not merge them back into one chain of alternatives (pool_kernel.inc).
+// The comment it leaves in the compiled kernel says which phase's code ends there (tools/isa_copies.py, tools/isa_scratch.py).
+#define CHUNKY_PHASE_END(X, name) asm volatile("; chunky-mark phase-end " name : "+s"(X))
 
 // The hot kernel, twice (pool_kernel.inc): render_pool for pinhole and pre-generated rays, proj::render_pool for the projected
 // cameras (projector types 1-5).  A compile-time choice, as SORT is: a branch on the projector type inside the kernel would cost

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/isa_scratch.py [-D...] [--kernel MANGLED-SUBSTRING] — where the scratch (spill) instructions of a render_pool instantiation sit.
+"""tools/isa_scratch.py [-D...] [--kernel MANGLED-SUBSTRING] [--asm FILE] — where the scratch (spill) instructions of a render_pool instantiation sit.
 
 Compiles csrc/render_pool.hip for gfx950 with the library's flags (+ any -D given), cuts the instantiation's ISA out of hipcc's
 assembly and attributes every `scratch_` instruction to the phase of the state machine its basic block belongs to.  Phases are
@@ -23,11 +23,19 @@ if "--kernel" in args:
     i = args.index("--kernel")
     kernel = args[i + 1]
     del args[i:i + 2]
+asm = None  # --asm FILE: an assembly file compiled earlier (hipcc --save-temps), instead of compiling
+if "--asm" in args:
+    i = args.index("--asm")
+    asm = args[i + 1]
+    del args[i:i + 2]
 flags = [f for f in native.HIPCC_FLAGS if f != "-shared"] + args
-with tempfile.TemporaryDirectory() as td:
-    subprocess.run(["hipcc", *flags, "-x", "hip", "-c", os.path.join(native.CSRC, "render_pool.hip"), "-o", os.path.join(td, "rp.o"), "--save-temps"],
-                   cwd=td, check=True, capture_output=True)
-    text = open(os.path.join(td, "render_pool-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines()
+if asm:
+    text = open(asm).read().splitlines()
+else:
+  with tempfile.TemporaryDirectory() as td:
+      subprocess.run(["hipcc", *flags, "-x", "hip", "-c", os.path.join(native.CSRC, "render_pool.hip"), "-o", os.path.join(td, "rp.o"), "--save-temps"],
+                     cwd=td, check=True, capture_output=True)
+      text = open(os.path.join(td, "render_pool-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines()
 start = next(i for i, ln in enumerate(text) if ln.startswith("_ZN6chunky") and kernel in ln and ln.rstrip().split(":")[0].endswith("E") and ":" in ln)
 end = next(i for i in range(start, len(text)) if ".end_amdhsa_kernel" in text[i])
 body = text[start:end]
@@ -35,43 +43,22 @@ tail = text[end:end + 60]  # the resource comments follow the kernel descriptor
 meta = {k: next((re.search(r"(\d+)", ln.split(k)[1]).group(1) for ln in tail if k in ln), None)
         for k in ("; NumVgprs:", "; ScratchSize:", "; Occupancy:", "; TotalNumSgprs:", "; codeLenInByte =")}
 
-# phase landmarks -> line ranges.  The kernel's main loop is one big loop; its phases are contiguous regions in program order.
-marks = []
-for i, ln in enumerate(body):
-    if "v_cvt_flr_i32_f32" in ln:
-        marks.append((i, "MARCH"))
-    elif "ds_wrxchg_rtn_b64" in ln:
-        marks.append((i, "SWAP"))
-    elif re.search(r"global_store_dword.* nt", ln) or "global_atomic_add" in ln:
-        marks.append((i, "SHADE"))
-    elif "s_getreg_b32" in ln:
-        marks.append((i, "PROLOGUE"))
-    elif "chunky-mark models-end" in ln:
-        marks.append((i, "MODELS-END"))
-    elif "chunky-mark models" in ln:
-        marks.append((i, "MODELS"))
-# BLOCK: everything between the last SHADE landmark and the first MARCH landmark (program order of the compiled kernel)
-last_shade = max((i for i, p in marks if p == "SHADE"), default=0)
-first_march = min((i for i, p in marks if p == "MARCH"), default=len(body))
-first_swap = min((i for i, p in marks if p == "SWAP"), default=0)
-last_swap = max((i for i, p in marks if p == "SWAP"), default=0)
-# (render_pool.hip leaves a comment where the cube test ends and the model-block tests begin)
-first_models = min((i for i, p in marks if p == "MODELS"), default=None)
-last_models = max((i for i, p in marks if p == "MODELS-END"), default=None)
+# phase landmarks -> line ranges (tools/isa_copies.py phase_function: by the `; chunky-mark phase-end` comments where the kernel has them — the
+# phases as consecutive ifs — else by the landmarks, the phases being contiguous regions in the program order SWAP, SHADE, BLOCK, MARCH)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import isa_copies  # noqa: E402
+
+_mk = isa_copies.landmarks(body)
+first_swap, last_swap = min(_mk["SWAP"], default=0), max(_mk["SWAP"], default=0)
+last_shade, first_march = max(_mk["SHADE"], default=0), min(_mk["MARCH"], default=len(body))
+_header = next((i for i, ln in enumerate(body) if "This Loop Header: Depth=1" in ln), None)
+_phase = isa_copies.phase_function(body, header_line=_header)
+_names = {"PROLOGUE": "PROLOGUE (before the main loop)", "SWAP": "VOTE+SWAP", "MODELS": "MODEL (model blocks)", "SHADE": "SHADE (incl. new samples, trace_setup)",
+          "BLOCK": "BLOCK", "MARCH": "MARCH", "WALK": "WALK (entity BVHs)", "LATCH": "LATCH (census)"}
 
 
 def phase_of(i):
-    if i < first_swap - 250:
-        return "PROLOGUE (before the main loop)"
-    if i <= last_swap + 60:
-        return "VOTE+SWAP"
-    if first_models is not None and first_models - 40 <= i <= last_models + 40:  # (the phase's code may sit anywhere in program order)
-        return "MODEL (model blocks)"
-    if i <= last_shade + 40:
-        return "SHADE (incl. new samples, trace_setup)"
-    if i < first_march - 120:
-        return "BLOCK"
-    return "MARCH"
+    return _names[_phase(i)]
 
 
 label, depth = "(entry)", "0"
