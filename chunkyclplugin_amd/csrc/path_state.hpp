@@ -488,23 +488,40 @@ struct WorkQueue {
 // ~30 % of its VALU issue before this).
 struct WaveArgs {
     SceneView S;
-    CameraView C;
     RenderOpts O;
-    ShardView T;
     PassSeeds P;
-    WorkQueue Q;
     float* res;
     unsigned long long* stats;
     unsigned stack_bytes;  // size of the BVH-stack area at the start of dynamic LDS
+    // From here to the end: what the deposit and the new-sample section of render_pool's SHADE read, as ONE block that starts on a
+    // 64-byte line.  The section reads it whole at its head (sample_args): adjacent words requested in one basic block merge into
+    // wide scalar loads behind one wait.  Read field by field where each is first used, every word was a round trip of its own.
+    alignas(64) CameraView C;
+    ShardView T;
+    WorkQueue Q;
     float* staging;        // render_pool: radiance of every sample of the launch, [tile][pass][slot in tile][3]
     unsigned n_samples;    // render_pool: tiles of kSampleTile pixel slots (the last one padded) x P.n
     unsigned xcd_stripe;   // render_pool: samples per range (xcd_claim): the tiles over kXcdRanges, rounded up, x P.n x kSampleTile
     FastDiv div_sub;       // render_pool: division of a sample index by P.n x kSubBlock (the samples of one sub-block)
     FastDiv div_bw;        // render_pool: division of a tile index by the tiles per image row
     const int* seeds_dev;  // render_pool: the launch's seeds in device memory when it carries more passes than P.seed holds, else null
+    int n_passes;          // render_pool: P.n once more, inside the block
 };
 static_assert(sizeof(WaveArgs) <= 4096, "launch arguments must fit the 4 KB kernel-argument segment");
+static_assert(offsetof(WaveArgs, C) % 64 == 0, "the new-sample block starts on a 64-byte line");
 typedef const WaveArgs __attribute__((address_space(4))) * WaveArgPtr;
+// The ONE place a WaveArgs is built (n_passes repeats P.n inside the new-sample block: nothing else may set either).  The last six
+// arguments are render_pool's; render_waves leaves them at their defaults.
+inline WaveArgs make_wave_args(const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P, int* queue,
+                               float* res, unsigned long long* stats, unsigned stack_bytes, float* staging = nullptr, unsigned n_samples = 0u,
+                               unsigned xcd_stripe = 0u, FastDiv div_sub = FastDiv{0u, 0}, FastDiv div_bw = FastDiv{0u, 0},
+                               const int* seeds_dev = nullptr) {
+    WaveArgs A{};
+    A.S = S, A.O = O, A.P = P, A.res = res, A.stats = stats, A.stack_bytes = stack_bytes;
+    A.C = C, A.T = T, A.Q = WorkQueue{queue}, A.n_passes = P.n;
+    A.staging = staging, A.n_samples = n_samples, A.xcd_stripe = xcd_stripe, A.div_sub = div_sub, A.div_bw = div_bw, A.seeds_dev = seeds_dev;
+    return A;
+}
 
 // copy one member struct out of the argument segment (explicit cast: the host pass has no
 // address-space-qualified copy constructors; on the device the loads stay scalar)
@@ -522,6 +539,55 @@ DEV WaveArgPtr fresh_args() {
     WaveArgPtr a = (WaveArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(a));
     return a;
+}
+
+// A scalar argument word that has to be in its register HERE (no instruction): the optimiser cannot sink the word's load to the basic
+// block of its first use, so the loads of words pinned side by side are issued together and waited for once.
+template <typename V>
+DEV void pin_scalar(V& x) {
+    asm volatile("" : "+s"(x));
+}
+// ... and a pointer word.  Behind the asm the optimiser no longer knows that a pointer out of the argument segment is a global one and
+// would address it as flat (flat_load / flat_atomic: both counters, an aperture test per access): the cast says so again.
+template <typename V>
+DEV V* pin_pointer(V* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    unsigned long long bits = (unsigned long long)p;
+    asm volatile("" : "+s"(bits));
+    return (V*)(V __attribute__((address_space(1)))*)bits;
+#else
+    return p;
+#endif
+}
+// The new-sample block of the argument segment (WaveArgs from C on), read whole.  Everything in it is dead again at the end of the
+// section: nothing stays in scalar registers across a phase boundary.
+struct SampleArgs {
+    CameraView C;
+    ShardView T;
+    int* next;
+    float* staging;
+    unsigned n_samples, xcd_stripe;
+    FastDiv div_sub, div_bw;
+    const int* seeds_dev;
+    int n_passes;
+};
+template <bool PROJ>
+DEV SampleArgs sample_args(WaveArgPtr A) {
+    SampleArgs N{arg_copy(&A->C), arg_copy(&A->T), A->Q.next, A->staging, A->n_samples, A->xcd_stripe, arg_copy(&A->div_sub), arg_copy(&A->div_bw),
+                 A->seeds_dev, A->n_passes};
+    if (!PROJ) N.C.rays = pin_pointer(N.C.rays), pin_scalar(N.C.aperture);  // (the projected cameras read neither)
+    pin_scalar(N.C.projector_type);
+#pragma unroll
+    for (int k = 0; k < 3; k++) pin_scalar(N.C.pos[k]);
+#pragma unroll
+    for (int k = 0; k < 9; k++) pin_scalar(N.C.m[k]);
+    pin_scalar(N.C.subject_distance), pin_scalar(N.C.fov_tan), pin_scalar(N.C.width), pin_scalar(N.C.height);
+    pin_scalar(N.C.half_width), pin_scalar(N.C.inv_height);
+    pin_scalar(N.T.rank), pin_scalar(N.T.world), pin_scalar(N.T.tile), pin_scalar(N.T.n_local), N.T.list = pin_pointer(N.T.list);
+    N.next = pin_pointer(N.next), N.staging = pin_pointer(N.staging), pin_scalar(N.n_samples), pin_scalar(N.xcd_stripe);
+    pin_scalar(N.div_sub.m), pin_scalar(N.div_sub.s), pin_scalar(N.div_bw.m), pin_scalar(N.div_bw.s);
+    N.seeds_dev = pin_pointer(N.seeds_dev), pin_scalar(N.n_passes);
+    return N;
 }
 
 // Cycle sums of parts of SHADE for the profiling build (chunky_render_phase_stats values 14..23).
@@ -551,12 +617,20 @@ DEV int shade_phase(const SceneView& S, const RenderOpts& O, LaneState& L, LdsSt
     const bool hit = BVH ? L.trace_hit : L.oct_hit;  // closestIntersect (K/kernel.h:14-24) is complete
     // Each block below appears once, so a shade round issues it once however the lanes split.
     const bool main_trace = !L.shadow;
+    SkyTexels sky_q;
+    f3 sky_d = mk3(0, 0, 0);
+    float sky_e = 0;
     if (!hit) {  // intersectSky (K/kernel.h:26-31); record.emittance = 1 for the main ray (K/rayTracer.cl:95)
         // a shadow ray's record.emittance is the |dot(sun dir, normal)| stored at its start (K/sky.h:90) and nothing writes it during
         // the trace — nor L.d or the normal: it is evaluated here, from the same operands, instead of being carried through the trace
         // (render_pool's six-word parked record has no place for it while 1/d and the distance marched are alive)
-        const float e = main_trace ? 1.0f : rt_fabs(dot(L.d, L.h.normal));
-        L.radiance = L.radiance + sky_radiance(S, L.d, L.throughput, e);
+        // Only the four texel reads are issued here (sky_fetch); the disc test and the blend follow the sampling block below, which reads
+        // nothing the sky produces and runs while the texels are on their way.  A lane that ends in the sky keeps its throughput and its
+        // radiance through that block (only a main ray's hit changes them), but a shadow ray that missed bounces there and overwrites
+        // L.d: the direction looked up, and e with it, are taken first.
+        sky_e = main_trace ? 1.0f : rt_fabs(dot(L.d, L.h.normal));
+        sky_d = L.d;
+        sky_q = sky_fetch(S, L.d);
     }
     part_end<PROF>(pt, PT_SKY);
     // one exit: a main ray that reached the sky is finished; every other lane goes on below
@@ -619,6 +693,8 @@ DEV int shade_phase(const SceneView& S, const RenderOpts& O, LaneState& L, LdsSt
         }
     }
     part_end<PROF>(pt, PT_SAMPLING);
+    if (!hit) L.radiance = L.radiance + sky_finish(S, sky_q, sky_d, L.throughput, sky_e);
+    part_end<PROF>(pt, PT_SKY);
     return finished ? ST_NEXT : ST_SETUP;
 }
 

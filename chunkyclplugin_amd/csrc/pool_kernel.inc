@@ -248,6 +248,13 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
         CHUNKY_PHASE_END(X, "walk");
         if (X == 2) {
             n_exec = count_lanes(st == ST_SHADE);
+            // Every vector load of the phases before has been waited for on the path that was taken, but not on every path the compiler
+            // sees (a pre-generated ray's two loads are waited for in trace_setup, a block it cannot tell every lane with a new ray enters):
+            // what it still counts as outstanding here it would wait for at the first touch of the register — in the middle of the
+            // sampling block, with SHADE's own sky texels in the queue behind it (vector memory operations retire in order).  One
+            // s_waitcnt vmcnt(0) here resets that.  It is not provably free — the counter also holds stores, such as the staging stores of
+            // the SHADE before — but measured it is a net gain on all four configurations (EXPERIMENTS 7.2: headline +0.5 %).
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), the other counters at their maximum
             WaveArgPtr A = fresh_args();
             const SceneView S = arg_copy(&A->S);
             const RenderOpts O = arg_copy(&A->O);
@@ -258,9 +265,11 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
                 st = EXT ? shade_phase_ext<TREE, BVH>(S, O, L) : shade_phase<TREE, BVH, STATS>(S, O, L, stack, &parts);
             }
             part_begin<STATS>(&parts);
+            // what the deposit and the new-sample section read of the launch arguments: one burst of scalar loads, one wait (path_state.hpp sample_args)
+            const SampleArgs N = sample_args<CHUNKY_POOL_PROJ>(A);
             if (st == ST_NEXT) {  // the path is finished: its radiance waits in the staging array for fold_kernel
                 // streamed past the caches (nt): written once, read once by fold_kernel; the L2 stays with the tree
-                float* __restrict__ out = A->staging + 3 * (size_t)(unsigned)L.sidx;
+                float* __restrict__ out = N.staging + 3 * (size_t)(unsigned)L.sidx;
 #if CHUNKY_STAGING_STORE == 1  // tuning builds (tools/variants.sh): plain stores, merged by the L2 (-2.3 % on the bench)
                 out[0] = L.radiance.x, out[1] = L.radiance.y, out[2] = L.radiance.z;
 #elif CHUNKY_STAGING_STORE == 2  // device-scope stores (sc1): written through the L2
@@ -284,28 +293,27 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
             //      thousand neighbouring pixels — a part of the scene that stays in the 4 MB L2s (pass-major order spread
             //      them over a third of the image: L2 hit rate 91 %, 66 GB of fabric reads per launch instead of 4) ----
             const bool need = fresh;
-            const unsigned sidx = xcd_claim(A->Q.next + kXcdCounters, claim, ranges_tried, need, A->xcd_stripe, A->n_samples);  // convergent
+            const unsigned sidx = xcd_claim(N.next + kXcdCounters, claim, ranges_tried, need, N.xcd_stripe, N.n_samples);  // convergent
             if (need && sidx != kClaimNone) {
-                const unsigned n_samples = A->n_samples;
-                if (sidx >= n_samples) {
+                if (sidx >= N.n_samples) {
                     st = ST_DONE;
                     fresh = false;
                 } else {
-                    const CameraView C = arg_copy(&A->C);
-                    const ShardView T = arg_copy(&A->T);
                     // sidx = ((tile * sub-blocks per tile + sub-block) * passes + pass) * kSubBlock + slot in the sub-block
-                    const unsigned per_sub = (unsigned)A->P.n * (unsigned)kSubBlock;
-                    const unsigned sub = fast_quotient(sidx, arg_copy(&A->div_sub)), rem = sidx - sub * per_sub;  // sub = tile * (kSampleTile / kSubBlock) + sub-block
+                    const unsigned per_sub = (unsigned)N.n_passes * (unsigned)kSubBlock;
+                    const unsigned sub = fast_quotient(sidx, N.div_sub), rem = sidx - sub * per_sub;  // sub = tile * (kSampleTile / kSubBlock) + sub-block
                     const unsigned pass = rem / (unsigned)kSubBlock;
+                    // The pass's seed is requested as soon as the pass is known and waited for where rng is formed: the pixel decode runs under
+                    // the load.  A padding slot (gid outside the image) fetches a seed it discards — the index is inside P.seed / seeds_dev
+                    // for every sample index below n_samples, because pass < P.n.
+                    const unsigned seed = (unsigned)(N.seeds_dev ? N.seeds_dev[pass] : A->P.seed[pass]);  // (seeds_dev is wave-uniform: launches longer than P.seed holds)
                     const int slot = (int)(sub * (unsigned)kSubBlock + (rem & (unsigned)(kSubBlock - 1)));
-                    const SlotPixel px = pool_slot_pixel(T, C.width, C.height, slot, arg_copy(&A->div_bw));
+                    const SlotPixel px = pool_slot_pixel(N.T, N.C.width, N.C.height, slot, N.div_bw);
                     const int gid = px.gid;
-                    if (gid < C.width * C.height) {  // else: a padding slot, nothing to render (the lane claims again)
-                        const int* seeds_dev = A->seeds_dev;  // (wave-uniform: launches longer than P.seed holds)
-                        const unsigned seed = (unsigned)(seeds_dev ? seeds_dev[pass] : A->P.seed[pass]);
+                    if (gid < N.C.width * N.C.height) {  // else: a padding slot, nothing to render (the lane claims again)
                         unsigned rng = seed + (unsigned)gid;
                         rt_pcg_next(&rng);
-                        const RayOD pr = primary_ray<CHUNKY_POOL_PROJ>(C, seed, gid, rng, false, px.x, px.y);
+                        const RayOD pr = primary_ray<CHUNKY_POOL_PROJ>(N.C, seed, gid, rng, false, px.x, px.y);
                         L.sidx = (int)sidx;
                         L.rng = rng;
                         L.o = pr.o;

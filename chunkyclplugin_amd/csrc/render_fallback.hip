@@ -564,7 +564,7 @@ hipError_t launch_fallback(int variant, const SceneView& S, const CameraView& C,
         if (chosen) *chosen = KernelChoice{tree, group, has_bvh ? 1 : 0, grid, -1, 0};
         e = hipMemsetAsync(work_counter, 0, sizeof(int), stream);
         if (e != hipSuccess) return e;
-        WaveArgs A{S, C, O, T, P, WorkQueue{work_counter}, res, (unsigned long long*)(work_counter + 2), (unsigned)stack, nullptr, 0u};
+        const WaveArgs A = make_wave_args(S, C, O, T, P, work_counter, res, (unsigned long long*)(work_counter + 2), (unsigned)stack);
         hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, stream, A);
         return hipGetLastError();
     }

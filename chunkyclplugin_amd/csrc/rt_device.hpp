@@ -608,8 +608,9 @@ DEV void sun_disc(const SceneView& S, f3 d, f4& c) {
 }
 
 // intersectSky — K/kernel.h:26-31: returns color.xyz * throughput * emittance
-DEV f3 sky_radiance(const SceneView& S, f3 d, f3 throughput, float emittance) {
-    const SkyTexels q = sky_fetch(S, d);
+// ... in two halves, so that a caller can put work of its own between the request for the four texels (sky_fetch) and their use
+// (sky_finish: the disc test, then the blend); sky_radiance is the two back to back.
+DEV f3 sky_finish(const SceneView& S, const SkyTexels& q, f3 d, f3 throughput, float emittance) {
     // the disc's texel, fetched while the sky's four are on their way; `in_disc` keeps "+= texel" apart from "no add"
     bool in_disc = false;
     f3 add = mk3(0, 0, 0);
@@ -638,6 +639,10 @@ DEV f3 sky_radiance(const SceneView& S, f3 d, f3 throughput, float emittance) {
         c.z += add.z;
     }
     return (mk3(c.x, c.y, c.z) * throughput) * emittance;
+}
+DEV f3 sky_radiance(const SceneView& S, f3 d, f3 throughput, float emittance) {
+    const SkyTexels q = sky_fetch(S, d);
+    return sky_finish(S, q, d, throughput, emittance);
 }
 
 // Sun_sampleDirection — K/sky.h:68-93 (direction = u * v component-wise, then += w)
