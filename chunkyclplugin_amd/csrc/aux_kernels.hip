@@ -67,6 +67,8 @@ __global__ void __launch_bounds__(256) preview_lanes(SceneView S, CameraView C, 
     argb[gid] = (int)(0xFF000000u | ((unsigned)r << 16) | ((unsigned)g << 8) | (unsigned)b);
 }
 
+constexpr int kSweepFirst = 40, kSweepRecord = 60;
+
 // Device evaluation of the rt_math.h contract, compared bit-for-bit with the host by the tests.
 __global__ void math_selftest_kernel(int which, int n, const float* __restrict__ a, const float* __restrict__ b,
                                      float* __restrict__ out) {
@@ -93,9 +95,54 @@ __global__ void math_selftest_kernel(int which, int n, const float* __restrict__
         case 16: r = rt_pow(x, y); break;
         case 18: r = (float)floor_to_int(x); break;
         case 17: r = (float)((double)x * (double)y); break;
+        // the short exact forms (rt_short_forms.h) and, odd numbers, the compiled IEEE operations they stand for
+        case 20: r = rcp_exact(x); break;
+        case 21: r = 1.0f / x; break;
+        case 22: r = rt_sqrt(x); break;
+        case 23: r = __builtin_sqrtf(x); break;
+        case 24: r = rt_div_const(x, kSkyTwoPi); break;
+        case 25: r = x / kSkyTwoPi; break;
+        case 26: r = rt_div_const(x, kSunDiscWidth2); break;
+        case 27: r = x / kSunDiscWidth2; break;
+        case 28: { const f3 q = rcp3(mk3(x, y, x)); r = (i & 1) ? q.y : q.x; break; }  // (odd rows: 1 / b)
         default: break;
     }
     out[i] = r;
+}
+
+// Sweeps (`which` >= kSweepFirst): a short form against the compiled operation over a run of bit patterns, bits compared (NaNs
+// included).  a[0] holds the first pattern and b[0] the number of patterns per thread, both as bit patterns; thread i takes
+// first + k * n + i for k < count, so that a wave's lanes hold neighbouring patterns, and n * count = 2^32 covers every float once.
+// out (as unsigned, zeroed by the launcher): [0] mismatches, [1] mismatches recorded so far, [2 ..] the first kSweepRecord
+// mismatching patterns that got a slot.  40-43 are the forms the kernels use, 50 a form that must fail.
+template <class NEW, class REF>
+DEV void sweep_patterns(int i, int n, unsigned first, unsigned count, unsigned* out, NEW form, REF ieee) {
+    unsigned bad = 0;
+    for (unsigned k = 0; k < count; ++k) {
+        const unsigned u = first + k * (unsigned)n + (unsigned)i;
+        const float x = __uint_as_float(u);
+        if (__float_as_uint(form(x)) != __float_as_uint(ieee(x))) {
+            ++bad;
+            const unsigned slot = atomicAdd(&out[1], 1u);
+            if (slot < (unsigned)kSweepRecord) out[2 + slot] = u;
+        }
+    }
+    if (bad) atomicAdd(&out[0], bad);
+}
+__global__ void math_sweep_kernel(int which, int n, const float* __restrict__ a, const float* __restrict__ b, unsigned* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned first = __float_as_uint(a[0]), count = __float_as_uint(b[0]);
+    const auto rcp = [](float x) { return 1.0f / x; };
+    const auto root = [](float x) { return __builtin_sqrtf(x); };
+    switch (which) {
+        case 40: sweep_patterns(i, n, first, count, out, [](float x) { return rcp_exact(x); }, rcp); break;
+        case 41: sweep_patterns(i, n, first, count, out, [](float x) { return rt_sqrt(x); }, root); break;
+        case 42: sweep_patterns(i, n, first, count, out, [](float x) { return rt_div_const(x, kSkyTwoPi); }, [](float x) { return x / kSkyTwoPi; }); break;
+        case 43: sweep_patterns(i, n, first, count, out, [](float x) { return rt_div_const(x, kSunDiscWidth2); }, [](float x) { return x / kSunDiscWidth2; }); break;
+        case 50: sweep_patterns(i, n, first, count, out, [](float x) { return rt_rcp_outside(x) ? 1.0f / x : __builtin_amdgcn_rcpf(x); }, rcp); break;  // the control: the bare estimate is NOT 1 / x
+        default: break;
+    }
 }
 
 // Helper-level known answers (chunky_selftest_helpers): the device functions the kernels are made of, one call per input
@@ -312,6 +359,13 @@ hipError_t launch_shard_map_selftest(int mode, const ShardView& T, int width, in
 }
 
 hipError_t launch_math_selftest(int which, int n, const float* a, const float* b, float* out, hipStream_t stream) {
+    if (which >= kSweepFirst) {
+        if (n < kSweepRecord + 2) return hipErrorInvalidValue;  // (out has n words)
+        const hipError_t e = hipMemsetAsync(out, 0, (size_t)n * 4, stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(math_sweep_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, which, n, a, b, (unsigned*)out);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(math_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, which, n, a, b, out);
     return hipGetLastError();
 }

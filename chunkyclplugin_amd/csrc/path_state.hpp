@@ -677,7 +677,7 @@ DEV int shade_phase(const SceneView& S, const RenderOpts& O, LaneState& L, LdsSt
             a = mk3(xy * n.z - xz * n.y, xz * n.x - xx * n.z, xx * n.y - xy * n.x);
             len2 = a.x * a.x + a.y * a.y + a.z * a.z;
         }
-        const float rl = 1 / rt_sqrt(len2);
+        const float rl = rcp_exact(rt_sqrt(len2));
         a = a * rl;
         if (to_sun) {
             L.d = a;
@@ -716,7 +716,7 @@ DEV f3 cosine_direction(f3 n, float x1, float x2) {
     float ux = xy * n.z - xz * n.y;
     float uy = xz * n.x - xx * n.z;
     float uz = xx * n.y - xy * n.x;
-    r = 1 / rt_sqrt(ux * ux + uy * uy + uz * uz);
+    r = rcp_exact(rt_sqrt(ux * ux + uy * uy + uz * uz));
     ux *= r;
     uy *= r;
     uz *= r;

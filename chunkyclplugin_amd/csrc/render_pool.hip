@@ -110,7 +110,7 @@ DEV int shade_phase_ext(const SceneView& S, const RenderOpts& O, LaneState& L) {
             const f3 l = pe - L.o;
             const float d2 = dot(l, l);
             const float dist = rt_sqrt(d2);
-            const f3 dir = l * (1 / dist);
+            const f3 dir = l * rcp_exact(dist);
             const float cs = dot(dir, n), cl = -dot(dir, nf);
             L.after_nee = true;
             if (cs > 0 && cl > 0 && dist > 0.002f) {
@@ -459,6 +459,23 @@ template <int TREE, int K, bool STATS, bool BVH = false, bool EXT = false, bool 
 static void (*pool_kernel(bool projected))(WaveArgs) {
     return projected ? proj::render_pool<TREE, K, STATS, BVH, EXT, SORT> : render_pool<TREE, K, STATS, BVH, EXT, SORT>;
 }
+// The entity-BVH instantiations are compiled in a translation unit of their own, render_pool_bvh.hip: this file again, up to here, with
+// CHUNKY_IEEE_FORMS (rt_short_forms.h) — those kernels keep the compiler's divisions and roots.  `tree` and `park` as launch_pool settled
+// them (tree 17, 18 or -1; with statistics 17 or -1).  This unit instantiates no kernel with BVH = true, that one none with BVH = false.
+typedef void (*PoolKernel)(WaveArgs);
+PoolKernel pool_kernel_bvh(int tree, int park, bool stats, bool ext, bool proj);
+#ifdef CHUNKY_POOL_BVH_TU
+PoolKernel pool_kernel_bvh(int tree, int park, bool stats, bool ext, bool proj) {
+    if (ext) return tree == 17 ? pool_kernel<17, 16, false, true, true>(proj) : (tree == 18 ? pool_kernel<18, 16, false, true, true>(proj) : pool_kernel<-1, 16, false, true, true>(proj));
+    if (stats) return tree == 17 ? pool_kernel<17, 16, true, true>(proj) : pool_kernel<-1, 16, true, true>(proj);
+#ifdef CHUNKY_POOL_BVH_PARK  // tuning builds (tools/variants.sh): a fixed pool size for the entity kernel, e.g. 8 parked paths at six waves
+    return tree == 17 ? pool_kernel<17, CHUNKY_POOL_BVH_PARK, false, true>(proj) : pool_kernel<-1, CHUNKY_POOL_BVH_PARK, false, true>(proj);
+#endif
+    if (park == 32) return tree == 17 ? pool_kernel<17, 32, false, true>(proj) : (tree == 18 ? pool_kernel<18, 32, false, true>(proj) : pool_kernel<-1, 32, false, true>(proj));
+    return tree == 17 ? pool_kernel<17, 16, false, true>(proj) : (tree == 18 ? pool_kernel<18, 16, false, true>(proj) : pool_kernel<-1, 16, false, true>(proj));
+}
+}  // namespace chunky
+#else
 
 // The running mean of K/rayTracer.cl:109-112 over the staged samples of a launch, strictly in pass order: one thread per
 // pixel and channel, reads coalesced across pixels ([pass][slot][3]).
@@ -536,8 +553,7 @@ static hipError_t launch_pool(int variant, const SceneView& S, const CameraView&
         case 2: park = 32; break;
         default: break;
     }
-    typedef void (*Kernel)(WaveArgs);
-    Kernel k;
+    PoolKernel k;
     const bool proj = C.projector_type > 0;  // a projected camera: proj::render_pool, same template arguments
     const bool ext = opts_extended(O);  // EXPERIMENTAL light-transport options: their own instantiations
     // Block tests sorted by kind (full cubes / model blocks in phases of their own): for scenes in which model blocks are common
@@ -551,7 +567,7 @@ static hipError_t launch_pool(int variant, const SceneView& S, const CameraView&
         words = 9;
         park = bvh ? 16 : 32;
         if (bvh)
-            k = tree == 17 ? pool_kernel<17, 16, false, true, true>(proj) : (tree == 18 ? pool_kernel<18, 16, false, true, true>(proj) : pool_kernel<-1, 16, false, true, true>(proj));
+            k = pool_kernel_bvh(tree, park, false, true, proj);
         else
             k = tree == 17 ? pool_kernel<17, 32, false, false, true>(proj) : (tree == 18 ? pool_kernel<18, 32, false, false, true>(proj) : pool_kernel<-1, 32, false, false, true>(proj));
     } else if (bvh) {
@@ -561,17 +577,15 @@ static hipError_t launch_pool(int variant, const SceneView& S, const CameraView&
         if (stats) {
             if (tree != 17) tree = -1;
             park = 16;
-            k = tree == 17 ? pool_kernel<17, 16, true, true>(proj) : pool_kernel<-1, 16, true, true>(proj);
+            k = pool_kernel_bvh(tree, park, true, false, proj);
 #ifdef CHUNKY_POOL_BVH_PARK  // tuning builds (tools/variants.sh): a fixed pool size for the entity kernel, e.g. 8 parked paths at six waves
         } else if (true) {
             if (tree != 17) tree = -1;
             park = CHUNKY_POOL_BVH_PARK;
-            k = tree == 17 ? pool_kernel<17, CHUNKY_POOL_BVH_PARK, false, true>(proj) : pool_kernel<-1, CHUNKY_POOL_BVH_PARK, false, true>(proj);
+            k = pool_kernel_bvh(tree, park, false, false, proj);
 #endif
-        } else if (park == 32) {
-            k = tree == 17 ? pool_kernel<17, 32, false, true>(proj) : (tree == 18 ? pool_kernel<18, 32, false, true>(proj) : pool_kernel<-1, 32, false, true>(proj));
         } else {
-            k = tree == 17 ? pool_kernel<17, 16, false, true>(proj) : (tree == 18 ? pool_kernel<18, 16, false, true>(proj) : pool_kernel<-1, 16, false, true>(proj));
+            k = pool_kernel_bvh(tree, park, false, false, proj);
         }
     } else if (stats) {
         if (tree != 17) tree = -1;
@@ -686,3 +700,4 @@ hipError_t launch_clear_foreign(const ShardView& T, int width, int height, float
 }
 
 }  // namespace chunky
+#endif  // CHUNKY_POOL_BVH_TU

@@ -39,7 +39,12 @@ DEV f3 cross(f3 a, f3 b) {
     return f3{rt_cross_c(a.y, b.z, a.z, b.y), rt_cross_c(a.z, b.x, a.x, b.z), rt_cross_c(a.x, b.y, a.y, b.x)};
 }
 DEV f3 normalize(f3 a) { return a * rt_rlen3(a.x, a.y, a.z); }
-DEV f3 rcp3(f3 a) { return f3{1.0f / a.x, 1.0f / a.y, 1.0f / a.z}; }
+// 1 / a per component, bit for bit: the short exact form with one range test for the three (rt_short_forms.h)
+DEV f3 rcp3(f3 a) {
+    f3 r;
+    rcp_exact3(a.x, a.y, a.z, &r.x, &r.y, &r.z);
+    return r;
+}
 DEV float as_float(int i) { return __int_as_float(i); }
 
 // ---------------------------------------------------------------------------------------------
@@ -563,9 +568,13 @@ struct SkyTexels {
     float4 t00, t10, t01, t11;
     float a, b;
 };
+// the two constants device code divides by at run time: sky_fetch's 2 pi and the sun disc's width2 (K/sky.h:42-66: radius 0.03, width = 4 radius).
+// Defined once: the kernels divide by them with rt_div_const, and math_selftest_kernel sweeps rt_div_const over these two (which 42, 43).
+constexpr float kSkyTwoPi = RT_PI_F * 2;
+constexpr float kSunDiscRadius = 0.03f, kSunDiscWidth = kSunDiscRadius * 4, kSunDiscWidth2 = kSunDiscWidth * 2;
 DEV SkyTexels sky_fetch(const SceneView& S, f3 d) {
     float theta = rt_atan2(d.z, d.x);
-    theta = theta / (RT_PI_F * 2);
+    theta = rt_div_const(theta, kSkyTwoPi);
     theta = rt_fmod1(rt_fmod1(theta) + 1);
     float phi = (rt_asin(rt_clamp(d.y, -1.0f, 1.0f)) + RT_PI_2_F) * RT_1_PI_F;
     int i0, i1, j0, j1;
@@ -592,14 +601,12 @@ DEV f4 sky_color(const SceneView& S, f3 d) { return sky_blend(S, sky_fetch(S, d)
 // Sun_intersect — K/sky.h:42-66: adds the sun-disc texel (x intensity) to c
 DEV void sun_disc(const SceneView& S, f3 d, f4& c) {
     if (!(S.sun_flags & 1) || dot(d, S.sw) < 0.5f) return;  // (c + 0 would turn a -0 channel into +0)
-    const float radius = 0.03f;
-    const float width = radius * 4;
-    const float width2 = width * 2;
+    const float width = kSunDiscWidth, width2 = kSunDiscWidth2;
     float a = RT_PI_2_F - rt_acos(dot(d, S.su)) + width;
     if (a >= 0 && a < width2) {
         float b = RT_PI_2_F - rt_acos(dot(d, S.sv)) + width;
         if (b >= 0 && b < width2) {
-            f4 t = unpack_unorm8(atlas_texel(S, a / width2, b / width2, S.sun_tex, S.sun_tex_size));
+            f4 t = unpack_unorm8(atlas_texel(S, rt_div_const(a, width2), rt_div_const(b, width2), S.sun_tex, S.sun_tex_size));
             c.x += t.x * S.sun_intensity;
             c.y += t.y * S.sun_intensity;
             c.z += t.z * S.sun_intensity;
@@ -619,14 +626,12 @@ DEV f3 sky_finish(const SceneView& S, const SkyTexels& q, f3 d, f3 throughput, f
     // ran whenever ANY lane of a SHADE execution looked within 60 degrees of the sun); the outcome of no lane changes.
     const float xu = dot(d, S.su);
     if ((S.sun_flags & 1) && !(dot(d, S.sw) < 0.5f) && rt_fabs(xu) <= 0.125f) {
-        const float radius = 0.03f;
-        const float width = radius * 4;
-        const float width2 = width * 2;
+        const float width = kSunDiscWidth, width2 = kSunDiscWidth2;
         float a = RT_PI_2_F - rt_acos(xu) + width;
         if (a >= 0 && a < width2) {
             float b = RT_PI_2_F - rt_acos(dot(d, S.sv)) + width;
             if (b >= 0 && b < width2) {
-                f4 t = unpack_unorm8(atlas_texel(S, a / width2, b / width2, S.sun_tex, S.sun_tex_size));
+                f4 t = unpack_unorm8(atlas_texel(S, rt_div_const(a, width2), rt_div_const(b, width2), S.sun_tex, S.sun_tex_size));
                 add = mk3(t.x * S.sun_intensity, t.y * S.sun_intensity, t.z * S.sun_intensity);
                 in_disc = true;
             }
@@ -678,7 +683,7 @@ DEV f3 diffuse_bounce(f3 n, unsigned& rng) {
     float ux = xy * n.z - xz * n.y;
     float uy = xz * n.x - xx * n.z;
     float uz = xx * n.y - xy * n.x;
-    r = 1 / rt_sqrt(ux * ux + uy * uy + uz * uz);
+    r = rcp_exact(rt_sqrt(ux * ux + uy * uy + uz * uz));
     ux *= r;
     uy *= r;
     uz *= r;

@@ -36,7 +36,15 @@ RT_FN float rt_u2f(unsigned u) { float f; __builtin_memcpy(&f, &u, 4); return f;
 
 RT_FN float rt_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 RT_FN float rt_fabs(float x) { return __builtin_fabsf(x); }
+/* (device code takes a shorter form that a sweep over all 2^32 patterns holds equal to the builtin: rt_short_forms.h) */
+#if defined(__HIPCC__)
+#include "rt_short_forms.h"
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+RT_FN float rt_sqrt(float x) { return rt_sqrt_short(x); }
+#else
 RT_FN float rt_sqrt(float x) { return __builtin_sqrtf(x); }
+#endif
 RT_FN float rt_floor(float x) { return __builtin_floorf(x); }
 RT_FN float rt_trunc(float x) { return __builtin_truncf(x); }
 RT_FN float rt_rint(float x) { return __builtin_rintf(x); }
@@ -78,7 +86,11 @@ RT_FN float rt_dot3(float ax, float ay, float az, float bx, float by, float bz) 
 /* one component of a cross product: a*b - c*d */
 RT_FN float rt_cross_c(float a, float b, float c, float d) { return rt_fma(a, b, -(c * d)); }
 /* 1/|v| used by normalize: v * rt_rlen3(v) */
+#if defined(__HIP_DEVICE_COMPILE__)
+RT_FN float rt_rlen3(float x, float y, float z) { return rcp_exact(rt_sqrt(rt_dot3(x, y, z, x, y, z))); }
+#else
 RT_FN float rt_rlen3(float x, float y, float z) { return 1.0f / rt_sqrt(rt_dot3(x, y, z, x, y, z)); }
+#endif
 
 /* fmod(x, 1.0f): exact (x - trunc(x) is representable), sign of x kept like C fmod. */
 RT_FN float rt_fmod1(float x) {

@@ -18,7 +18,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("CHUNKY_HIP_LIB") or os.path.join(PKG_DIR, "libchunky_hip.so")  # override: tuning builds (tools/variants.sh)
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
-SOURCES = ["render_pool.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "denoise.hip", "adaptive.hip",
+SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "denoise.hip", "adaptive.hip",
            "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_adaptive.hip", "capi_denoise.hip",
            "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "adaptive_host.cpp", "denoise_host.cpp",
            "scene_records.cpp", "widetree.cpp"]

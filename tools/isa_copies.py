@@ -304,10 +304,12 @@ def compile_kernel(kernel, extra):
     sys.path.insert(0, root)
     from chunkyclplugin_amd import native
     flags = [f for f in native.HIPCC_FLAGS if f != "-shared"] + extra
+    # (the entity-BVH instantiations — the fourth template argument true — are compiled in render_pool_bvh.hip)
+    unit = "render_pool_bvh" if re.search(r"render_poolILi\w+ELi\w+ELb[01]ELb1E", kernel) else "render_pool"
     with tempfile.TemporaryDirectory() as td:
-        subprocess.run(["hipcc", *flags, "-x", "hip", "-c", os.path.join(native.CSRC, "render_pool.hip"), "-o", os.path.join(td, "rp.o"), "--save-temps"],
+        subprocess.run(["hipcc", *flags, "-x", "hip", "-c", os.path.join(native.CSRC, unit + ".hip"), "-o", os.path.join(td, "rp.o"), "--save-temps"],
                        cwd=td, check=True, capture_output=True)
-        text = open(os.path.join(td, "render_pool-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines()
+        text = open(os.path.join(td, unit + "-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines()
     return cut_kernel(text, kernel)
 
 
