@@ -57,7 +57,7 @@ DEV AovArgPtr aov_args() {
 }
 
 // Five waves per SIMD (at most 96 VGPRs) without the BVH walk; with it, four (at five it would spill to scratch).  PROJ: a projected
-// camera (projector types 1-5, rt_device.hpp projected_ray), instantiated apart so that the other cameras keep their code.
+// camera (projector types 1-5, 7, 8, rt_device.hpp projected_ray), instantiated apart so that the other cameras keep their code.
 template <int TREE, bool BVH, bool PROJ = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BVH ? 4 : 5))) aov_kernel(AovArgs) {
     extern __shared__ int lds[];

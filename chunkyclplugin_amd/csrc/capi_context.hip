@@ -5,6 +5,7 @@
 // 0.5: chunky_group_transport / chunky_group_set_transport (the group's read-back exchange through RCCL, bound at run time)
 // 0.6: albedo and normal images for denoisers: chunky_render_aov_passes / _read / _reset / _kernel_time / _kernel_info
 //      also: projected cameras (CHUNKY_PROJ_PARALLEL .. CHUNKY_PROJ_STEREOGRAPHIC), chunky_camera_rays, chunky_selftest_camera_rays
+//      also: their lens and the ODS types: chunky_render_set_lens, chunky_camera_rays_lens, CHUNKY_PROJ_ODS, CHUNKY_PROJ_ODS_STACKED
 //      also: the À-Trous denoiser: chunky_denoise_default_params / _host / _frame / _exp, chunky_render_denoise / _denoise_kernel_time
 //      (additions only, so the version string stays "0.6": hosts that check it for the AOV calls keep working)
 extern "C" const char* chunky_version(void) { return "chunky-hip 0.6 gfx950"; }

@@ -19,38 +19,60 @@ int check_ints(const int32_t* p, int64_t n, const char* what) {
     return CHUNKY_OK;
 }
 
-// projected cameras (types 1-5, camera_proj.h): 15 floats laid out as the pinhole camera's, all finite, no aperture (depth of field
-// stays pinhole-only), settings[14] > 0, and settings[13] = 0 where the type has no use for it
+// projected cameras (types 1-5, 7, 8, camera_proj.h): 15 floats laid out as the pinhole camera's, all finite, settings[12] = 0 (the
+// lens has a call of its own, chunky_render_set_lens), settings[14] > 0, settings[13] = 0 where the type has no use for it; the
+// stacked ODS image has an eye offset >= 0 and an even height
 static_assert(RT_PROJ_PARALLEL == CHUNKY_PROJ_PARALLEL && RT_PROJ_FISHEYE == CHUNKY_PROJ_FISHEYE && RT_PROJ_PANORAMIC == CHUNKY_PROJ_PANORAMIC &&
-                  RT_PROJ_PANORAMIC_SLOT == CHUNKY_PROJ_PANORAMIC_SLOT && RT_PROJ_STEREOGRAPHIC == CHUNKY_PROJ_STEREOGRAPHIC, "camera_proj.h");
-int check_projected(const char* who, int type, const float* s, int64_t n) {
-    if (type < CHUNKY_PROJ_PARALLEL || type > CHUNKY_PROJ_STEREOGRAPHIC)
-        return fail(CHUNKY_E_INVALID, "%s: projector type %d is not a projected camera (1-5)", who, type);
+                  RT_PROJ_PANORAMIC_SLOT == CHUNKY_PROJ_PANORAMIC_SLOT && RT_PROJ_STEREOGRAPHIC == CHUNKY_PROJ_STEREOGRAPHIC &&
+                  RT_PROJ_ODS == CHUNKY_PROJ_ODS && RT_PROJ_ODS_STACKED == CHUNKY_PROJ_ODS_STACKED, "camera_proj.h");
+bool is_projected_type(int type) {
+    return (type >= CHUNKY_PROJ_PARALLEL && type <= CHUNKY_PROJ_STEREOGRAPHIC) || type == CHUNKY_PROJ_ODS || type == CHUNKY_PROJ_ODS_STACKED;
+}
+int check_projected(const char* who, int type, const float* s, int64_t n, int height) {
+    if (!is_projected_type(type))
+        return fail(CHUNKY_E_INVALID, "%s: projector type %d is not a projected camera (1-5, 7, 8)", who, type);
     if (!s) return fail(CHUNKY_E_INVALID, "%s: NULL settings", who);
     if (n != 15) return fail(CHUNKY_E_INVALID, "%s: projector type %d needs 15 floats, got %lld", who, type, (long long)n);
     for (int i = 0; i < 15; i++)
         if (!std::isfinite(s[i])) return fail(CHUNKY_E_INVALID, "%s: settings[%d] is not finite", who, i);
-    if (s[12] != 0.0f) return fail(CHUNKY_E_INVALID, "%s: projector type %d takes no aperture (depth of field is pinhole-only)", who, type);
+    if (s[12] != 0.0f) return fail(CHUNKY_E_INVALID, "%s: settings[12] must be 0 for projector type %d (its lens is set by chunky_render_set_lens)", who, type);
     if (!(s[14] > 0.0f)) return fail(CHUNKY_E_INVALID, "%s: settings[14] must be > 0, got %g", who, (double)s[14]);
     if (s[13] != 0.0f && (type == CHUNKY_PROJ_FISHEYE || type == CHUNKY_PROJ_PANORAMIC || type == CHUNKY_PROJ_STEREOGRAPHIC))
         return fail(CHUNKY_E_INVALID, "%s: settings[13] must be 0 for projector type %d", who, type);
+    if (type == CHUNKY_PROJ_ODS_STACKED) {
+        if (s[13] < 0.0f) return fail(CHUNKY_E_INVALID, "%s: the stacked ODS image needs an eye offset >= 0, got %g", who, (double)s[13]);
+        if (height % 2 != 0) return fail(CHUNKY_E_INVALID, "%s: the stacked ODS image needs an even height, got %d", who, height);
+    }
+    return CHUNKY_OK;
+}
+// the lens of a projected camera: finite, aperture >= 0, focus > 0 where there is an aperture
+int check_lens(const char* who, float aperture, float focus) {
+    if (!std::isfinite(aperture) || !std::isfinite(focus)) return fail(CHUNKY_E_INVALID, "%s: aperture and focus must be finite", who);
+    if (aperture < 0.0f) return fail(CHUNKY_E_INVALID, "%s: aperture must be >= 0, got %g", who, (double)aperture);
+    if (aperture > 0.0f && !(focus > 0.0f)) return fail(CHUNKY_E_INVALID, "%s: focus must be > 0 with an aperture, got %g", who, (double)focus);
     return CHUNKY_OK;
 }
 
-extern "C" int chunky_camera_rays(int projector_type, const float* settings, int64_t n_floats, int width, int height, int32_t seed, float* out) {
-    if (int rc = check_projected("camera_rays", projector_type, settings, n_floats)) return rc;
+extern "C" int chunky_camera_rays_lens(int projector_type, const float* settings, int64_t n_floats, int width, int height, int32_t seed,
+                                       float aperture, float focus, float* out) {
+    if (int rc = check_projected("camera_rays", projector_type, settings, n_floats, height)) return rc;
+    if (int rc = check_lens("camera_rays", aperture, focus)) return rc;
     if (width <= 0 || height <= 0 || (int64_t)width * height > INT32_MAX / 6)
         return fail(CHUNKY_E_INVALID, "camera_rays: bad size %dx%d", width, height);
     if (!out) return fail(CHUNKY_E_INVALID, "camera_rays: NULL output");
     const float half_width = (float)(width / (2.0 * height)), inv_height = (float)(1.0 / height);  // as set_camera
     for (int gid = 0; gid < width * height; gid++) {
         const RtRay r = rt_projected_ray(projector_type, settings, settings + 3, settings[13], settings[14], half_width, inv_height,
-                                         gid % width, gid / width, (unsigned)seed, gid);
+                                         height, aperture, focus, gid % width, gid / width, (unsigned)seed, gid);
         float* o = out + 6 * (size_t)gid;
         o[0] = r.ox; o[1] = r.oy; o[2] = r.oz;
         o[3] = r.dx; o[4] = r.dy; o[5] = r.dz;
     }
     return CHUNKY_OK;
+}
+
+extern "C" int chunky_camera_rays(int projector_type, const float* settings, int64_t n_floats, int width, int height, int32_t seed, float* out) {
+    return chunky_camera_rays_lens(projector_type, settings, n_floats, width, height, seed, 0.0f, 0.0f, out);
 }
 
 extern "C" int chunky_java_random_ints(int64_t seed, int32_t* out, int n) {

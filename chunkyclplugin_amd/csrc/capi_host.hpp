@@ -15,6 +15,8 @@ struct JavaRandom {  // java.util.Random: 48-bit LCG, nextInt() = top 32 bits
 
 #pragma GCC visibility push(hidden)
 int check_ints(const int32_t* p, int64_t n, const char* what);
-int check_projected(const char* who, int type, const float* s, int64_t n);
+bool is_projected_type(int type);
+int check_projected(const char* who, int type, const float* s, int64_t n, int height);
+int check_lens(const char* who, float aperture, float focus);
 const float* gamma_thresholds();
 #pragma GCC visibility pop

@@ -120,20 +120,34 @@ extern "C" int chunky_render_set_camera(chunky_render* r, int projector_type, co
         r->ad_resumable = false;  // (before the table changes: an upload that fails half way has changed it too)
         HIP_TRY(r->rays.upload(settings, (size_t)n * 4, r->ctx->stream));
         c.rays = (const float*)r->rays.p;
-    } else if (projector_type >= CHUNKY_PROJ_PARALLEL && projector_type <= CHUNKY_PROJ_STEREOGRAPHIC) {
-        if (int rc = check_projected("set_camera", projector_type, settings, n)) return rc;
+    } else if (is_projected_type(projector_type)) {
+        if (int rc = check_projected("set_camera", projector_type, settings, n, r->height)) return rc;
         memcpy(c.pos, settings, 12);
         memcpy(c.m, settings + 3, 36);
-        c.aperture = 0.0f;
+        c.aperture = 0.0f;  // no lens until chunky_render_set_lens
         c.subject_distance = settings[13];  // (CameraView: settings[13] / [14] of a projected camera)
         c.fov_tan = settings[14];
         c.rays = nullptr;
     } else {
-        return fail(CHUNKY_E_INVALID, "set_camera: projector type %d is not supported (-1 to 5)", projector_type);
+        return fail(CHUNKY_E_INVALID, "set_camera: projector type %d is not supported (-1 to 5, 7, 8)", projector_type);
     }
+    c.lens_focus = 0.0f;
     c.projector_type = projector_type;
     r->have_camera = true;
     r->ad_resumable = false;  // what a pass renders changes: an adaptive run cannot continue across it
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_set_lens(chunky_render* r, float aperture, float focus) {
+    FAN_RENDER(r, chunky_render_set_lens(m_, aperture, focus));
+    LOCK_RENDER(r);
+    if (!r->have_camera) return fail(CHUNKY_E_STATE, "set_lens before set_camera");
+    if (r->cam.projector_type <= 0)
+        return fail(CHUNKY_E_STATE, "set_lens: projector type %d has its own aperture or table; the lens is for the projected cameras", r->cam.projector_type);
+    if (int rc = check_lens("set_lens", aperture, focus)) return rc;
+    r->cam.aperture = aperture;
+    r->cam.lens_focus = aperture > 0.0f ? focus : 0.0f;
+    r->ad_resumable = false;  // what a pass renders changes
     return CHUNKY_OK;
 }
 

@@ -224,6 +224,9 @@ JNIEXPORT void JNICALL J(renderSetCamera)(JNIEnv* env, jclass, jlong r, jint typ
     env->ReleaseFloatArrayElements(settings, p, JNI_ABORT);
     CHECK(rc);
 }
+JNIEXPORT void JNICALL J(renderSetLens)(JNIEnv* env, jclass, jlong r, jfloat aperture, jfloat focus) {
+    CHECK(chunky_render_set_lens((chunky_render*)r, aperture, focus));
+}
 JNIEXPORT void JNICALL J(renderPasses)(JNIEnv* env, jclass, jlong r, jintArray seeds, jint first) {
     if (bad_length(env, seeds, 0, "renderPasses")) return;
     Ints d(env, seeds);

@@ -575,7 +575,8 @@ template <bool PROJ>
 DEV SampleArgs sample_args(WaveArgPtr A) {
     SampleArgs N{arg_copy(&A->C), arg_copy(&A->T), A->Q.next, A->staging, A->n_samples, A->xcd_stripe, arg_copy(&A->div_sub), arg_copy(&A->div_bw),
                  A->seeds_dev, A->n_passes};
-    if (!PROJ) N.C.rays = pin_pointer(N.C.rays), pin_scalar(N.C.aperture);  // (the projected cameras read neither)
+    if (!PROJ) N.C.rays = pin_pointer(N.C.rays), pin_scalar(N.C.aperture);  // (the projected cameras read no table)
+    else pin_scalar(N.C.aperture), pin_scalar(N.C.lens_focus);              // (their lens: chunky_render_set_lens)
     pin_scalar(N.C.projector_type);
 #pragma unroll
     for (int k = 0; k < 3; k++) pin_scalar(N.C.pos[k]);

@@ -444,7 +444,7 @@ DEV void march_loop(const SceneView& Sm, const RenderOpts& Om, LaneState& L, Lan
 #define CHUNKY_PHASE_END(X, name) asm volatile("; chunky-mark phase-end " name : "+s"(X))
 
 // The hot kernel, twice (pool_kernel.inc): render_pool for pinhole and pre-generated rays, proj::render_pool for the projected
-// cameras (projector types 1-5).  A compile-time choice, as SORT is: a branch on the projector type inside the kernel would cost
+// cameras (projector types 1-5, 7, 8).  A compile-time choice, as SORT is: a branch on the projector type inside the kernel would cost
 // the pinhole path registers it does not have.
 #define CHUNKY_POOL_PROJ false
 #include "pool_kernel.inc"

@@ -113,11 +113,12 @@ struct SceneView {
 
 struct CameraView {
     const float* __restrict__ rays;  // projector -1: W*H*6 floats (K/camera.h:8-11)
-    int projector_type;              // 0 pinhole, -1 pre-generated, 1-5 projected (camera_proj.h)
+    int projector_type;              // 0 pinhole, -1 pre-generated, 1-5, 7, 8 projected (camera_proj.h)
     float pos[3], m[9];              // ClCamera.java:42-52
-    float aperture, subject_distance, fov_tan;  // settings[12..14] (projected types: 0, settings[13], settings[14])
+    float aperture, subject_distance, fov_tan;  // settings[12..14] (projected types: the lens's aperture, settings[13], settings[14])
     int width, height;
     float half_width, inv_height;    // K/rayTracer.cl:66-67 (double sites, rounded once on the host)
+    float lens_focus;                // projected types: the lens's focus distance (chunky_render_set_lens); nothing else reads it
 };
 
 struct RenderOpts {
@@ -738,12 +739,13 @@ DEV RayOD primary_ray(const CameraView& C, int gid, unsigned& rng, bool unit_dir
     return RayOD{mk3(ox, oy, oz), mk3(dx, dy, dz)};
 }
 
-// Projected cameras (projector types 1-5, camera_proj.h): the ray from the pass seed's own jitter stream.
+// Projected cameras (projector types 1-5, 7, 8, camera_proj.h): the ray from the pass seed's own jitter stream.
 // It draws nothing from the path's state and does not take the preview's extra normalize (the projection normalises already,
-// and the reference preview does not normalise pre-generated rays).  settings[13] / [14] travel in subject_distance / fov_tan.
+// and the reference preview does not normalise pre-generated rays).  settings[13] / [14] travel in subject_distance / fov_tan, the
+// lens (a uniform branch on aperture > 0) in aperture / lens_focus.
 DEV RayOD projected_ray(const CameraView& C, unsigned seed, int gid, int px, int py) {
-    const RtRay r = rt_projected_ray(C.projector_type, C.pos, C.m, C.subject_distance, C.fov_tan, C.half_width, C.inv_height, px, py,
-                                     seed, gid);
+    const RtRay r = rt_projected_ray(C.projector_type, C.pos, C.m, C.subject_distance, C.fov_tan, C.half_width, C.inv_height, C.height,
+                                     C.aperture, C.lens_focus, px, py, seed, gid);
     return RayOD{mk3(r.ox, r.oy, r.oz), mk3(r.dx, r.dy, r.dz)};
 }
 // PROJ: a compile-time choice of the kernels whose registers are budgeted (render_pool, aov_kernel): their pinhole / pre-generated

@@ -40,6 +40,7 @@ DENOISE_KERNEL_SHIFT = 8  # ... bits 8-9: 0 the default kernels (the images as t
 DENOISE_KERNEL_GATHER, DENOISE_KERNEL_PACKED = 0, 1
 PROJ_PREGENERATED, PROJ_PINHOLE = -1, 0  # chunky_render_set_camera: the reference's two projector types
 PROJ_PARALLEL, PROJ_FISHEYE, PROJ_PANORAMIC, PROJ_PANORAMIC_SLOT, PROJ_STEREOGRAPHIC = 1, 2, 3, 4, 5  # CHUNKY_PROJ_* (projected cameras)
+PROJ_ODS, PROJ_ODS_STACKED = 7, 8  # omnidirectional stereo: one eye, both eyes stacked (6 is unassigned)
 
 
 class ChunkyHipError(RuntimeError):
@@ -204,6 +205,7 @@ def lib() -> C.CDLL:
             "chunky_render_create": [vp, vp, C.c_int, C.c_int, C.POINTER(vp)],
             "chunky_render_destroy": [vp],
             "chunky_render_set_camera": [vp, C.c_int, vp, i64],
+            "chunky_render_set_lens": [vp, f32, f32],
             "chunky_render_set_option": [vp, C.c_int, i32],
             "chunky_render_set_shard": [vp, C.c_int, C.c_int, C.c_int],
             "chunky_render_set_device_buffer": [vp, vp],
@@ -252,6 +254,7 @@ def lib() -> C.CDLL:
             "chunky_selftest_camera_rays": [vp, i32, vp, i64],
             "chunky_selftest_shard_map": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp],
             "chunky_camera_rays": [C.c_int, vp, i64, C.c_int, C.c_int, i32, vp],
+            "chunky_camera_rays_lens": [C.c_int, vp, i64, C.c_int, C.c_int, i32, f32, f32, vp],
             "chunky_filter_frame": [vp, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int],
             "chunky_filter_gamma_thresholds": [vp],
             "chunky_filter_frame_device": [vp, i64, f32, vp, vp, C.c_int, C.c_int, C.POINTER(f32)],
@@ -282,12 +285,17 @@ def java_random_ints(n: int, seed: int = 0) -> np.ndarray:
     return out
 
 
-def camera_rays(projector_type: int, settings, width: int, height: int, seed: int) -> np.ndarray:
+def camera_rays(projector_type: int, settings, width: int, height: int, seed: int, lens=None) -> np.ndarray:
     """chunky_camera_rays: the width*height*6-float table (projector type -1) of a projected camera for the pass of `seed`,
-    computed on the host with the kernels' arithmetic (no device needed)."""
+    computed on the host with the kernels' arithmetic (no device needed).  lens = (aperture, focus): chunky_camera_rays_lens,
+    the table of the camera with that lens (chunky_render_set_lens)."""
     s = np.ascontiguousarray(settings, np.float32)
     out = np.zeros(int(width) * int(height) * 6, np.float32)
-    check(lib().chunky_camera_rays(int(projector_type), ptr(s), s.size, int(width), int(height), int(np.int32(np.uint32(seed & 0xFFFFFFFF))), ptr(out)))
+    seed32 = int(np.int32(np.uint32(seed & 0xFFFFFFFF)))
+    if lens is None:
+        check(lib().chunky_camera_rays(int(projector_type), ptr(s), s.size, int(width), int(height), seed32, ptr(out)))
+    else:
+        check(lib().chunky_camera_rays_lens(int(projector_type), ptr(s), s.size, int(width), int(height), seed32, float(lens[0]), float(lens[1]), ptr(out)))
     return out
 
 

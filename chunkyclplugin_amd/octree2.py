@@ -343,7 +343,8 @@ def camera_settings(cam: dict, origin=(0.0, 0.0, 0.0), world_width: float = 0.0)
     """(projector_type, settings) for chunky_render_set_camera from Chunky's scene JSON camera block.  PINHOLE (or no
     projectionMode) is type 0 with camera_from_json's 15 floats; PARALLEL, FISHEYE, PANORAMIC, PANORAMIC_SLOT and STEREOGRAPHIC
     are the projected types 1-5 (include/chunky_hip.h), which the kernels generate from the pass seed.  Anything else — the ODS
-    modes, or depth of field on a non-pinhole mode — is (-1, None): the host builds a ray table for it as before.  How Chunky's
+    modes, or depth of field on a non-pinhole mode — is (-1, None) HERE, as it always was (callers and a test rely on it):
+    camera_settings_lens below maps those too, to the ODS types and to a lens.  How Chunky's
     fov maps to settings[13] / [14] is this project's reading of its projectors: the parallel view is `fov` world units per unit
     of y, backed off by `world_width`; the fisheye and both panoramas take the fov in degrees; the stereographic scale is
     2 tan(fov / 4), so that the image's top and bottom edges lie fov / 2 off the axis."""
@@ -368,6 +369,37 @@ def camera_settings(cam: dict, origin=(0.0, 0.0, 0.0), world_width: float = 0.0)
     settings = base.copy()
     settings[12], settings[13], settings[14] = 0.0, s13, s14
     return kind, settings
+
+
+# the ODS modes: (projected type, sign of the eye offset); Chunky's eyes are 0.069 world units apart
+ODS_TYPES = {"ODS_LEFT": (7, -1.0), "ODS_RIGHT": (7, 1.0), "ODS_STACKED": (8, 1.0)}
+ODS_EYE_OFFSET = 0.069 / 2.0
+
+
+def camera_settings_lens(cam: dict, origin=(0.0, 0.0, 0.0), world_width: float = 0.0):
+    """(projector_type, settings, lens) from Chunky's scene JSON camera block: camera_settings with the two cases it leaves to the
+    host table mapped as well.  ODS_LEFT / ODS_RIGHT are type 7 (CHUNKY_PROJ_ODS) with eye offset -0.0345 / +0.0345, ODS_STACKED
+    is type 8 with 0.0345, all with a vertical fov of 180 degrees.  `dof` on a non-pinhole mode becomes lens = (aperture, focus)
+    for chunky_render_set_lens, aperture = focalOffset / dof as camera_from_json computes it for the pinhole camera and focus =
+    focalOffset; lens is None where there is none (and for PINHOLE, whose aperture travels in its settings).  A `dof` that gives no
+    lens chunky_render_set_lens would take (a negative or non-finite aperture, focalOffset <= 0) is dropped without a word: lens is
+    None then too, and the caller who needs to know compares cam["dof"] itself.  A mode neither function knows stays (-1, None, None)."""
+    mode = str(cam.get("projectionMode", "PINHOLE")).upper()
+    base = camera_from_json(cam, origin)
+    if mode == "PINHOLE":
+        return 0, base, None
+    aperture, focus = float(base[12]), float(base[13])
+    if mode in ODS_TYPES:
+        kind, sign = ODS_TYPES[mode]
+        settings = base.copy()
+        settings[12], settings[13], settings[14] = 0.0, sign * ODS_EYE_OFFSET, 180.0
+    else:
+        no_dof = {k: v for k, v in cam.items() if k != "dof"}
+        kind, settings = camera_settings(no_dof, origin, world_width)
+        if settings is None:
+            return -1, None, None
+    lens = (aperture, focus) if aperture > 0.0 and math.isfinite(aperture) and focus > 0.0 else None
+    return kind, settings, lens
 
 
 def load_scene(octree2_path: str, json_path: str = None, width: int = 1920, height: int = 1080,

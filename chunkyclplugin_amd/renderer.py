@@ -7,7 +7,7 @@ reference (Java, JOCL)                                 this module (Python, ctyp
 =====================================================  ==========================================
 `RendererInstance.get()` (RendererInstance.java:23)    `RendererInstance.get(device)`
 `ClSceneLoader` getters (ClSceneLoader.java:95-150)     `HipSceneLoader.load_packed(scene)` + getters
-`ClCamera` (ClCamera.java:33-105)                       `HipPathTracingRenderer.set_camera`
+`ClCamera` (ClCamera.java:33-105)                       `HipPathTracingRenderer.set_camera`, `.set_lens`
 `OpenClPathTracingRenderer.render` (:54-191)            `HipPathTracingRenderer.render`
 `OpenClPreviewRenderer.render` (:47-115)                `HipPathTracingRenderer.preview`
 =====================================================  ==========================================
@@ -27,10 +27,11 @@ from . import native
 from .native import check, ptr
 
 
-def camera_rays(projector_type: int, settings, width: int, height: int, seed: int) -> np.ndarray:
-    """The projector type -1 table equivalent to a projected camera (types 1-5) in the pass of `seed`: feeding it to
-    set_camera(-1, ...) renders that pass bit for bit (include/chunky_hip.h chunky_camera_rays).  Host only."""
-    return native.camera_rays(projector_type, settings, width, height, seed)
+def camera_rays(projector_type: int, settings, width: int, height: int, seed: int, lens=None) -> np.ndarray:
+    """The projector type -1 table equivalent to a projected camera (types 1-5, 7, 8) in the pass of `seed`: feeding it to
+    set_camera(-1, ...) renders that pass bit for bit (include/chunky_hip.h chunky_camera_rays).  lens = (aperture, focus): the
+    table of that camera with the lens set_lens(aperture, focus) gives it (chunky_camera_rays_lens).  Host only."""
+    return native.camera_rays(projector_type, settings, width, height, seed, lens)
 
 
 def denoise_frame(instance, width: int, height: int, color, albedo, normal, params=None) -> np.ndarray:
@@ -239,8 +240,13 @@ class HipPathTracingRenderer:
         s = np.ascontiguousarray(settings, np.float32)
         check(native.lib().chunky_render_set_camera(self._h, int(projector_type), ptr(s), s.size))
 
+    def set_lens(self, aperture: float, focus: float) -> None:
+        """chunky_render_set_lens: depth of field for the projected camera set last (types 1-5, 7, 8): a lens disc of radius
+        `aperture` in focus at distance `focus`; aperture 0 switches it off.  set_camera clears the lens."""
+        check(native.lib().chunky_render_set_lens(self._h, float(aperture), float(focus)))
+
     def camera_rays(self, seed: int) -> np.ndarray:
-        """Self test of a projected camera (types 1-5): the rays the render kernels compute for the pass of `seed`, every pixel,
+        """Self test of a projected camera (types 1-5, 7, 8, with its lens if one is set): the rays the render kernels compute for the pass of `seed`, every pixel,
         width*height*6 floats as camera_rays() lays them out."""
         out = np.zeros(self.width * self.height * 6, np.float32)
         check(native.lib().chunky_selftest_camera_rays(self._h, int(np.int32(np.uint32(int(seed) & 0xFFFFFFFF))), ptr(out), out.size))

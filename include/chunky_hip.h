@@ -158,13 +158,15 @@ int chunky_scene_set_sun(chunky_scene* scene, const int32_t sun[6]);
 int chunky_render_create(chunky_ctx* ctx, chunky_scene* scene, int width, int height, chunky_render** out);
 int chunky_render_destroy(chunky_render* r);
 /* ClCamera (ClCamera.java:33-70): projector_type 0 = pinhole with 15 floats; -1 = pre-generated rays,
- * width*height*6 floats (ClCamera.java:72-105); 1-5 = a projected camera (below); any other value is rejected.
+ * width*height*6 floats (ClCamera.java:72-105); 1-5, 7 and 8 = a projected camera (below); any other value (6 is unassigned) is
+ * rejected.
  * Types 0 and -1 are the reference's own; -1 stays the route that reproduces any of Chunky's projectors exactly. */
 int chunky_render_set_camera(chunky_render* r, int projector_type, const float* settings, int64_t n_floats);
 
 /* Projected cameras: the kernels compute the primary ray of every sample from the pass seed, with fresh jitter on every pass; no
  * table is built or uploaded.  15 floats laid out as the pinhole camera's: pos[3], m[9] (rows, ClCamera.java:42-52), then
- * settings[12] = aperture, which must be 0 (depth of field stays pinhole-only: use -1 for it), settings[13] and settings[14]:
+ * settings[12] = aperture, which must be 0 (the depth of field of a projected camera is set by chunky_render_set_lens, below),
+ * settings[13] and settings[14]:
  *
  *   type                         settings[13]                          settings[14]
  *   CHUNKY_PROJ_PARALLEL         origin back-off b (world units)       view scale w (world units per unit of y)
@@ -172,9 +174,16 @@ int chunky_render_set_camera(chunky_render* r, int projector_type, const float* 
  *   CHUNKY_PROJ_PANORAMIC        0                                     fov in degrees
  *   CHUNKY_PROJ_PANORAMIC_SLOT   fovTan (as the host computes it for pinhole)   fov in degrees
  *   CHUNKY_PROJ_STEREOGRAPHIC    0                                     scale k
+ *   CHUNKY_PROJ_ODS              eye offset e (world units), signed:   vertical fov in degrees (180: the full sphere)
+ *                                e > 0 the right eye, e < 0 the left
+ *   CHUNKY_PROJ_ODS_STACKED      eye offset e >= 0                     vertical fov in degrees
  *
- * A non-finite value, settings[14] <= 0, a non-zero aperture, a non-zero settings[13] where it must be 0, or n_floats != 15 is
- * CHUNKY_E_INVALID, and the camera is left as it was.
+ * ODS is omnidirectional stereo: the image's width spans the full turn whatever its aspect, and each column looks from its own
+ * point of the circle of radius |e| about the camera.  ODS_STACKED holds both eyes: rows py < height / 2 are the eye -e (left, on
+ * top), the rest the eye +e; it needs an even height.
+ *
+ * A non-finite value, settings[14] <= 0, a non-zero aperture, a non-zero settings[13] where it must be 0, a negative offset or an
+ * odd image height for ODS_STACKED, or n_floats != 15 is CHUNKY_E_INVALID, and the camera is left as it was.
  *
  * Per sample (pixel gid = y * width + x, the same gid on shards and group members; pass seed s):
  *   j  = ((uint)s ^ 0x9E3779B9u) + (uint)gid             the jitter's own stream: the path's state stays seed + gid advanced once,
@@ -186,7 +195,11 @@ int chunky_render_set_camera(chunky_render* r, int projector_type, const float* 
  *   PANORAMIC       ax = rad(x fov), ay = rad(y fov); d = (cos ay sin ax, sin ay, cos ay cos ax)
  *   PANORAMIC_SLOT  ax = rad(x fov); d = (sin ax, fovTan y, cos ax)
  *   STEREOGRAPHIC   X = k x, Y = k y, r2 = X^2 + Y^2; d = (2X, 2Y, 1 - r2) / (1 + r2)
- * (o = 0 where not given), d normalised, then rotated by m and moved by pos as the pinhole camera's ray.  The exact arithmetic is
+ *   ODS             th = x * (PI_F / (width / (2 height)))   (one float division); y2 = y, eye = e
+ *   ODS_STACKED     th as ODS; py < height / 2: y2 = 2 y + 0.5, eye = -e; else y2 = 2 y - 0.5, eye = e
+ *                   both: ph = rad(y2 fov); d = (cos ph sin th, sin ph, cos ph cos th); o = (eye cos th, 0, -(eye sin th))
+ * (o = 0 where not given), d normalised; then the lens, if one is set (below); then o and d are rotated by m and o moved by pos
+ * as the pinhole camera's ray.  The exact arithmetic is
  * chunkyclplugin_amd/csrc/camera_proj.h.  Chunky's own projector classes were not at hand: these formulas follow them as this
  * project understands them, and they are this project's specification, not Chunky's.
  *
@@ -197,10 +210,42 @@ int chunky_render_set_camera(chunky_render* r, int projector_type, const float* 
 #define CHUNKY_PROJ_PANORAMIC 3
 #define CHUNKY_PROJ_PANORAMIC_SLOT 4
 #define CHUNKY_PROJ_STEREOGRAPHIC 5
+#define CHUNKY_PROJ_ODS 7
+#define CHUNKY_PROJ_ODS_STACKED 8
 /* The width*height*6-float table (origin, direction per pixel, the layout of projector type -1) of projected camera
  * `projector_type` for the pass of seed `seed`, computed on the host with the kernels' arithmetic; needs no device.  Types 0 and
  * -1, and settings set_camera would reject, are CHUNKY_E_INVALID. */
 int chunky_camera_rays(int projector_type, const float* settings, int64_t n_floats, int width, int height, int32_t seed, float* out);
+
+/* The lens (depth of field) of the projected cameras.  chunky_render_set_lens(r, aperture, focus) gives the camera set last a
+ * lens disc of radius `aperture` (world units) in focus at distance `focus`; aperture == 0 switches the lens off.  A successful
+ * chunky_render_set_camera clears the lens, so the lens is set after the camera, every time.
+ *   CHUNKY_E_STATE    before a camera is set, and while the camera is projector type 0 or -1 (which have their own aperture or table)
+ *   CHUNKY_E_INVALID  a non-finite value, aperture < 0, or aperture > 0 with focus <= 0; the lens is left as it was
+ * Like set_camera it reaches every member of a group, and it ends an adaptive run that could have been resumed.
+ *
+ * Per sample, with lo / ld the local origin and the normalised local direction of the projection above, just before the rotation
+ * by m (float, no fused multiply-add, in this order):
+ *   aperture == 0:  nothing is drawn and nothing changes
+ *   otherwise:
+ *     u1 = rand(j); u2 = rand(j)                  draws 3 and 4 of the jitter stream j (the path's own state stays untouched)
+ *     r = sqrt(u1) * aperture
+ *     theta = (float)((double)(u2 * PI_F) * 2.0)  (the pinhole lens's rounding, K/camera.h:24-27)
+ *     rx = cos(theta) * r;  ry = sin(theta) * r
+ *     PARALLEL (a planar lens in the origins' plane local z = -b, in focus on the plane `focus` in front of it; with b = 0 these are
+ *     local z = 0 and local z = focus):
+ *         off = (rx, ry, 0);  t = (0, 0, focus) - off
+ *     every other type (in focus on the sphere of radius focus about lo):
+ *         U = |ld.x| > |ld.y| ? (-ld.z, 0, ld.x) : (0, ld.z, -ld.y);  U = U / |U|;  V = cross(ld, U)
+ *         off = U rx + V ry;  t = ld focus - off
+ *     lo = lo + off;  ld = t / |t|
+ * The equivalence above holds with a lens: the pass is the pass on projector type -1 fed chunky_camera_rays_lens(k, ..., s,
+ * aperture, focus), the host twin of the kernels' arithmetic, which needs no device.  With aperture == 0 it returns
+ * chunky_camera_rays' bytes; it refuses what chunky_camera_rays and chunky_render_set_lens refuse.  As the projections, this lens
+ * is this project's specification, not a transcription of Chunky's ApertureProjector. */
+int chunky_render_set_lens(chunky_render* r, float aperture, float focus);
+int chunky_camera_rays_lens(int projector_type, const float* settings, int64_t n_floats, int width, int height, int32_t seed,
+                            float aperture, float focus, float* out);
 
 typedef enum chunky_option {
     CHUNKY_OPT_DRAW_DEPTH = 0,      /* int, default 256  (K/rayTracer.cl:94) */
@@ -670,8 +715,8 @@ int chunky_selftest_math(chunky_ctx* ctx, int which, int n, const float* a, cons
 int chunky_selftest_helpers(chunky_scene* scene, int which, int tree, int n, const float* in_rows, float* out_rows, int32_t* tree_used);
 
 /* ---- self test of the projected camera: the device function the render kernels use, run over all width*height pixels of the
- * target's camera for `seed`; out receives width*height*6 floats (n_floats must be that), as chunky_camera_rays lays them out.
- * CHUNKY_E_STATE unless the target has a projected camera. */
+ * target's camera for `seed`, with its lens if one is set; out receives width*height*6 floats (n_floats must be that), as
+ * chunky_camera_rays(_lens) lays them out.  CHUNKY_E_STATE unless the target has a projected camera. */
 int chunky_selftest_camera_rays(chunky_render* r, int32_t seed, float* out, int64_t n_floats);
 
 /* ---- self test of the shard-to-pixel map (no reference counterpart): the device functions every image-writing kernel takes its

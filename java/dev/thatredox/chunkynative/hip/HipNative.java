@@ -53,6 +53,9 @@ public final class HipNative {
     public static native long renderCreate(long ctx, long scene, int width, int height);
     public static native void renderDestroy(long render);
     public static native void renderSetCamera(long render, int projectorType, float[] settings);
+    /** chunky_render_set_lens: depth of field for the projected cameras (projector types 1-5, 7, 8); call it after renderSetCamera,
+     *  which clears the lens.  aperture 0 switches it off. */
+    public static native void renderSetLens(long render, float aperture, float focus);
     /** chunky_render_set_option: the render-loop constants of the reference kernel (OPT_DRAW_DEPTH 256, OPT_MAX_DEPTH 5) and
      *  the extensions, all of which default to the reference's behaviour (include/chunky_hip.h). */
     public static native void renderSetOption(long render, int option, int value);
