@@ -10,12 +10,24 @@
 #include "camera_proj.h"
 #include "capi_error.hpp"
 #include "rt_math.h"
+#include "scene_records.hpp"
 #include "widetree.hpp"
 
 using namespace chunky;
 
 int check_ints(const int32_t* p, int64_t n, const char* what) {
     if (n < 0 || (n > 0 && !p)) return fail(CHUNKY_E_INVALID, "%s: bad array (n=%lld)", what, (long long)n);
+    return CHUNKY_OK;
+}
+
+// the decisions of scene_records.cpp behind SceneView::addr32, as entry points (tests/test_addr_bounds_cpu.py)
+extern "C" int chunky_addr32_word(const int64_t dims[5], const uint64_t bytes[2], int indices_checked, uint32_t* word) {
+    if (!dims || !bytes || !word) return fail(CHUNKY_E_INVALID, "addr32_word: NULL");
+    AddrBounds b;
+    b.atlas_w = dims[0], b.atlas_h = dims[1], b.atlas_layers = dims[2], b.sky_w = dims[3], b.sky_h = dims[4];
+    b.aabb_rec_bytes = bytes[0], b.quad_rec_bytes = bytes[1];
+    b.indices_checked = indices_checked != 0;
+    *word = addr32_word(b);
     return CHUNKY_OK;
 }
 

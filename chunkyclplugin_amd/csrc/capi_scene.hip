@@ -368,11 +368,32 @@ int scene_view(chunky_scene* s, SceneView* v, bool want_emitters) {
     v->mat8 = (const int4*)s->mat8.p;
     v->aabb_rec = (const int4*)s->aabb_rec.p;
     v->quad_rec = (const int4*)s->quad_rec.p;
+    {
+        // which arrays kernels may address by 32-bit offsets (addr32.h): the sizes as they stand now, the derived arrays rebuilt above
+        AddrBounds b;
+        b.atlas_w = s->atlas_w, b.atlas_h = s->atlas_h, b.atlas_layers = s->atlas_layers, b.sky_w = s->sky_w, b.sky_h = s->sky_h;
+        b.aabb_rec_bytes = s->aabb_rec.bytes, b.quad_rec_bytes = s->quad_rec.bytes;
+        b.indices_checked = !s->derived_dirty && s->block_info.p != nullptr;
+        v->addr32 = addr32_word(b);
+#ifdef CHUNKY_TUNING
+        if (const char* e = getenv("CHUNKY_ADDR32_MASK")) v->addr32 &= (unsigned)atoi(e);  // tests/test_gpu_addr32_parity.py: 0 = as a scene too large for the 32-bit forms
+#endif
+    }
     v->wide = s->wide_meta.nlev > 0 ? (const uint32_t*)s->wide.p : nullptr;
     v->wide_nlev = s->wide_meta.nlev;
     for (int i = 0; i < 6; i++) {
         v->wide_shift[i] = s->wide_meta.shift[i];
         v->wide_bits[i] = s->wide_meta.bits[i];
     }
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_scene_addr32(chunky_scene* scene, uint32_t* word) {
+    if (scene && !scene->replicas.empty()) return chunky_scene_addr32(scene->replicas[0], word);  // replicas agree
+    LOCK_SCENE(scene);
+    if (!word) return fail(CHUNKY_E_INVALID, "scene_addr32: NULL");
+    SceneView v;
+    if (int rc = scene_view(scene, &v, false)) return rc;
+    *word = v.addr32;
     return CHUNKY_OK;
 }

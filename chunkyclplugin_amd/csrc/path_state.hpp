@@ -54,6 +54,16 @@ DEV void leaf_lookup(const SceneView& S, int bx, int by, int bz, int& data, int&
             }
 #pragma unroll
             for (int i = 0; i < N3; i++) {
+#if defined(CHUNKY_MARCH_HOIST) && CHUNKY_MARCH_HOIST  // render_pool.hip's own kernels: the in-node index ahead of the wait for the entry above it (below, the compiler sinks its five instructions behind the wait and the branch, onto the chain between the two tree reads)
+                const int sh = 3 * (N3 - 1 - i);
+                const unsigned xs = sh <= 6 ? (unsigned)bx << (6 - sh) : (unsigned)bx >> (sh - 6);
+                const unsigned ys = sh <= 3 ? (unsigned)by << (3 - sh) : (unsigned)by >> (sh - 3);
+                unsigned idx = ((unsigned)bz >> sh) & 7u;
+                asm("v_and_or_b32 %0, %1, 56, %0" : "+v"(idx) : "v"(ys));
+                asm("v_and_or_b32 %0, %1, %2, %0" : "+v"(idx) : "v"(xs), "s"(0x1c0u));
+                asm volatile("" : "+v"(idx));  // idx is in its register here, and e is first looked at below
+                if (e >= 0) e = *(const int*)((const char*)tree + (((unsigned)e + idx) << 2));
+#else
                 if (e >= 0) {
                     // index in the 8^3 node = x:3 y:3 z:3 of the cell's bits [sh, sh + 3): each field shifted into place, then two
                     // v_and_or_b32 (the compiler's form is three v_and and a v_or3)
@@ -65,6 +75,7 @@ DEV void leaf_lookup(const SceneView& S, int bx, int by, int bz, int& data, int&
                     asm("v_and_or_b32 %0, %1, %2, %0" : "+v"(idx) : "v"(xs), "s"(0x1c0u));  // (no literal operands in VOP3 on gfx9: the mask rides in an SGPR)
                     e = *(const int*)((const char*)tree + (((unsigned)e + idx) << 2));
                 }
+#endif
             }
         } else
 #pragma unroll

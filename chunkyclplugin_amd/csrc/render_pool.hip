@@ -8,6 +8,17 @@
 
 #include <cstdlib>
 
+// This unit's kernels read the atlas, the sky and the record arrays by 32-bit offsets off scalar bases (rt_device.hpp load_at; launch_render
+// starts them only for scenes whose SceneView::addr32 allows all three).  render_pool_bvh.hip, which includes this file, does not: the
+// entity-BVH instantiations keep the 64-bit addresses.  (-DCHUNKY_ADDR32_FORMS=n: experiments, the arrays one at a time.)
+#if !defined(CHUNKY_POOL_BVH_TU) && !defined(CHUNKY_ADDR32_FORMS)
+#define CHUNKY_ADDR32_FORMS 7
+#endif
+// ... and they form a tree node's in-node index ahead of the wait for the entry above it (path_state.hpp leaf_lookup; EXPERIMENTS 7.4)
+#if !defined(CHUNKY_POOL_BVH_TU) && !defined(CHUNKY_MARCH_HOIST)
+#define CHUNKY_MARCH_HOIST 1
+#endif
+
 #include "path_state.hpp"
 #include "pool_walk.hpp"
 
@@ -655,7 +666,10 @@ bool pool_kernel_applies(int variant, const SceneView& S, const RenderOpts& O, b
     // reference-layout walk, which only the plain instantiations have (pool_kernel<0, 0 | 32 | 64>): with entity BVHs, the extended
     // options or phase statistics launch_pool would pick a wide-tree instantiation, so those go to the fallback kernels
     const bool form0_fits = S.wide != nullptr || (!any_bvh && !opts_extended(O) && !(variant & 4));
-    return !(variant & 2) && !(variant & 8) && have_queue_and_staging && steps_fit && form0_fits &&
+    // the plain instantiations read the atlas, the sky and the records by 32-bit offsets (CHUNKY_ADDR32_FORMS above): a scene whose
+    // arrays are too large for that (scene_records.cpp addr32_word) runs the fallback kernels; the entity-BVH instantiations read any scene
+    const bool addr_fits = any_bvh || (S.addr32 & (unsigned)(CHUNKY_ADDR32_FORMS)) == (unsigned)(CHUNKY_ADDR32_FORMS);
+    return !(variant & 2) && !(variant & 8) && have_queue_and_staging && steps_fit && form0_fits && addr_fits &&
            (!any_bvh || (S.bvh_rec && S.tri_rec && S.mat8 && !(variant & 1)));
 }
 hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,

@@ -14,6 +14,7 @@
 
 #include "rt_math.h"
 #include "camera_proj.h"
+#include "addr32.h"
 
 namespace chunky {
 
@@ -76,6 +77,11 @@ struct SceneView {
     const uint32_t* __restrict__ wide;
     int wide_nlev;
     int wide_shift[6], wide_bits[6];
+    // Which scene arrays kernels may read as `kernel-argument base + 32-bit byte offset` (kAddr32*, addr32.h; scene_records.cpp
+    // addr32_word computes it at upload from the arrays' sizes).  Read by the host alone: launch_render starts kernels that have the
+    // 32-bit forms only for a scene whose word allows them.  (It stands in what was four bytes of padding ahead of the next pointer:
+    // no other member moved, and the kernels that do not use the forms are the kernels they were, argument offsets included.)
+    unsigned addr32;
     // per block (index = block pointer / 2) 8 ints: {modelType, modelPointer, material words 0..4 of a
     // full cube (K/material.h:31-40), 0} — the block-palette and material-palette reads of
     // K/block.h:36-49 as ONE 32-byte load; built at upload, null when a palette is missing
@@ -190,6 +196,35 @@ DEV f4 unpack_unorm8(uint32_t t) {
     return f4{rt_unorm8(t & 0xFF), rt_unorm8((t >> 8) & 0xFF), rt_unorm8((t >> 16) & 0xFF), rt_unorm8(t >> 24)};
 }
 
+// ---------------------------------------------------------------------------------------------
+// Scene reads as "scalar base + 32-bit offset".  `base` is a pointer out of the kernel's arguments (wave-uniform, in SGPRs),
+// `byte_offset` a per-lane unsigned byte offset: the compiler then emits global_load_* v, v_offset, s[base:base+1] — no 64-bit
+// per-lane address, no sign extension, no v_lshl_add_u64 (leaf_lookup, path_state.hpp, has read the tree this way since round 6).
+// Only legal where the host guarantees the offset (SceneView::addr32, addr32.h): an unsigned offset made from a negative index is 4 GB away.
+//
+// Which form a kernel has is decided when its translation unit is compiled, not in the kernel: CHUNKY_ADDR32_FORMS, defined ahead of
+// every include, names the arrays (kAddr32* bits) that unit's kernels read by 32-bit offsets; without it every array keeps its 64-bit
+// per-lane addresses, the code from before these forms.  render_pool.hip defines it for the plain, sorted, proj:: and extended
+// instantiations of render_pool, and launch_render starts those only for a scene whose word has every bit (pool_kernel_applies); any
+// other scene runs the fallback kernels, which have the 64-bit forms, as the entity-BVH instantiations do (render_pool_bvh.hip).
+// (A wave-uniform branch inside the kernel was tried first: render_pool<17, 64> stands at its 80 VGPRs, and with the branch and the
+// fences that keep the two arms' loads apart it spilled 16 to 32 bytes per lane, with any one array alone — EXPERIMENTS 7.4.)
+#ifndef CHUNKY_ADDR32_FORMS
+#define CHUNKY_ADDR32_FORMS 0
+#endif
+#define CHUNKY_ADDR32(bit) (((CHUNKY_ADDR32_FORMS) & (bit)) != 0)
+template <typename T>
+DEV T load_at(const void* __restrict__ base, unsigned byte_offset) {
+    return *(const T*)((const char*)base + byte_offset);
+}
+// a * b + c on the low 24 bits of a and b, b wave-uniform (a scene dimension): one v_mad_u32_u24.  Written as the instruction: from
+// `__umul24(a, b) + c` the compiler, which knows a's range, makes a v_mad_u64_u32 (a 64-bit multiply-add for a 32-bit result).
+DEV unsigned mad_u24(unsigned a, unsigned b_uniform, unsigned c) {
+    unsigned r;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b_uniform), "v"(c));
+    return r;
+}
+
 // K/textureAtlas.h:10-28: nearest, unnormalised, clamp-to-edge, layer clamped
 DEV uint32_t atlas_texel(const SceneView& S, float u, float v, int location, int size) {
     int width = (size >> 16) & 0xFFFF, height = size & 0xFFFF;
@@ -202,6 +237,9 @@ DEV uint32_t atlas_texel(const SceneView& S, float u, float v, int location, int
     x = rt_clampi(x, 0, S.atlas_w - 1);
     y = rt_clampi(y, 0, S.atlas_h - 1);
     d = rt_clampi(d, 0, S.atlas_layers - 1);
+    // x, y and d are clamped: the texel's index is below the atlas's own size, and with kAddr32Atlas every factor fits 24 bits
+    if (CHUNKY_ADDR32(kAddr32Atlas))
+        return load_at<uint32_t>(S.atlas, mad_u24(mad_u24((unsigned)d, (unsigned)S.atlas_h, (unsigned)y), (unsigned)S.atlas_w, (unsigned)x) << 2);
     return S.atlas[((size_t)d * S.atlas_h + y) * S.atlas_w + x];
 }
 
@@ -363,6 +401,8 @@ DEV float quad_model_hit(const SceneView& S, int ptr, f3 no, f3 dir, Hit& h) {
 }
 
 DEV bool material_sample8(const SceneView& S, int m8, float u, float v, Hit& h) {
+    // Stays a signed 64-bit index in every unit: m8 is read out of a record, and a leaf with an odd block pointer (which no upload
+    // refuses) makes block_hit find its "record" across two blocks of block_info — what stands there as a material index is anything.
     const int4 a = S.mat8[m8], b = S.mat8[m8 + 1];
     return material_eval(S, a.x, a.y, a.z, a.w, b.x, u, v, h, b.y);
 }
@@ -372,8 +412,16 @@ DEV float aabb_model_hit_rec(const SceneView& S, int rec, f3 no, f3 dir, f3 inv,
     const int boxes = rec & 0xFF, first = (int)((unsigned)rec >> 8);
     float best = rt_inf();
     bool hit = false;
-    for (int i = 0; i < boxes; i++) {
-        const int4 r0 = S.aabb_rec[(first + i) * 3], r1 = S.aabb_rec[(first + i) * 3 + 1], r2 = S.aabb_rec[(first + i) * 3 + 2];
+    // (first is 24 bits of a word and boxes 8, whatever the word: the record's byte offset, (first + i) * 48, is below 2^30 — one 24-bit
+    // multiply, the loop adds 48 to it, the three reads are immediate offsets off it)
+    unsigned off = (unsigned)first * 48u;
+    for (int i = 0; i < boxes; i++, off += 48u) {
+        int4 r0, r1, r2;
+        if (CHUNKY_ADDR32(kAddr32Records)) {
+            r0 = load_at<int4>(S.aabb_rec, off), r1 = load_at<int4>(S.aabb_rec, off + 16u), r2 = load_at<int4>(S.aabb_rec, off + 32u);
+        } else {
+            r0 = S.aabb_rec[(first + i) * 3], r1 = S.aabb_rec[(first + i) * 3 + 1], r2 = S.aabb_rec[(first + i) * 3 + 2];
+        }
         Slabs s = slabs(as_float(r0.x), as_float(r0.y), as_float(r0.z), as_float(r0.w), as_float(r1.x), as_float(r1.y), no, inv);
         float tn = slab_near(s), tf = slab_far(s);
         if (tf < tn) continue;
@@ -404,9 +452,17 @@ DEV float quad_model_hit_rec(const SceneView& S, int rec, f3 no, f3 dir, Hit& h)
     const int quads = rec & 0xFF, first = (int)((unsigned)rec >> 8);
     float best = rt_inf();
     bool hit = false;
-    for (int i = 0; i < quads; i++) {
+    constexpr bool a32 = CHUNKY_ADDR32(kAddr32Records);  // (offsets as in aabb_model_hit_rec: (first + i) * 96 < 2^31)
+    unsigned off = (unsigned)first * 96u;
+    for (int i = 0; i < quads; i++, off += 96u) {
         const int4* __restrict__ q = S.quad_rec + (first + i) * 6;
-        const int4 r0 = q[0], r1 = q[1], r2 = q[2], r4 = q[4];
+        int4 r0, r1, r2, r4;
+        if (a32) {
+            r0 = load_at<int4>(S.quad_rec, off), r1 = load_at<int4>(S.quad_rec, off + 16u), r2 = load_at<int4>(S.quad_rec, off + 32u),
+            r4 = load_at<int4>(S.quad_rec, off + 64u);
+        } else {
+            r0 = q[0], r1 = q[1], r2 = q[2], r4 = q[4];
+        }
         const f3 qo = mk3(as_float(r0.x), as_float(r0.y), as_float(r0.z));
         const f3 xv = mk3(as_float(r1.x), as_float(r1.y), as_float(r1.z));
         const f3 yv = mk3(as_float(r2.x), as_float(r2.y), as_float(r2.z));
@@ -420,7 +476,12 @@ DEV float quad_model_hit_rec(const SceneView& S, int rec, f3 no, f3 dir, Hit& h)
         float u = dot(pt, xv) / xx;
         float v = dot(pt, yv) / yy;
         if (!(u >= 0 && u <= 1 && v >= 0 && v <= 1)) continue;
-        const int4 r3 = q[3], r5 = q[5];
+        int4 r3, r5;
+        if (a32) {
+            r3 = load_at<int4>(S.quad_rec, off + 48u), r5 = load_at<int4>(S.quad_rec, off + 80u);
+        } else {
+            r3 = q[3], r5 = q[5];
+        }
         float tu = as_float(r3.x) + (u * as_float(r3.y));
         float tv = as_float(r3.z) + (v * as_float(r3.w));
         if (material_eval(S, r5.x, r5.y, r5.z, r5.w, r4.w, tu, tv, h, (int)((unsigned)r4.w >> 8))) {  // r4.w = emittance byte | word 5 << 8
@@ -445,6 +506,7 @@ DEV float block_hit(const SceneView& S, int block, int bx, int by, int bz, f3 po
     f3 no = (pos - dir * kOffset) - mk3((float)bx, (float)by, (float)bz);
     int type, ptr;
     if (KINDS != kBlockAny || S.block_info) {
+        // (stays an unsigned index off a 64-bit address: as a 32-bit byte offset it cost render_pool<-1, 0> a spilled register — EXPERIMENTS 7.4)
         const int4 a = S.block_info[(unsigned)block], b = S.block_info[(unsigned)block + 1u];
         type = a.x;
         ptr = a.y;
@@ -582,6 +644,16 @@ DEV SkyTexels sky_fetch(const SceneView& S, f3 d) {
     SkyTexels k;
     rt_mirror_linear(theta, S.sky_w, &i0, &i1, &k.a);
     rt_mirror_linear(phi, S.sky_h, &j0, &j1, &k.b);
+    if (CHUNKY_ADDR32(kAddr32Sky)) {
+        // rt_mirror_linear's indices lie in [0, sky_w) and [0, sky_h): a texel's byte offset is row * (sky_w * 16) + (column << 4), the
+        // row's pitch a scalar made once, the two columns shifted once
+        const unsigned pitch = (unsigned)S.sky_w << 4, c0 = (unsigned)i0 << 4, c1 = (unsigned)i1 << 4;
+        k.t00 = load_at<float4>(S.sky, mad_u24((unsigned)j0, pitch, c0));
+        k.t10 = load_at<float4>(S.sky, mad_u24((unsigned)j0, pitch, c1));
+        k.t01 = load_at<float4>(S.sky, mad_u24((unsigned)j1, pitch, c0));
+        k.t11 = load_at<float4>(S.sky, mad_u24((unsigned)j1, pitch, c1));
+        return k;
+    }
     k.t00 = S.sky[j0 * S.sky_w + i0];
     k.t10 = S.sky[j0 * S.sky_w + i1];
     k.t01 = S.sky[j1 * S.sky_w + i0];

@@ -63,6 +63,19 @@ int model_leaf_permille(const std::vector<int32_t>& T, const std::vector<int32_t
     return cubes + models > 0 ? (int)(models * 1000 / (cubes + models)) : 0;
 }
 
+unsigned addr32_word(const AddrBounds& b) {
+    constexpr int64_t k24 = (int64_t)1 << 24;
+    constexpr uint64_t k32 = (uint64_t)1 << 32;
+    unsigned word = 0;
+    // (dimensions below 2^24 and a product below 2^32 bytes: nothing here overflows 64 bits)
+    if (b.atlas_w > 0 && b.atlas_h > 0 && b.atlas_layers > 0 && b.atlas_w < k24 && b.atlas_h < k24 && b.atlas_layers < k24 &&
+        b.atlas_layers * b.atlas_h < k24 && (uint64_t)(b.atlas_layers * b.atlas_h) * (uint64_t)b.atlas_w * 4 < k32)
+        word |= kAddr32Atlas;
+    if (b.sky_w > 0 && b.sky_h > 0 && b.sky_w * 16 < k24 && b.sky_h < k24 && (uint64_t)b.sky_w * (uint64_t)b.sky_h * 16 < k32) word |= kAddr32Sky;
+    if (b.indices_checked && b.aabb_rec_bytes < k32 && b.quad_rec_bytes < k32) word |= kAddr32Records;
+    return word;
+}
+
 void derive_records(const std::vector<int32_t>& B, const std::vector<int32_t>& M, const std::vector<int32_t>& A, const std::vector<int32_t>& Q,
                     DerivedRecords* out) {
     const size_t n_blocks = B.size() / 2, n_mats = M.size() / 6;

@@ -6,6 +6,8 @@
 #include <cstring>
 #include <vector>
 
+#include "addr32.h"
+
 namespace chunky {
 
 inline float bits_to_float(int32_t i) {
@@ -36,6 +38,16 @@ struct DerivedRecords {
 };
 void derive_records(const std::vector<int32_t>& blocks, const std::vector<int32_t>& materials, const std::vector<int32_t>& aabbs,
                     const std::vector<int32_t>& quads, DerivedRecords* out);
+
+// SceneView::addr32 (addr32.h): which arrays the kernels may address as a scalar base + a 32-bit unsigned byte offset.  Sizes are what
+// the scene holds (the record arrays in bytes); `indices_checked` says that the record arrays are the ones derive_records built from the
+// palettes as they are now (the record numbers in block_info are its own), and not a stale or foreign copy.
+struct AddrBounds {
+    int64_t atlas_w = 0, atlas_h = 0, atlas_layers = 0, sky_w = 0, sky_h = 0;
+    uint64_t aabb_rec_bytes = 0, quad_rec_bytes = 0;
+    bool indices_checked = false;
+};
+unsigned addr32_word(const AddrBounds& b);
 
 // quad_aux (rt_device.hpp), for the quads that kept the packed path; false = no table
 bool build_quad_aux(const std::vector<int32_t>& blocks, const std::vector<int32_t>& quads, std::vector<float>* out);

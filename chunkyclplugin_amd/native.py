@@ -106,7 +106,7 @@ TUNING_LIB_PATH = os.path.join(PKG_DIR, "libchunky_hip_tuning.so")
 def build_tuning(force: bool = False) -> str:
     """The same library compiled with -DCHUNKY_TUNING: the build that reads the tuning / test-rig environment variables
     (CHUNKY_WIDE_LEVELS, CHUNKY_WIDE_TOP_BITS, CHUNKY_DEBUG_WIDE_BITS, CHUNKY_BVH_LAYOUT, CHUNKY_GROUP_TRANSPORT,
-    CHUNKY_GROUP_SELF_EXCHANGE, CHUNKY_GROUP_NO_PROBE, CHUNKY_GROUP_TIMEOUT_MS, CHUNKY_RCCL_TRY_SHARED).  The shipping
+    CHUNKY_GROUP_SELF_EXCHANGE, CHUNKY_GROUP_NO_PROBE, CHUNKY_GROUP_TIMEOUT_MS, CHUNKY_RCCL_TRY_SHARED, CHUNKY_ADDR32_MASK).  The shipping
     library reads none of them; tests and tools that need one run a child process with CHUNKY_HIP_LIB pointing here."""
     if force or _stale(TUNING_LIB_PATH):
         build(force=True, extra_flags=["-DCHUNKY_TUNING"], out=TUNING_LIB_PATH, objdir=os.path.join(CSRC, "build", "tuning"))
@@ -259,6 +259,8 @@ def lib() -> C.CDLL:
             "chunky_filter_gamma_thresholds": [vp],
             "chunky_filter_frame_device": [vp, i64, f32, vp, vp, C.c_int, C.c_int, C.POINTER(f32)],
             "chunky_widetree_lookup": [vp, i64, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(i64)],
+            "chunky_addr32_word": [vp, vp, C.c_int, C.POINTER(C.c_uint32)],
+            "chunky_scene_addr32": [vp, C.POINTER(C.c_uint32)],
         }
         for name, args in sig.items():
             if not hasattr(L, name) and os.environ.get("CHUNKY_HIP_LIB") and os.environ.get("CHUNKY_HIP_LIB_EARLIER") == "1":
@@ -311,6 +313,20 @@ def widetree_lookup(tree: np.ndarray, depth: int, xyz: np.ndarray, level_bits=No
                                        0 if lb is None else lb.size, ptr(xyz), len(xyz), ptr(data), ptr(level),
                                        C.byref(n_entries)))
     return data, level, n_entries.value
+
+
+ADDR32_ATLAS, ADDR32_SKY, ADDR32_RECORDS = 1, 2, 4  # chunky_addr32_word / chunky_scene_addr32 (csrc/addr32.h)
+
+
+def addr32_word(atlas=(1, 1, 1), sky=(1, 1), record_bytes=(0, 0), indices_checked: bool = True) -> int:
+    """chunky_addr32_word: which scene arrays kernels may address by 32-bit offsets, for an atlas (width, height, layers), a sky
+    (width, height), the sizes in bytes of (aabb_rec, quad_rec) and whether those arrays are the library's own."""
+    dims = np.array([*atlas, *sky], np.int64)
+    sizes = np.array(record_bytes, np.uint64)
+    assert dims.size == 5 and sizes.size == 2
+    word = C.c_uint32()
+    check(lib().chunky_addr32_word(ptr(dims), ptr(sizes), 1 if indices_checked else 0, C.byref(word)))
+    return word.value
 
 
 def denoise_params(iterations: Optional[int] = None, sigma_color: Optional[float] = None, sigma_normal: Optional[float] = None,

@@ -190,6 +190,12 @@ class HipSceneLoader:
         check(native.lib().chunky_scene_emitters(self._h, ptr(out), n.value, C.byref(n)))
         return out[:n.value]
 
+    def addr32(self) -> int:
+        """chunky_scene_addr32: the arrays the next launch reads by 32-bit offsets (native.ADDR32_*)."""
+        word = C.c_uint32()
+        check(native.lib().chunky_scene_addr32(self._h, C.byref(word)))
+        return word.value
+
     def selftest_helpers(self, which: int, rows, tree: int = 1):
         """chunky_selftest_helpers: the device counterpart of reference helper `which` on rows of 32 floats; returns
         (rows of 12 floats, tree form used for row kind 14)."""

@@ -698,6 +698,15 @@ int chunky_filter_frame_device(chunky_ctx* ctx, int64_t n_pixels, float exposure
 int chunky_widetree_lookup(const int32_t* tree, int64_t n_ints, int depth, const int32_t* level_bits, int n_levels,
                            const int32_t* xyz /* 3n */, int n, int32_t* data_out, int32_t* level_out, int64_t* n_entries);
 
+/* ---- host-side verification hook for how the kernels address scene arrays (no device needed).  At upload the library decides, per
+ * array, whether kernels may read it as "base + 32-bit unsigned byte offset" (DESIGN.md section 5).  chunky_addr32_word is that
+ * decision: dims = {atlas width, height, layers, sky width, height}, bytes = the sizes in bytes of the model-record arrays {aabb_rec,
+ * quad_rec}, indices_checked = those arrays are the library's own, built from the palettes as they are.  *word: bit 0 the
+ * atlas, bit 1 the sky, bit 2 the record arrays.  A scene whose word lacks a bit renders on kernels with 64-bit addresses. */
+int chunky_addr32_word(const int64_t dims[5], const uint64_t bytes[2], int indices_checked, uint32_t* word);
+/* The word the next launch on this scene carries (needs a complete scene, as a launch does).  On a group: member 0's. */
+int chunky_scene_addr32(chunky_scene* scene, uint32_t* word);
+
 /* ---- self test: evaluate the rt_math.h contract on the device (bit-compared with the host by tests) */
 int chunky_selftest_math(chunky_ctx* ctx, int which, int n, const float* a, const float* b, float* out);
 

@@ -305,7 +305,8 @@ def compile_kernel(kernel, extra):
     from chunkyclplugin_amd import native
     flags = [f for f in native.HIPCC_FLAGS if f != "-shared"] + extra
     # (the entity-BVH instantiations — the fourth template argument true — are compiled in render_pool_bvh.hip)
-    unit = "render_pool_bvh" if re.search(r"render_poolILi\w+ELi\w+ELb[01]ELb1E", kernel) else "render_pool"
+    # (digits only between the markers: `\w+` would run across them and take the sorted kernel's last flag for the fourth argument)
+    unit = "render_pool_bvh" if re.search(r"render_poolILin?\d+ELi\d+ELb[01]ELb1E", kernel) else "render_pool"
     with tempfile.TemporaryDirectory() as td:
         subprocess.run(["hipcc", *flags, "-x", "hip", "-c", os.path.join(native.CSRC, unit + ".hip"), "-o", os.path.join(td, "rp.o"), "--save-temps"],
                        cwd=td, check=True, capture_output=True)
