@@ -1,5 +1,11 @@
-// capi_aov.hip — albedo and normal images for denoisers (aov.hip).
+// capi_aov.hip — albedo and normal images for denoisers, and the first-hit images of chunky_render_aov_passes_ex (aov.hip).
 #include "capi_internal.hpp"
+
+// words per pixel of the images of chunky_render_aov_read_ex, and the offset (in words per pixel) of each inside r->aov_ex
+static const int kAovWords[7] = {3, 3, 1, 1, 3, 1, 1};
+static const int kAovExOffset[7] = {0, 0, 0, 1, 2, 5, 6};  // alpha, depth, position, emittance, block
+constexpr int kAovExWords = 7;
+static size_t aov_ex_bytes(const chunky_render* r) { return (size_t)r->width * r->height * kAovExWords * 4; }
 
 // On a group's render target member 0 renders the caller's whole share (as chunky_render_preview does): the images are then the
 // one-context images without an exchange, and every AOV entry point below forwards to member 0.
@@ -10,12 +16,22 @@ static int aov_ensure(chunky_render* r) {
     HIP_TRY(hipMemsetAsync(r->aov.p, 0, bytes, r->ctx->stream));
     return CHUNKY_OK;
 }
+// the five first-hit images: allocated, zeroed, by the first chunky_render_aov_passes_ex
+static int aov_ex_ensure(chunky_render* r) {
+    if (r->aov_ex.p) return CHUNKY_OK;
+    HIP_TRY(r->aov_ex.alloc(aov_ex_bytes(r)));
+    HIP_TRY(hipMemsetAsync(r->aov_ex.p, 0, aov_ex_bytes(r), r->ctx->stream));
+    return CHUNKY_OK;
+}
 
 // n passes over the pixel slots of shard T (a single-device target: its own share; member 0 of a group: the caller's share)
-static int aov_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n, int first_buffer_spp) {
+// `ex`: chunky_render_aov_passes_ex, which folds the five first-hit images from the same trace
+static int aov_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n, int first_buffer_spp, bool ex) {
     LOCK_RENDER(r);
     if (!r->have_camera) return fail(CHUNKY_E_STATE, "aov_passes before set_camera");
     if (int rc = aov_ensure(r)) return rc;
+    if (ex)
+        if (int rc = aov_ex_ensure(r)) return rc;
     r->aov_last_launches = 0;
     if (n == 0 || T.n_local <= 0) return CHUNKY_OK;
     SceneView S;
@@ -26,13 +42,24 @@ static int aov_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n
     float* albedo = (float*)r->aov.p;
     float* normal = (float*)((char*)r->aov.p + aov_image_bytes(r));
     int* counter = (int*)((char*)r->aov.p + 2 * aov_image_bytes(r));
+    const size_t plane = (size_t)r->width * r->height;  // words of a one-word image
+    AovExImages images{albedo, normal, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (ex) {
+        float* exf = (float*)r->aov_ex.p;
+        images.alpha = exf + kAovExOffset[CHUNKY_AOV_ALPHA] * plane;
+        images.depth = exf + kAovExOffset[CHUNKY_AOV_DEPTH] * plane;
+        images.position = exf + kAovExOffset[CHUNKY_AOV_POSITION] * plane;
+        images.emittance = exf + kAovExOffset[CHUNKY_AOV_EMITTANCE] * plane;
+        images.block = (int*)exf + kAovExOffset[CHUNKY_AOV_BLOCK] * plane;
+    }
     for (int done = 0; done < n;) {  // launches of at most kMaxPassesPerLaunch: each continues the running mean where the last left it
         PassSeeds ps;
         ps.n = (n - done) < kMaxPassesPerLaunch ? (n - done) : kMaxPassesPerLaunch;
         ps.first_spp = first_buffer_spp + done;
         memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
         if (int rc = r->aov_clock.open(r->ctx->stream)) return rc;
-        HIP_TRY(launch_aov(r->kernel_variant, S, r->cam, r->opts, T, ps, albedo, normal, counter, r->ctx->stream, &r->aov_choice));
+        if (ex) HIP_TRY(launch_aov_ex(r->kernel_variant, S, r->cam, r->opts, T, ps, images, counter, r->ctx->stream, &r->aov_choice));
+        else HIP_TRY(launch_aov(r->kernel_variant, S, r->cam, r->opts, T, ps, albedo, normal, counter, r->ctx->stream, &r->aov_choice));
         if (int rc = r->aov_clock.close(r->ctx->stream)) return rc;
         r->aov_last_launches += 1;
         done += ps.n;
@@ -40,18 +67,26 @@ static int aov_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n
     return CHUNKY_OK;
 }
 
-extern "C" int chunky_render_aov_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp) {
+static int aov_passes_entry(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp, bool ex) {
     if (n < 0 || (n > 0 && !seeds) || first_buffer_spp < 0) return fail(CHUNKY_E_INVALID, "aov_passes: bad arguments");
     if (r && !r->parts.empty()) {
         std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
         ShardView t;  // the caller's share of the image, all of it on member 0
         if (!make_shard_view(r->width, r->height, r->outer.rank, r->outer.world, r->outer.tile, &t))
             return fail(CHUNKY_E_INVALID, "aov_passes: the group's share needs more than 2^31 pixel slots");
-        return aov_passes(r->parts[0], t, seeds, n, first_buffer_spp);
+        return aov_passes(r->parts[0], t, seeds, n, first_buffer_spp, ex);
     }
     if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
     std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
-    return aov_passes(r, r->shard, seeds, n, first_buffer_spp);
+    return aov_passes(r, r->shard, seeds, n, first_buffer_spp, ex);
+}
+
+extern "C" int chunky_render_aov_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp) {
+    return aov_passes_entry(r, seeds, n, first_buffer_spp, false);
+}
+
+extern "C" int chunky_render_aov_passes_ex(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp) {
+    return aov_passes_entry(r, seeds, n, first_buffer_spp, true);
 }
 
 extern "C" int chunky_render_aov_read(chunky_render* r, int which, float* out, int64_t n) {
@@ -62,10 +97,22 @@ extern "C" int chunky_render_aov_read(chunky_render* r, int which, float* out, i
     return read_floats("aov_read", r, src, out, n, (int64_t)r->width * r->height * 3);
 }
 
+extern "C" int chunky_render_aov_read_ex(chunky_render* r, int which, void* out, int64_t n) {
+    if (r && !r->parts.empty()) return chunky_render_aov_read_ex(r->parts[0], which, out, n);
+    LOCK_RENDER(r);
+    if (which < CHUNKY_AOV_ALBEDO || which > CHUNKY_AOV_BLOCK) return fail(CHUNKY_E_INVALID, "aov_read_ex: unknown image %d", which);
+    const int64_t need = (int64_t)r->width * r->height * kAovWords[which];
+    const char* src;  // null before any pass that writes the image
+    if (which <= CHUNKY_AOV_NORMAL) src = r->aov.p ? (const char*)r->aov.p + (which == CHUNKY_AOV_NORMAL ? aov_image_bytes(r) : 0) : nullptr;
+    else src = r->aov_ex.p ? (const char*)r->aov_ex.p + (size_t)kAovExOffset[which] * r->width * r->height * 4 : nullptr;
+    return read_floats("aov_read_ex", r, src, out, n, need);
+}
+
 extern "C" int chunky_render_aov_reset(chunky_render* r) {
     if (r && !r->parts.empty()) return chunky_render_aov_reset(r->parts[0]);
     LOCK_RENDER(r);
     if (r->aov.p) HIP_TRY(hipMemsetAsync(r->aov.p, 0, 2 * aov_image_bytes(r), r->ctx->stream));
+    if (r->aov_ex.p) HIP_TRY(hipMemsetAsync(r->aov_ex.p, 0, aov_ex_bytes(r), r->ctx->stream));
     return CHUNKY_OK;
 }
 

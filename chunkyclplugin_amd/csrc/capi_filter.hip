@@ -31,6 +31,28 @@ extern "C" int chunky_filter_frame(chunky_ctx* ctx, int width, int height, doubl
     return CHUNKY_OK;
 }
 
+extern "C" int chunky_filter_frame_alpha(chunky_ctx* ctx, int width, int height, double exposure, const double* input, const float* alpha,
+                                         int32_t* argb_out, int type) {
+    if (!ctx) return fail(CHUNKY_E_INVALID, "filter_frame_alpha: NULL context");
+    if (!ctx->members.empty()) ctx = ctx->members[0];
+    if (width < 0 || height < 0) return fail(CHUNKY_E_INVALID, "filter_frame_alpha: %dx%d", width, height);
+    const long long n = (long long)width * height;
+    if (n == 0) return CHUNKY_OK;
+    if (!input || !alpha || !argb_out) return fail(CHUNKY_E_INVALID, "filter_frame_alpha: NULL buffer");
+    std::lock_guard<std::recursive_mutex> guard(ctx->mu);
+    HIP_TRY(hipSetDevice(ctx->device));
+    DevBuf in, cover, out;
+    HIP_TRY(in.upload(input, (size_t)n * 24, ctx->stream));
+    HIP_TRY(cover.upload(alpha, (size_t)n * 4, ctx->stream));
+    HIP_TRY(out.alloc((size_t)n * 4));
+    const float* table = nullptr;
+    if (int rc = device_gamma_table(ctx, &table)) return rc;
+    HIP_TRY(launch_filter_alpha(n, (float)exposure, (const double*)in.p, (const float*)cover.p, (unsigned*)out.p, type, ctx->stream, table));
+    HIP_TRY(hipMemcpyAsync(argb_out, out.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return CHUNKY_OK;
+}
+
 extern "C" int chunky_filter_frame_device(chunky_ctx* ctx, int64_t n_pixels, float exposure, const void* d_input,
                                           void* d_argb, int type, int repeat, float* kernel_ms) {
     if (!ctx) return fail(CHUNKY_E_INVALID, "filter_frame_device: NULL context");

@@ -9,6 +9,7 @@
 #include "../../include/chunky_hip.h"
 #include "camera_proj.h"
 #include "capi_error.hpp"
+#include "filter_alpha.h"
 #include "rt_math.h"
 #include "scene_records.hpp"
 #include "widetree.hpp"
@@ -157,6 +158,12 @@ const float* gamma_thresholds() {
     });
     return T;
 }
+extern "C" int chunky_filter_alpha_bytes(const float* alpha, int64_t n, int32_t* out) {
+    if (n < 0 || (n > 0 && (!alpha || !out))) return fail(CHUNKY_E_INVALID, "filter_alpha_bytes: bad arguments");
+    for (int64_t i = 0; i < n; i++) out[i] = (int32_t)rt_alpha_byte(alpha[i]);
+    return CHUNKY_OK;
+}
+
 extern "C" int chunky_filter_gamma_thresholds(float* out256) {
     if (!out256) return fail(CHUNKY_E_INVALID, "gamma_thresholds: NULL output");
     memcpy(out256, gamma_thresholds(), 256 * sizeof(float));

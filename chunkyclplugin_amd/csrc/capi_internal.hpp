@@ -173,6 +173,9 @@ struct chunky_render {
     // kernel's claim counter; allocated (and zeroed) by the first AOV call.  Timing and the last instantiation are kept apart from
     // the render kernels' (chunky_render_kernel_time / _kernel_info do not see AOV launches)
     DevBuf aov;
+    // chunky_render_aov_passes_ex: alpha, depth (a word per pixel each), position (3), emittance, block id (1 each), allocated (and
+    // zeroed) by the first _ex call; its launches share the AOV's counter, clock and choice
+    DevBuf aov_ex;
     LaunchClock aov_clock{&free_events};
     AovChoice aov_choice{0, 0, 0};
     int aov_last_launches = 0;  // launches of the most recent chunky_render_aov_passes

@@ -3,6 +3,7 @@
 // Compiled with -ffp-contract=off (see rt_device.hpp).
 #include <hip/hip_runtime.h>
 
+#include "filter_alpha.h"
 #include "kernels.hpp"
 #include "rt_device.hpp"
 
@@ -212,6 +213,72 @@ __global__ __launch_bounds__(256) void filter_kernel(long long n, float exposure
         }
         __syncthreads();
     }
+}
+
+// chunky_filter_frame_alpha: filter_kernel with the word's top byte taken from alpha[pixel] (filter_alpha.h) instead of 0xFF.  A kernel of its own, not a flag on filter_kernel:
+// that one keeps the code it has (sharing the body through a template changed its schedule).  R, G and B go through the same
+// functions in the same order, so they are the same bytes.
+__global__ __launch_bounds__(256) void filter_alpha_kernel(long long n, float exposure, const double* __restrict__ in, const float* __restrict__ alpha,
+                                                           unsigned* __restrict__ out, int type, int vec_ok, const float* __restrict__ thresholds) {
+    __shared__ float stage[3 * kFilterTile];
+    __shared__ float kT[256];
+    const int t = threadIdx.x;
+    const bool bytes = thresholds != nullptr && (type == 0 || type == 2);  // GAMMA, ACES through the threshold table
+    if (bytes) kT[t] = thresholds[t];
+    const long long total = 3 * n;
+    for (long long base = (long long)blockIdx.x * kFilterTile; base < n; base += (long long)gridDim.x * kFilterTile) {
+        const long long first = 3 * base;
+        if (vec_ok && base + kFilterTile <= n) {
+            const double2* __restrict__ src = reinterpret_cast<const double2*>(in + first);
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const double2 v = src[t + 256 * k];
+                stage[2 * (t + 256 * k)] = (float)v.x;
+                stage[2 * (t + 256 * k) + 1] = (float)v.y;
+            }
+        } else {
+            for (int k = t; k < 3 * kFilterTile; k += 256) stage[k] = first + k < total ? (float)in[first + k] : 0.0f;
+        }
+        unsigned top[2];  // the alpha bytes of this lane's two pixels, in place (a pixel beyond n: 0, never stored)
+#pragma unroll
+        for (int k = 0; k < 2; k++) top[k] = base + t + 256 * k < n ? rt_alpha_byte(alpha[base + t + 256 * k]) << 24 : 0u;
+        __syncthreads();
+        float c[6];
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            const int px = t + 256 * k;
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) c[3 * k + ch] = stage[3 * px + ch];
+        }
+        if (bytes) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) c[i] *= exposure;
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const int px = t + 256 * k;
+                const unsigned word = top[k] | (type == 2 ? aces_bytes3(c[3 * k], c[3 * k + 1], c[3 * k + 2], kT)
+                                                          : gamma_bytes3(c[3 * k], c[3 * k + 1], c[3 * k + 2], kT));
+                if (base + px < n) out[base + px] = word;
+            }
+        } else {
+            filter_curve<6>(c, exposure, type);
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const int px = t + 256 * k;
+                if (base + px < n) out[base + px] = top[k] | (filter_pack(c[3 * k], c[3 * k + 1], c[3 * k + 2]) & 0x00FFFFFFu);
+            }
+        }
+        __syncthreads();
+    }
+}
+hipError_t launch_filter_alpha(long long n_pixels, float exposure, const double* in, const float* alpha, unsigned* out, int type,
+                               hipStream_t stream, const float* thresholds) {
+    if (n_pixels <= 0) return hipSuccess;
+    long long tiles = (n_pixels + kFilterTile - 1) / kFilterTile;
+    int blocks = (int)(tiles < 4096 ? tiles : 4096);
+    int vec_ok = (reinterpret_cast<uintptr_t>(in) & 15u) == 0;
+    hipLaunchKernelGGL(filter_alpha_kernel, dim3(blocks), dim3(256), 0, stream, n_pixels, exposure, in, alpha, out, type, vec_ok, thresholds);
+    return hipGetLastError();
 }
 hipError_t launch_gamma_scan(unsigned first, unsigned long long count, int curve, const float* thresholds, unsigned long long* mismatches,
                              float* worst, hipStream_t stream) {

@@ -117,6 +117,15 @@ struct AovChoice {
 // pixel slots of shard T; `counter` is one int of device memory the launch claims its work from.
 hipError_t launch_aov(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
                       float* albedo, float* normal, int* counter, hipStream_t stream, AovChoice* chosen);
+// The seven images of chunky_render_aov_passes_ex (aov.hip aov_ex_kernel): albedo, normal and position 3 * width * height floats, the
+// others width * height words
+struct AovExImages {
+    float *albedo, *normal, *alpha, *depth, *position, *emittance;
+    int* block;
+};
+// launch_aov with the five first-hit images folded from the same trace
+hipError_t launch_aov_ex(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
+                         const AovExImages& I, int* counter, hipStream_t stream, AovChoice* chosen);
 // The À-Trous denoiser (denoise.hip; specification: denoise_spec.h).  color / albedo / normal / out: 3 * width * height floats on the
 // device (out may not alias an input); `work`: denoise_work_bytes of device memory, 16-byte aligned, the launch's own while it runs.
 // One launch per iteration plus the pack (or demodulation) pass, all on `stream`; *launches receives their number.  `form` picks how taps
@@ -144,6 +153,9 @@ hipError_t launch_adaptive_finish(int n_pixels, const unsigned char* active, int
 // thresholds: 256 floats on the device (capi_host.cpp gamma_thresholds) or null = evaluate pow per channel
 hipError_t launch_filter(long long n_pixels, float exposure, const double* in, unsigned* out, int type, hipStream_t stream,
                          const float* thresholds = nullptr);
+// the same tone map with the alpha byte of pixel p taken from alpha[p] (n_pixels floats on the device): chunky_filter_frame_alpha
+hipError_t launch_filter_alpha(long long n_pixels, float exposure, const double* in, const float* alpha, unsigned* out, int type,
+                               hipStream_t stream, const float* thresholds);
 // tone map self test: gamma_bytes3 (curve 0) / aces_bytes3 (curve 2) against the reference's arithmetic and a search of the
 // threshold table, for `count` consecutive float bit patterns
 hipError_t launch_gamma_scan(unsigned first, unsigned long long count, int curve, const float* thresholds, unsigned long long* mismatches,

@@ -35,6 +35,8 @@ PEER_LOCAL, PEER_DIRECT, PEER_STAGED = 0, 1, 2
 TRANSPORT_PEER_COPY, TRANSPORT_RCCL_SENDRECV, TRANSPORT_RCCL_REDUCE = 0, 1, 2
 E_INVALID, E_NO_DEVICE, E_HIP, E_STATE, E_ABORTED = -1, -2, -3, -4, -5
 AOV_ALBEDO, AOV_NORMAL = 0, 1  # chunky_render_aov_read
+AOV_ALPHA, AOV_DEPTH, AOV_POSITION, AOV_EMITTANCE, AOV_BLOCK = 2, 3, 4, 5, 6  # chunky_render_aov_read_ex (with the two above)
+AOV_WORDS = {AOV_ALBEDO: 3, AOV_NORMAL: 3, AOV_ALPHA: 1, AOV_DEPTH: 1, AOV_POSITION: 3, AOV_EMITTANCE: 1, AOV_BLOCK: 1}  # words per pixel
 DENOISE_DEMODULATE = 1  # chunky_denoise_params.flags
 DENOISE_KERNEL_SHIFT = 8  # ... bits 8-9: 0 the default kernels (the images as they are), 1 the packed words
 DENOISE_KERNEL_GATHER, DENOISE_KERNEL_PACKED = 0, 1
@@ -225,6 +227,8 @@ def lib() -> C.CDLL:
             "chunky_render_aov_reset": [vp],
             "chunky_render_aov_kernel_time": [vp, C.POINTER(f32), C.POINTER(C.c_int)],
             "chunky_render_aov_kernel_info": [vp, vp],
+            "chunky_render_aov_passes_ex": [vp, vp, C.c_int, C.c_int],
+            "chunky_render_aov_read_ex": [vp, C.c_int, vp, i64],
             "chunky_denoise_default_params": [C.POINTER(DenoiseParams)],
             "chunky_denoise_host": [C.c_int, C.c_int, vp, vp, vp, C.POINTER(DenoiseParams), vp],
             "chunky_denoise_frame": [vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(DenoiseParams), vp],
@@ -256,6 +260,8 @@ def lib() -> C.CDLL:
             "chunky_camera_rays": [C.c_int, vp, i64, C.c_int, C.c_int, i32, vp],
             "chunky_camera_rays_lens": [C.c_int, vp, i64, C.c_int, C.c_int, i32, f32, f32, vp],
             "chunky_filter_frame": [vp, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int],
+            "chunky_filter_frame_alpha": [vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, C.c_int],
+            "chunky_filter_alpha_bytes": [vp, i64, vp],
             "chunky_filter_gamma_thresholds": [vp],
             "chunky_filter_frame_device": [vp, i64, f32, vp, vp, C.c_int, C.c_int, C.POINTER(f32)],
             "chunky_widetree_lookup": [vp, i64, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(i64)],
@@ -298,6 +304,14 @@ def camera_rays(projector_type: int, settings, width: int, height: int, seed: in
         check(lib().chunky_camera_rays(int(projector_type), ptr(s), s.size, int(width), int(height), seed32, ptr(out)))
     else:
         check(lib().chunky_camera_rays_lens(int(projector_type), ptr(s), s.size, int(width), int(height), seed32, float(lens[0]), float(lens[1]), ptr(out)))
+    return out
+
+
+def filter_alpha_bytes(alpha) -> np.ndarray:
+    """chunky_filter_alpha_bytes: the alpha byte chunky_filter_frame_alpha writes for each value, on the host (no device needed)."""
+    a = np.ascontiguousarray(alpha, np.float32).reshape(-1)
+    out = np.zeros(a.size, np.int32)
+    check(lib().chunky_filter_alpha_bytes(ptr(a), a.size, ptr(out)))
     return out
 
 

@@ -368,6 +368,23 @@ class HipPathTracingRenderer:
         check(native.lib().chunky_render_aov_kernel_info(self._h, ptr(out)))
         return {"tree": int(out[0]), "bvh": bool(out[1]), "blocks": int(out[2]), "launches": int(out[3])}
 
+    # --- the first-hit images beside them (chunky_render_aov_passes_ex / _read_ex) -------------------
+    def render_aov_ex(self, seeds, first_buffer_spp: int = 0, sync: bool = True) -> None:
+        """render_aov with coverage, depth, position, emittance and block id folded from the same trace (all seven images)."""
+        s = np.ascontiguousarray(seeds, np.int32)
+        check(native.lib().chunky_render_aov_passes_ex(self._h, ptr(s), s.size, first_buffer_spp))
+        if sync:
+            self.sync()
+
+    def read_aov_ex(self, which: int) -> np.ndarray:
+        """One of the seven images (native.AOV_ALBEDO .. native.AOV_BLOCK): (height, width, 3) float32 for albedo, normal and
+        position, (height, width) float32 for alpha, depth and emittance, (height, width) int32 for the block id."""
+        words = native.AOV_WORDS.get(int(which), 1)  # (an unknown image: the library refuses it)
+        shape = (self.height, self.width, 3) if words == 3 else (self.height, self.width)
+        out = np.empty(shape, np.int32 if which == native.AOV_BLOCK else np.float32)
+        check(native.lib().chunky_render_aov_read_ex(self._h, int(which), ptr(out), out.size))
+        return out
+
     # --- denoising (chunky_render_denoise) ------------------------------------------------------------
     def denoise(self, params=None) -> np.ndarray:
         """The framebuffer filtered with this target's AOV images, all on the device; only the (height, width, 3) result is read
@@ -541,6 +558,19 @@ class HipPostProcessingFilter:
             raise ValueError("output must be a contiguous int32 array of width*height pixels")
         check(native.lib().chunky_filter_frame(self.instance._h, width, height, float(exposure), ptr(input_samples),
                                                ptr(output_argb), self.type))
+
+    def process_frame_alpha(self, width: int, height: int, input_samples: np.ndarray, alpha: np.ndarray, output_argb: np.ndarray,
+                            exposure: float) -> None:
+        """process_frame with the alpha byte of each pixel from `alpha` (width*height float32, e.g. read_aov_ex(native.AOV_ALPHA)):
+        chunky_filter_frame_alpha."""
+        if input_samples.dtype != np.float64 or input_samples.size != 3 * width * height or not input_samples.flags.c_contiguous:
+            raise ValueError("input must be a contiguous float64 array of width*height*3 samples")
+        if alpha.dtype != np.float32 or alpha.size != width * height or not alpha.flags.c_contiguous:
+            raise ValueError("alpha must be a contiguous float32 array of width*height values")
+        if output_argb.dtype not in (np.int32, np.uint32) or output_argb.size != width * height or not output_argb.flags.c_contiguous:
+            raise ValueError("output must be a contiguous int32 array of width*height pixels")
+        check(native.lib().chunky_filter_frame_alpha(self.instance._h, width, height, float(exposure), ptr(input_samples), ptr(alpha),
+                                                     ptr(output_argb), self.type))
 
     def process_device(self, n_pixels: int, exposure: float, d_input: int, d_argb: int, repeat: int = 1) -> float:
         """The same kernel on device buffers; returns the mean kernel time in ms (HIP events)."""

@@ -392,6 +392,50 @@ int chunky_render_aov_kernel_time(chunky_render* r, float* total_ms, int* launch
  * workgroups launched, launches made by the most recent chunky_render_aov_passes}. */
 int chunky_render_aov_kernel_info(chunky_render* r, int32_t out4[4]);
 
+/* ---- five more images of the same first hit, for compositing: coverage ("transparent sky"), depth, position, emittance and the
+ * block hit.  The sample is exactly the AOV sample above, and `rec` is record 0 of chunky_render_trace_records for it:
+ *
+ *   image                  words per pixel   sample on a hit                       on a miss
+ *   CHUNKY_AOV_ALPHA       1 float           1.0f                                  0.0f
+ *   CHUNKY_AOV_DEPTH       1 float           rec.distance                          0.0f
+ *   CHUNKY_AOV_POSITION    3 floats          rec.point = o + d * (distance - OFFSET)   (0, 0, 0)
+ *   CHUNKY_AOV_EMITTANCE   1 float           rec.emittance                         0.0f
+ *   CHUNKY_AOV_BLOCK       1 int32           rec.material                          -1
+ *
+ * The four float images are folded like albedo and normal: (img * spp + v) / (spp + 1) in float, in pass order.  A miss folds a 0,
+ * so DEPTH, POSITION and EMITTANCE are hit-weighted sums over the passes, divided by the pass count: the mean over the samples
+ * that hit is image / ALPHA (where ALPHA > 0).  BLOCK is not averaged: every pass overwrites it, so it holds the value of the last
+ * pass folded.
+ * DEPTH is the reference's ray parameter t of the hit (hit = o + d * t), so its unit is the length of the camera ray's direction d:
+ *  - the projected cameras (CHUNKY_PROJ_PARALLEL .. CHUNKY_PROJ_ODS_STACKED, with or without a lens) normalise d: DEPTH is the
+ *    distance from the ray's origin in blocks (to float rounding, and given the orthonormal matrix a camera has);
+ *  - the pinhole camera (type 0) does not (K/camera.h:19): without a lens d = m * (fovTan x, fovTan y, 1), so DEPTH is the depth
+ *    along the view axis (planar z), not the distance; with a lens (aperture > 0) d's view-axis component is subjectDistance, and
+ *    DEPTH * subjectDistance is that planar depth;
+ *  - pre-generated rays (type -1) have the length their table gives them.
+ * POSITION is in world units (blocks, octree coordinates) for every camera.
+ * BLOCK is rec.material: for a block hit, the octree leaf's value for that block (its offset in the block palette, K/octree.h:88).
+ * The entity BVHs never write that field (K/bvh.h), so for an entity hit it is what the octree part of the same trace left there:
+ * the block the ray would have hit behind the entity, or 0 where the octree missed.
+ * chunky_render_aov_passes_ex folds all seven images (albedo, normal and these five) from one trace per sample; albedo and normal
+ * after it are, bit for bit, what chunky_render_aov_passes gives with the same arguments.  The five images are allocated, zeroed, by
+ * the first _ex call on a target, and chunky_render_aov_reset zeroes them too where they exist.  chunky_render_aov_passes never
+ * touches them: a host that mixes the two calls lets the five images lag behind albedo and normal.  Shards and groups as for the
+ * AOV; chunky_render_aov_kernel_time / _kernel_info cover _ex launches as they cover AOV launches. */
+#define CHUNKY_AOV_ALPHA 2
+#define CHUNKY_AOV_DEPTH 3
+#define CHUNKY_AOV_POSITION 4
+#define CHUNKY_AOV_EMITTANCE 5
+#define CHUNKY_AOV_BLOCK 6
+/* Enqueue n passes over all seven images (asynchronous; cut into launches of at most 256 passes, which changes no bit).
+ * CHUNKY_E_STATE before chunky_render_set_camera. */
+int chunky_render_aov_passes_ex(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp);
+/* Blocking read-back of one image, which = CHUNKY_AOV_ALBEDO .. CHUNKY_AOV_BLOCK; n_words = width*height times the words per pixel
+ * of the image (3 for albedo, normal and position, else 1; floats, int32 for CHUNKY_AOV_BLOCK).  CHUNKY_E_STATE before the first
+ * _ex pass for which >= CHUNKY_AOV_ALPHA (before any AOV pass for the other two); CHUNKY_E_INVALID for an unknown image or a
+ * wrong count. */
+int chunky_render_aov_read_ex(chunky_render* r, int which, void* out, int64_t n_words);
+
 /* ---- denoising (no reference counterpart): an edge-avoiding À-Trous wavelet filter (Dammertz et al. 2010) guided by the albedo
  * and normal images above.  Closed-form and deterministic; the exact arithmetic is chunkyclplugin_amd/csrc/denoise_spec.h, which the
  * kernels and chunky_denoise_host both compile, so the device result equals the host's bit for bit.
@@ -680,6 +724,13 @@ int chunky_java_random_ints(int64_t seed, int32_t* out, int n);
 #define CHUNKY_FILTER_HABLE 3
 int chunky_filter_frame(chunky_ctx* ctx, int width, int height, double exposure, const double* input,
                         int32_t* argb_out, int type);
+/* The same tone map with the alpha byte of pixel p taken from alpha[p] (width*height floats, e.g. the CHUNKY_AOV_ALPHA image:
+ * Chunky's "transparent sky") instead of 0xFF: the byte is min(255, (uint)(clamp(alpha, 0, 1) * 255.0f + 0.5f)), 0 for a NaN.
+ * R, G and B are byte-identical to chunky_filter_frame's. */
+int chunky_filter_frame_alpha(chunky_ctx* ctx, int width, int height, double exposure, const double* input, const float* alpha,
+                              int32_t* argb_out, int type);
+/* Host-side instrument (no device needed): that alpha byte for each of n values, from the function the kernel compiles. */
+int chunky_filter_alpha_bytes(const float* alpha, int64_t n, int32_t* out);
 /* Host-side instrument (no device needed): the 256 thresholds the GAMMA / ACES curves are evaluated with — T[k] = the smallest
  * float c >= 0 whose output byte min(255, (uint)(pow(c, 1/2.2) * 255 + 0.5)) is >= k (post_processing_filter.cl:24-27,
  * rgba.h:9-14).  The byte is a monotone step function of c, so comparing c with these is the same function as evaluating

@@ -12,7 +12,12 @@ For N = 16 and 256 passes per call: one warm-up call of each kind, then three al
 the library's HIP-event accessors (chunky_render_kernel_time / chunky_render_aov_kernel_time).  One JSON line per view and N:
 Msamples/s of each kernel (median of the repeats, and all three), their ratio and both instantiations.
 
-    python tools/aov_bench.py [names...] > profiles/aov_bench.jsonl"""
+    python tools/aov_bench.py [names...] > profiles/aov_bench.jsonl
+
+With --ex the two kinds are chunky_render_aov_passes and chunky_render_aov_passes_ex (all seven first-hit images from the same trace,
+DESIGN.md section 14) instead, alternating in the same way; one JSON line per view and N with both rates and ex / plain:
+
+    python tools/aov_bench.py --ex [names...] > profiles/aov_ex_bench.jsonl"""
 import json
 import os
 import sys
@@ -72,7 +77,33 @@ def bench(name, sc, r, n):
             "device": RendererInstance.get(0).device_name()}
 
 
+def bench_ex(name, sc, r, n):
+    seeds = native.java_random_ints(n)
+    samples = sc.width * sc.height * n
+    r.render_aov(seeds)  # warm-up
+    r.render_aov_ex(seeds)
+    r.aov_kernel_time()
+    plain_ms, ex_ms = [], []
+    info = {}
+    for k in range(REPEATS):
+        for kind, call, ms_list in (("aov_kernel", r.render_aov, plain_ms), ("ex_kernel", r.render_aov_ex, ex_ms)):
+            call(seeds, first_buffer_spp=n * (k + 1))
+            ms_list.append(r.aov_kernel_time()[0])
+            ai = r.aov_info()
+            info[kind] = {"tree": ai["tree"], "bvh": ai["bvh"], "workgroups": ai["blocks"], "launches": ai["launches"]}
+    rate = lambda ms: samples / (ms * 1e3)  # noqa: E731  (Msamples/s)
+    plain_rate, ex_rate = [rate(ms) for ms in plain_ms], [rate(ms) for ms in ex_ms]
+    return {"view": name, "width": sc.width, "height": sc.height, "passes": n,
+            "aov_msamples_s": float(np.median(plain_rate)), "ex_msamples_s": float(np.median(ex_rate)),
+            "ex_over_aov": float(np.median(ex_rate) / np.median(plain_rate)),
+            "aov_msamples_s_runs": [round(x, 1) for x in plain_rate], "ex_msamples_s_runs": [round(x, 1) for x in ex_rate],
+            "aov_ms_runs": [round(x, 3) for x in plain_ms], "ex_ms_runs": [round(x, 3) for x in ex_ms],
+            **info, "device": RendererInstance.get(0).device_name()}
+
+
 def main(names):
+    ex = "--ex" in names
+    names = [n for n in names if n != "--ex"] or VIEWS
     for name in names:
         sc = view(name)
         loader = HipSceneLoader(RendererInstance.get(0))
@@ -80,7 +111,7 @@ def main(names):
         r = HipPathTracingRenderer(loader, sc.width, sc.height)
         r.set_camera(sc.projector_type, sc.camera)
         for n in PASSES:
-            print(json.dumps(bench(name, sc, r, n)), flush=True)
+            print(json.dumps((bench_ex if ex else bench)(name, sc, r, n)), flush=True)
         r.close()
         loader.close()
 
