@@ -150,7 +150,7 @@ struct chunky_render {
     DevBuf staging;  // render_pool: one launch's samples, [tile of 256 slots][pass][slot][3] floats
     DevBuf block_list;  // block shards under a kernel without the block mapping: this rank's pixels (ShardView::list)
     float* fb = nullptr;
-    std::vector<hipEvent_t> free_events;  // the one pool the four clocks below borrow from
+    std::vector<hipEvent_t> free_events;  // the one pool the five clocks below borrow from
     LaunchClock clock{&free_events};      // the render launches (chunky_render_kernel_time)
     KernelChoice last_choice{0, 0, 0, 0, -1, 0};  // what the most recent launch ran (chunky_render_kernel_info)
     int launch_cap = 0;  // most passes one launch carries here (staging size); 0 = not determined yet
@@ -179,6 +179,14 @@ struct chunky_render {
     LaunchClock aov_clock{&free_events};
     AovChoice aov_choice{0, 0, 0};
     int aov_last_launches = 0;  // launches of the most recent chunky_render_aov_passes
+    // chunky_render_matte_passes: 13 planes of width * height int32 (six of ids, six of counts, `other`), then the kernel's claim
+    // counter; allocated (and zeroed) by the first matte call.  matte_work holds a read-out on its way to the host (ranks: 12 planes;
+    // extract: one) and matte_set the sorted ids of an extract.  Clock, choice and counter are its own: the AOV calls do not see them
+    DevBuf matte, matte_work, matte_set;
+    LaunchClock matte_clock{&free_events};
+    AovChoice matte_choice{0, 0, 0};
+    int matte_last_launches = 0;  // launches of the most recent chunky_render_matte_passes
+    int32_t matte_passes = 0;     // passes folded since the last reset
     // chunky_render_denoise: the filter's workspace (kept between calls) and its timing, apart from the render and AOV launches'
     DevBuf dn_work, dn_out;
     LaunchClock dn_clock{&free_events};  // (a bracket holds all launches of one call: their number is its weight)

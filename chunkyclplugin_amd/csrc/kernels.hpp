@@ -1,5 +1,5 @@
 // kernels.hpp — host-visible launch interface of the kernel translation units (render_pool.hip, render_fallback.hip,
-// aux_kernels.hip, filter.hip, aov.hip, denoise.hip, adaptive.hip).
+// aux_kernels.hip, filter.hip, aov.hip, matte.hip, denoise.hip, adaptive.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -126,6 +126,14 @@ struct AovExImages {
 // launch_aov with the five first-hit images folded from the same trace
 hipError_t launch_aov_ex(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
                          const AovExImages& I, int* counter, hipStream_t stream, AovChoice* chosen);
+// ID-matte passes (matte.hip; specification: matte_spec.h): P.n <= kMaxPassesPerLaunch; `planes` is 13 * width * height ints (six planes of
+// ids, six of counts, `other`), updated in place over the pixel slots of shard T; `counter` as launch_aov's.  The choice record is the AOV's.
+hipError_t launch_matte(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
+                        int* planes, int* counter, hipStream_t stream, AovChoice* chosen);
+// the ranks of every pixel (out_ids, out_coverage: 6 * n_pixels words each, plane-major) and the mask of a set of ids (sorted: ascending,
+// each value once, n_set of them on the device; out: n_pixels floats); passes > 0
+hipError_t launch_matte_ranks(const int* planes, long long n_pixels, int passes, int* out_ids, float* out_coverage, hipStream_t stream);
+hipError_t launch_matte_extract(const int* planes, long long n_pixels, int passes, const int* sorted, int n_set, float* out, hipStream_t stream);
 // The À-Trous denoiser (denoise.hip; specification: denoise_spec.h).  color / albedo / normal / out: 3 * width * height floats on the
 // device (out may not alias an input); `work`: denoise_work_bytes of device memory, 16-byte aligned, the launch's own while it runs.
 // One launch per iteration plus the pack (or demodulation) pass, all on `stream`; *launches receives their number.  `form` picks how taps

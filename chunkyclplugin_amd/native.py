@@ -18,9 +18,9 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("CHUNKY_HIP_LIB") or os.path.join(PKG_DIR, "libchunky_hip.so")  # override: tuning builds (tools/variants.sh)
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
-SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "denoise.hip", "adaptive.hip",
-           "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_adaptive.hip", "capi_denoise.hip",
-           "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "adaptive_host.cpp", "denoise_host.cpp",
+SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "matte.hip", "denoise.hip", "adaptive.hip",
+           "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_matte.hip", "capi_adaptive.hip", "capi_denoise.hip",
+           "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp",
            "scene_records.cpp", "widetree.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
 
@@ -37,6 +37,8 @@ E_INVALID, E_NO_DEVICE, E_HIP, E_STATE, E_ABORTED = -1, -2, -3, -4, -5
 AOV_ALBEDO, AOV_NORMAL = 0, 1  # chunky_render_aov_read
 AOV_ALPHA, AOV_DEPTH, AOV_POSITION, AOV_EMITTANCE, AOV_BLOCK = 2, 3, 4, 5, 6  # chunky_render_aov_read_ex (with the two above)
 AOV_WORDS = {AOV_ALBEDO: 3, AOV_NORMAL: 3, AOV_ALPHA: 1, AOV_DEPTH: 1, AOV_POSITION: 3, AOV_EMITTANCE: 1, AOV_BLOCK: 1}  # words per pixel
+MATTE_SLOTS = 6  # CHUNKY_MATTE_*: slots per pixel, the ids of a miss and of the two entity BVHs, the id an empty rank reports
+MATTE_SKY, MATTE_WORLD_ENTITY, MATTE_ACTOR_ENTITY, MATTE_EMPTY = -1, -2, -3, -2 ** 31
 DENOISE_DEMODULATE = 1  # chunky_denoise_params.flags
 DENOISE_KERNEL_SHIFT = 8  # ... bits 8-9: 0 the default kernels (the images as they are), 1 the packed words
 DENOISE_KERNEL_GATHER, DENOISE_KERNEL_PACKED = 0, 1
@@ -229,6 +231,18 @@ def lib() -> C.CDLL:
             "chunky_render_aov_kernel_info": [vp, vp],
             "chunky_render_aov_passes_ex": [vp, vp, C.c_int, C.c_int],
             "chunky_render_aov_read_ex": [vp, C.c_int, vp, i64],
+            "chunky_render_matte_passes": [vp, vp, C.c_int],
+            "chunky_render_matte_reset": [vp],
+            "chunky_render_matte_read": [vp, vp, vp, vp, i64, C.POINTER(i32)],
+            "chunky_render_matte_restore": [vp, vp, vp, vp, i64, i32],
+            "chunky_render_matte_ranks": [vp, vp, vp, i64],
+            "chunky_render_matte_extract": [vp, vp, C.c_int, vp, i64],
+            "chunky_render_matte_kernel_time": [vp, C.POINTER(f32), C.POINTER(C.c_int)],
+            "chunky_render_matte_kernel_info": [vp, vp],
+            "chunky_matte_host_fold": [vp, C.c_int, i64, vp, vp, vp],
+            "chunky_matte_host_ranks": [vp, vp, i64, i32, vp, vp],
+            "chunky_matte_host_extract": [vp, vp, i64, i32, vp, C.c_int, vp],
+            "chunky_matte_state_check": [vp, vp, vp, i64, i32],
             "chunky_denoise_default_params": [C.POINTER(DenoiseParams)],
             "chunky_denoise_host": [C.c_int, C.c_int, vp, vp, vp, C.POINTER(DenoiseParams), vp],
             "chunky_denoise_frame": [vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(DenoiseParams), vp],
@@ -418,6 +432,46 @@ def adaptive_host(samples, params: Optional[AdaptiveParams] = None):
     stat = np.zeros((h, w, 2), np.float32)
     check(lib().chunky_adaptive_host(w, h, ptr(s), n, C.byref(p), ptr(counts), ptr(mean), ptr(stat)))
     return counts, mean, stat
+
+
+def matte_host_fold(sample_ids, state=None):
+    """chunky_matte_host_fold: the ID-matte state after the samples sample_ids (n_passes, n_pixels) int32, continued from `state` =
+    (ids (6, n_pixels), counts (6, n_pixels), other (n_pixels,)) or from the empty state.  Returns new arrays (no device needed)."""
+    s = np.ascontiguousarray(sample_ids, np.int32)
+    if s.ndim != 2:
+        raise ValueError(f"expected sample ids of shape (n_passes, n_pixels), got {s.shape}")
+    n = s.shape[1]
+    if state is None:
+        ids, counts, other = np.zeros((MATTE_SLOTS, n), np.int32), np.zeros((MATTE_SLOTS, n), np.int32), np.zeros(n, np.int32)
+    else:
+        ids, counts, other = (np.array(a, np.int32, order="C") for a in state)
+    check(lib().chunky_matte_host_fold(ptr(s), s.shape[0], n, ptr(ids), ptr(counts), ptr(other)))
+    return ids, counts, other
+
+
+def matte_host_ranks(ids, counts, passes: int):
+    """chunky_matte_host_ranks: (ids (6, n_pixels) int32, coverage (6, n_pixels) float32) by rank."""
+    i, c = np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(counts, np.int32)
+    n = i.shape[-1]
+    out_ids, out_cov = np.zeros((MATTE_SLOTS, n), np.int32), np.zeros((MATTE_SLOTS, n), np.float32)
+    check(lib().chunky_matte_host_ranks(ptr(i), ptr(c), n, int(passes), ptr(out_ids), ptr(out_cov)))
+    return out_ids, out_cov
+
+
+def matte_host_extract(ids, counts, passes: int, id_set) -> np.ndarray:
+    """chunky_matte_host_extract: the (n_pixels,) float32 mask of the ids in id_set."""
+    i, c = np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(counts, np.int32)
+    st = np.ascontiguousarray(id_set, np.int32).reshape(-1)
+    n = i.shape[-1]
+    out = np.zeros(n, np.float32)
+    check(lib().chunky_matte_host_extract(ptr(i), ptr(c), n, int(passes), ptr(st) if st.size else None, st.size, ptr(out)))
+    return out
+
+
+def matte_state_check(ids, counts, other, passes: int) -> int:
+    """chunky_matte_state_check: the status (0, or E_INVALID with the rule in chunky_last_error)."""
+    i, c, o = (np.ascontiguousarray(a, np.int32) for a in (ids, counts, other))
+    return lib().chunky_matte_state_check(ptr(i), ptr(c), ptr(o), o.size, int(passes))
 
 
 def adaptive_summary_dict(summ: AdaptiveSummary) -> dict:

@@ -385,6 +385,60 @@ class HipPathTracingRenderer:
         check(native.lib().chunky_render_aov_read_ex(self._h, int(which), ptr(out), out.size))
         return out
 
+    # --- antialiased ID mattes (chunky_render_matte_*) ------------------------------------------------
+    def render_matte(self, seeds, sync: bool = True) -> None:
+        """Matte passes: pass k traces the first ray of the render pass with seeds[k] and counts the id it hits, per pixel."""
+        s = np.ascontiguousarray(seeds, np.int32)
+        check(native.lib().chunky_render_matte_passes(self._h, ptr(s), s.size))
+        if sync:
+            self.sync()
+
+    def read_matte(self):
+        """The matte state: (ids (6, height, width) int32, counts (6, height, width) int32, other (height, width) int32, passes)."""
+        shape = (native.MATTE_SLOTS, self.height, self.width)
+        ids, counts, other = np.empty(shape, np.int32), np.empty(shape, np.int32), np.empty(shape[1:], np.int32)
+        passes = C.c_int32()
+        check(native.lib().chunky_render_matte_read(self._h, ptr(ids), ptr(counts), ptr(other), other.size, C.byref(passes)))
+        return ids, counts, other, passes.value
+
+    def restore_matte(self, ids, counts, other, passes: int) -> None:
+        """Replaces the matte state with one read_matte returned (a resumed render); a malformed state is refused and nothing changes."""
+        i, c, o = (np.ascontiguousarray(a, np.int32) for a in (ids, counts, other))
+        if i.size != native.MATTE_SLOTS * o.size or c.size != i.size:
+            raise ValueError(f"expected ids and counts of {native.MATTE_SLOTS} planes of other's size, got {i.shape}, {c.shape}, {o.shape}")
+        check(native.lib().chunky_render_matte_restore(self._h, ptr(i), ptr(c), ptr(o), o.size, int(passes)))
+
+    def matte_ranks(self):
+        """(ids (6, height, width) int32, coverage (6, height, width) float32): per pixel the ids by share of the passes, descending;
+        empty ranks hold native.MATTE_EMPTY and 0."""
+        shape = (native.MATTE_SLOTS, self.height, self.width)
+        ids, cov = np.empty(shape, np.int32), np.empty(shape, np.float32)
+        check(native.lib().chunky_render_matte_ranks(self._h, ptr(ids), ptr(cov), self.width * self.height))
+        return ids, cov
+
+    def matte_extract(self, id_set) -> np.ndarray:
+        """The (height, width) float32 mask of a set of ids: the share of each pixel's passes that saw one of them — what
+        HipPostProcessingFilter.process_frame_alpha takes as alpha."""
+        st = np.ascontiguousarray(id_set, np.int32).reshape(-1)
+        out = np.empty((self.height, self.width), np.float32)
+        check(native.lib().chunky_render_matte_extract(self._h, ptr(st) if st.size else None, st.size, ptr(out), out.size))
+        return out
+
+    def reset_matte(self) -> None:
+        check(native.lib().chunky_render_matte_reset(self._h))
+
+    def matte_kernel_time(self):
+        """(milliseconds, launches) of the matte-pass kernel since the last call."""
+        ms, n = C.c_float(), C.c_int()
+        check(native.lib().chunky_render_matte_kernel_time(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def matte_info(self) -> dict:
+        """The instantiation the last matte launch ran: tree form, entity-BVH walk, workgroups, launches of the last call."""
+        out = np.zeros(4, np.int32)
+        check(native.lib().chunky_render_matte_kernel_info(self._h, ptr(out)))
+        return {"tree": int(out[0]), "bvh": bool(out[1]), "blocks": int(out[2]), "launches": int(out[3])}
+
     # --- denoising (chunky_render_denoise) ------------------------------------------------------------
     def denoise(self, params=None) -> np.ndarray:
         """The framebuffer filtered with this target's AOV images, all on the device; only the (height, width, 3) result is read

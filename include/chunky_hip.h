@@ -405,7 +405,7 @@ int chunky_render_aov_kernel_info(chunky_render* r, int32_t out4[4]);
  * The four float images are folded like albedo and normal: (img * spp + v) / (spp + 1) in float, in pass order.  A miss folds a 0,
  * so DEPTH, POSITION and EMITTANCE are hit-weighted sums over the passes, divided by the pass count: the mean over the samples
  * that hit is image / ALPHA (where ALPHA > 0).  BLOCK is not averaged: every pass overwrites it, so it holds the value of the last
- * pass folded.
+ * pass folded.  For antialiased masks use the ID mattes below (chunky_render_matte_passes), which count every pass's id per pixel.
  * DEPTH is the reference's ray parameter t of the hit (hit = o + d * t), so its unit is the length of the camera ray's direction d:
  *  - the projected cameras (CHUNKY_PROJ_PARALLEL .. CHUNKY_PROJ_ODS_STACKED, with or without a lens) normalise d: DEPTH is the
  *    distance from the ray's origin in blocks (to float rounding, and given the orthonormal matrix a camera has);
@@ -435,6 +435,85 @@ int chunky_render_aov_passes_ex(chunky_render* r, const int32_t* seeds, int n, i
  * _ex pass for which >= CHUNKY_AOV_ALPHA (before any AOV pass for the other two); CHUNKY_E_INVALID for an unknown image or a
  * wrong count. */
 int chunky_render_aov_read_ex(chunky_render* r, int which, void* out, int64_t n_words);
+
+/* ---- antialiased ID mattes (no reference counterpart; the idea of Cryptomatte): per pixel a short list of (id, the number of passes
+ * that saw it), counted over the same camera rays the beauty passes use, so that a mask for any set of ids is a sum of shares and
+ * lines up with the antialiased image.  The exact arithmetic is chunkyclplugin_amd/csrc/matte_spec.h, which the kernels and the
+ * chunky_matte_host_* twins both compile: counts are integers, and the result does not depend on how the passes are cut into calls
+ * or launches.
+ *
+ * The sample of pass k at pixel gid is exactly the AOV sample above: seeds[k], RNG state seed + gid advanced once, the camera ray
+ * of the target's camera (with its aperture or lens), one closestIntersect with the target's draw depth and
+ * CHUNKY_OPT_BVH_CULL_BEHIND.  closestIntersect runs the octree, then the world BVH, then the actor BVH, and a later part wins only
+ * with a strictly smaller distance.  The id of the sample names the last part that won:
+ *
+ *   nothing hit                      CHUNKY_MATTE_SKY
+ *   the octree's block stands        rec.material (>= 0: the block's offset in the block palette, as CHUNKY_AOV_BLOCK for a block hit)
+ *   a world-BVH triangle won         CHUNKY_MATTE_WORLD_ENTITY
+ *   an actor-BVH triangle won        CHUNKY_MATTE_ACTOR_ENTITY
+ *
+ * (Unlike CHUNKY_AOV_BLOCK, an entity hit never reports the block behind it.)
+ *
+ * A pixel's state is CHUNKY_MATTE_SLOTS slots of (int32 id, int32 count) and one int32 `other`: 13 words, 52 bytes.  A slot with
+ * count 0 is empty.  A sample with id v goes to the first occupied slot that holds v (count + 1), else to the first empty slot
+ * (id = v, count = 1), else to `other` (+ 1).  Slots fill in arrival order and are never evicted; passes apply in call order; the sky
+ * takes a slot like any id; the counts of a pixel and its `other` add up to the passes folded into it.  The passes on a target since
+ * its last reset may not exceed 2^31 - 1.
+ *
+ * Layout: `ids` and `counts` are plane-major — slot (or rank) s of pixel gid is at [s * n_pixels + gid], six images each, with
+ * n_pixels = width * height; `other`, a mask and every other per-pixel array hold one word per pixel.
+ *
+ * The planes are allocated, zeroed, by the first matte call on a target.  The render, AOV, denoise and adaptive calls never see them
+ * and the matte calls never see theirs.  A set shard limits the passes to the rank's pixels; the others stay empty.  On a group's
+ * render target member 0 renders the caller's whole share, as for the AOV.  The Java binding does not reach these calls. */
+#define CHUNKY_MATTE_SLOTS 6
+#define CHUNKY_MATTE_SKY (-1)
+#define CHUNKY_MATTE_WORLD_ENTITY (-2)
+#define CHUNKY_MATTE_ACTOR_ENTITY (-3)
+#define CHUNKY_MATTE_EMPTY INT32_MIN
+/* Enqueue n matte passes (asynchronous, like chunky_render_aov_passes; cut into launches of at most 256 passes, which changes no
+ * word).  CHUNKY_E_STATE before chunky_render_set_camera; CHUNKY_E_INVALID, before any launch, when the target's passes would
+ * exceed 2^31 - 1. */
+int chunky_render_matte_passes(chunky_render* r, const int32_t* seeds, int n);
+/* Empty every slot and set the pass count to 0. */
+int chunky_render_matte_reset(chunky_render* r);
+/* Blocking read-back of the state: ids and counts 6 * n_pixels words each, other n_pixels, *passes the passes since the last reset.
+ * Waits for the queued passes.  CHUNKY_E_INVALID for a null pointer or n_pixels != width * height. */
+int chunky_render_matte_read(chunky_render* r, int32_t* ids, int32_t* counts, int32_t* other, int64_t n_pixels, int32_t* passes);
+/* Replace the state with one read earlier (a resumed render).  The state is checked with chunky_matte_state_check first:
+ * CHUNKY_E_INVALID, and nothing changed, when it fails. */
+int chunky_render_matte_restore(chunky_render* r, const int32_t* ids, const int32_t* counts, const int32_t* other, int64_t n_pixels,
+                                int32_t passes);
+/* The read-out for a Cryptomatte-style export: per pixel the slots by count descending, ties by the lower slot index.  Rank j gets
+ * ids[j * n_pixels + gid] and coverage[...] = (float)count / (float)passes (each conversion rounds to nearest; one division); empty
+ * slots come last with CHUNKY_MATTE_EMPTY and 0.0f, so a pixel outside the target's shard reads as six empty ranks.  Computed on the
+ * device; waits for the queued passes.  CHUNKY_E_STATE while the target has no pass; CHUNKY_E_INVALID as chunky_render_matte_read. */
+int chunky_render_matte_ranks(chunky_render* r, int32_t* ids, float* coverage, int64_t n_pixels);
+/* A mask for a set of ids (any order; duplicates count once; n_set = 0 is the empty set): out[gid] = (float)(the sum of the counts
+ * of the pixel's occupied slots whose id is in the set) / (float)passes — an integer sum and one division.  `other` is attributed to
+ * no id: where it is not 0 (chunky_render_matte_read) masks undercount.  out has the layout chunky_filter_frame_alpha takes as
+ * alpha.  Computed on the device; waits for the queued passes.  CHUNKY_E_STATE while the target has no pass; CHUNKY_E_INVALID for
+ * n_set < 0, a null pointer, a wrong n_pixels or CHUNKY_MATTE_EMPTY in the set. */
+int chunky_render_matte_extract(chunky_render* r, const int32_t* set, int n_set, float* out, int64_t n_pixels);
+/* Device time of the matte-pass launches enqueued since the last call (as chunky_render_aov_kernel_time; the AOV's timer does not
+ * see them, nor this one the AOV's). */
+int chunky_render_matte_kernel_time(chunky_render* r, float* total_ms, int* launches);
+/* The instantiation the most recent matte launch ran: the four words of chunky_render_aov_kernel_info. */
+int chunky_render_matte_kernel_info(chunky_render* r, int32_t out4[4]);
+/* The same arithmetic on the host (plain C++, no device needed), on states in the layout above.
+ * _host_fold continues the state passed in with n_passes samples per pixel, sample_ids[pass * n_pixels + gid], in pass order.
+ * _host_ranks and _host_extract are chunky_render_matte_ranks / _extract of a state after `passes` passes.  CHUNKY_E_INVALID for
+ * null pointers, n_pixels <= 0, passes <= 0 (ranks, extract), negative counts, counts that add up to more than `passes` (or, for the
+ * fold, that would pass 2^31 - 1), and CHUNKY_MATTE_EMPTY as a sample's id or in the set. */
+int chunky_matte_host_fold(const int32_t* sample_ids, int n_passes, int64_t n_pixels, int32_t* ids, int32_t* counts, int32_t* other);
+int chunky_matte_host_ranks(const int32_t* ids, const int32_t* counts, int64_t n_pixels, int32_t passes, int32_t* out_ids,
+                            float* out_coverage);
+int chunky_matte_host_extract(const int32_t* ids, const int32_t* counts, int64_t n_pixels, int32_t passes, const int32_t* set, int n_set,
+                              float* out);
+/* CHUNKY_OK when the state is one the fold can have left after `passes` passes (passes >= 0), else CHUNKY_E_INVALID with the rule
+ * in chunky_last_error: counts >= 0 and other >= 0; a pixel's occupied slots contiguous from slot 0; no id twice among them; no
+ * CHUNKY_MATTE_EMPTY in an occupied slot; per pixel the counts and `other` add up to 0 (a pixel outside the shard) or to passes. */
+int chunky_matte_state_check(const int32_t* ids, const int32_t* counts, const int32_t* other, int64_t n_pixels, int32_t passes);
 
 /* ---- denoising (no reference counterpart): an edge-avoiding À-Trous wavelet filter (Dammertz et al. 2010) guided by the albedo
  * and normal images above.  Closed-form and deterministic; the exact arithmetic is chunkyclplugin_amd/csrc/denoise_spec.h, which the
