@@ -117,7 +117,9 @@ int chunky_scene_destroy(chunky_scene* scene);
  *     unknown model type (K/block.h:44-47);
  *   - an entity BVH whose leaves leave the triangle palette, or whose triangles' materials leave the material palette, makes
  *     chunky_render_passes / _run / _preview fail with CHUNKY_E_INVALID.
- * Well-formed data is unaffected.  The palettes may arrive in any order; the checks run when a render call first sees them together. */
+ * Well-formed data is unaffected.  The palettes may arrive in any order; the checks run when a render call first sees them together.
+ * Any setter below (chunky_scene_load_octree and chunky_scene_write_atlas_tile included) may be called again at any time, also on a
+ * scene that render targets have rendered from: launches already queued finish on the old contents, the next launch sees the new ones. */
 /* octreeData after the leaf remap of ClSceneLoader.java:52-63 + octreeDepth (getOctreeData/getOctreeDepth) */
 int chunky_scene_set_octree(chunky_scene* scene, const int32_t* tree, int64_t n_ints, int depth);
 /* Same, from Chunky's raw PackedOctree.treeData + blockMapping: performs the remap
