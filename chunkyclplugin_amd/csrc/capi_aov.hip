@@ -7,8 +7,6 @@ static const int kAovExOffset[7] = {0, 0, 0, 1, 2, 5, 6};  // alpha, depth, posi
 constexpr int kAovExWords = 7;
 static size_t aov_ex_bytes(const chunky_render* r) { return (size_t)r->width * r->height * kAovExWords * 4; }
 
-// On a group's render target member 0 renders the caller's whole share (as chunky_render_preview does): the images are then the
-// one-context images without an exchange, and every AOV entry point below forwards to member 0.
 static int aov_ensure(chunky_render* r) {
     if (r->aov.p) return CHUNKY_OK;
     const size_t bytes = aov_image_bytes(r) * 2 + 256;  // albedo, normal, the claim counter
@@ -32,18 +30,14 @@ static int aov_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n
     if (int rc = aov_ensure(r)) return rc;
     if (ex)
         if (int rc = aov_ex_ensure(r)) return rc;
-    r->aov_last_launches = 0;
+    r->aov_pass.last_launches = 0;
     if (n == 0 || T.n_local <= 0) return CHUNKY_OK;
     SceneView S;
     if (int rc = scene_view(r->scene, &S)) return rc;
     S.bvh_cull = r->opts.bvh_cull;
-    if (r->aov_clock.full())
-        if (int rc = r->aov_clock.collect()) return rc;
-    float* albedo = (float*)r->aov.p;
-    float* normal = (float*)((char*)r->aov.p + aov_image_bytes(r));
     int* counter = (int*)((char*)r->aov.p + 2 * aov_image_bytes(r));
     const size_t plane = (size_t)r->width * r->height;  // words of a one-word image
-    AovExImages images{albedo, normal, nullptr, nullptr, nullptr, nullptr, nullptr};
+    AovExImages images{(float*)r->aov.p, (float*)((char*)r->aov.p + aov_image_bytes(r)), nullptr, nullptr, nullptr, nullptr, nullptr};  // albedo, normal
     if (ex) {
         float* exf = (float*)r->aov_ex.p;
         images.alpha = exf + kAovExOffset[CHUNKY_AOV_ALPHA] * plane;
@@ -52,33 +46,16 @@ static int aov_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n
         images.emittance = exf + kAovExOffset[CHUNKY_AOV_EMITTANCE] * plane;
         images.block = (int*)exf + kAovExOffset[CHUNKY_AOV_BLOCK] * plane;
     }
-    for (int done = 0; done < n;) {  // launches of at most kMaxPassesPerLaunch: each continues the running mean where the last left it
-        PassSeeds ps;
-        ps.n = (n - done) < kMaxPassesPerLaunch ? (n - done) : kMaxPassesPerLaunch;
-        ps.first_spp = first_buffer_spp + done;
-        memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
-        if (int rc = r->aov_clock.open(r->ctx->stream)) return rc;
-        if (ex) HIP_TRY(launch_aov_ex(r->kernel_variant, S, r->cam, r->opts, T, ps, images, counter, r->ctx->stream, &r->aov_choice));
-        else HIP_TRY(launch_aov(r->kernel_variant, S, r->cam, r->opts, T, ps, albedo, normal, counter, r->ctx->stream, &r->aov_choice));
-        if (int rc = r->aov_clock.close(r->ctx->stream)) return rc;
-        r->aov_last_launches += 1;
-        done += ps.n;
-    }
-    return CHUNKY_OK;
+    return first_hit_launches(r, r->aov_pass, seeds, n, first_buffer_spp, [&](const PassSeeds& ps) {  // (each continues the running mean)
+        if (ex) HIP_TRY(launch_aov_ex(r->kernel_variant, S, r->cam, r->opts, T, ps, images, counter, r->ctx->stream, &r->aov_pass.choice));
+        else HIP_TRY(launch_aov(r->kernel_variant, S, r->cam, r->opts, T, ps, images.albedo, images.normal, counter, r->ctx->stream, &r->aov_pass.choice));
+        return (int)CHUNKY_OK;
+    });
 }
 
 static int aov_passes_entry(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp, bool ex) {
     if (n < 0 || (n > 0 && !seeds) || first_buffer_spp < 0) return fail(CHUNKY_E_INVALID, "aov_passes: bad arguments");
-    if (r && !r->parts.empty()) {
-        std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
-        ShardView t;  // the caller's share of the image, all of it on member 0
-        if (!make_shard_view(r->width, r->height, r->outer.rank, r->outer.world, r->outer.tile, &t))
-            return fail(CHUNKY_E_INVALID, "aov_passes: the group's share needs more than 2^31 pixel slots");
-        return aov_passes(r->parts[0], t, seeds, n, first_buffer_spp, ex);
-    }
-    if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
-    std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
-    return aov_passes(r, r->shard, seeds, n, first_buffer_spp, ex);
+    return on_first_member("aov_passes", r, [&](chunky_render* m, const ShardView& t) { return aov_passes(m, t, seeds, n, first_buffer_spp, ex); });
 }
 
 extern "C" int chunky_render_aov_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp) {
@@ -116,19 +93,27 @@ extern "C" int chunky_render_aov_reset(chunky_render* r) {
     return CHUNKY_OK;
 }
 
-extern "C" int chunky_render_aov_kernel_time(chunky_render* r, float* total_ms, int* launches) {
-    if (r && !r->parts.empty()) return chunky_render_aov_kernel_time(r->parts[0], total_ms, launches);
+// ... and of every first-hit pass (capi_matte.hip's too): the record of member 0 on a group
+int first_hit_kernel_time(chunky_render* r, FirstHitPass chunky_render::*pass, float* total_ms, int* launches) {
+    if (r && !r->parts.empty()) r = r->parts[0];
     LOCK_RENDER(r);
-    return r->aov_clock.take(total_ms, launches);
+    return (r->*pass).clock.take(total_ms, launches);
+}
+
+int first_hit_kernel_info(const char* who, chunky_render* r, FirstHitPass chunky_render::*pass, int32_t out4[4]) {
+    if (r && !r->parts.empty()) r = r->parts[0];
+    LOCK_RENDER(r);
+    if (!out4) return fail(CHUNKY_E_INVALID, "%s: NULL output", who);
+    const FirstHitPass& fp = r->*pass;
+    out4[0] = fp.choice.tree, out4[1] = fp.choice.bvh;
+    out4[2] = fp.choice.blocks, out4[3] = fp.last_launches;
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_aov_kernel_time(chunky_render* r, float* total_ms, int* launches) {
+    return first_hit_kernel_time(r, &chunky_render::aov_pass, total_ms, launches);
 }
 
 extern "C" int chunky_render_aov_kernel_info(chunky_render* r, int32_t out4[4]) {
-    if (r && !r->parts.empty()) return chunky_render_aov_kernel_info(r->parts[0], out4);
-    LOCK_RENDER(r);
-    if (!out4) return fail(CHUNKY_E_INVALID, "aov_kernel_info: NULL output");
-    out4[0] = r->aov_choice.tree;
-    out4[1] = r->aov_choice.bvh;
-    out4[2] = r->aov_choice.blocks;
-    out4[3] = r->aov_last_launches;
-    return CHUNKY_OK;
+    return first_hit_kernel_info("aov_kernel_info", r, &chunky_render::aov_pass, out4);
 }

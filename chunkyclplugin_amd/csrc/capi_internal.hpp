@@ -136,6 +136,13 @@ struct LaunchClock {
     int take(float* ms_out, int* count_out);  // collect, report the totals since the last take, zero them
 };
 
+// What the launches of one first-hit pass (first_hit_pass.hpp: the AOV's, the mattes') leave on a render target
+struct FirstHitPass {
+    LaunchClock clock;           // their device time (chunky_render_*_kernel_time)
+    AovChoice choice{0, 0, 0};   // what the most recent one ran
+    int last_launches = 0;       // launches of the most recent *_passes call
+};
+
 struct chunky_render {
     chunky_ctx* ctx = nullptr;
     chunky_scene* scene = nullptr;
@@ -174,18 +181,14 @@ struct chunky_render {
     // the render kernels' (chunky_render_kernel_time / _kernel_info do not see AOV launches)
     DevBuf aov;
     // chunky_render_aov_passes_ex: alpha, depth (a word per pixel each), position (3), emittance, block id (1 each), allocated (and
-    // zeroed) by the first _ex call; its launches share the AOV's counter, clock and choice
+    // zeroed) by the first _ex call; its launches share the AOV's counter and record
     DevBuf aov_ex;
-    LaunchClock aov_clock{&free_events};
-    AovChoice aov_choice{0, 0, 0};
-    int aov_last_launches = 0;  // launches of the most recent chunky_render_aov_passes
+    FirstHitPass aov_pass{LaunchClock(&free_events)};
     // chunky_render_matte_passes: 13 planes of width * height int32 (six of ids, six of counts, `other`), then the kernel's claim
     // counter; allocated (and zeroed) by the first matte call.  matte_work holds a read-out on its way to the host (ranks: 12 planes;
-    // extract: one) and matte_set the sorted ids of an extract.  Clock, choice and counter are its own: the AOV calls do not see them
+    // extract: one) and matte_set the sorted ids of an extract.  Record and counter are its own: the AOV calls do not see them
     DevBuf matte, matte_work, matte_set;
-    LaunchClock matte_clock{&free_events};
-    AovChoice matte_choice{0, 0, 0};
-    int matte_last_launches = 0;  // launches of the most recent chunky_render_matte_passes
+    FirstHitPass matte_pass{LaunchClock(&free_events)};
     int32_t matte_passes = 0;     // passes folded since the last reset
     // chunky_render_denoise: the filter's workspace (kept between calls) and its timing, apart from the render and AOV launches'
     DevBuf dn_work, dn_out;
@@ -252,6 +255,37 @@ static int each_part(chunky_render* r, F call) {
 #define FAN_RENDER(r, expr) \
     if ((r) && !(r)->parts.empty()) return each_part((r), [&](chunky_render* m_) { return expr; })
 
+// n passes of a first-hit pass in launches of at most kMaxPassesPerLaunch, each continuing the images: launch(its seeds) returns a CHUNKY_ code
+template <class Launch>
+static int first_hit_launches(chunky_render* r, FirstHitPass& fp, const int32_t* seeds, int n, int first_buffer_spp, Launch launch) {
+    if (fp.clock.full())
+        if (int rc = fp.clock.collect()) return rc;
+    for (int done = 0; done < n; done += kMaxPassesPerLaunch) {
+        PassSeeds ps;
+        ps.n = std::min(n - done, kMaxPassesPerLaunch);
+        ps.first_spp = first_buffer_spp + done;
+        memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
+        if (int rc = fp.clock.open(r->ctx->stream)) return rc;
+        if (int rc = launch(ps)) return rc;
+        if (int rc = fp.clock.close(r->ctx->stream)) return rc;
+        fp.last_launches += 1;
+    }
+    return CHUNKY_OK;
+}
+
+// A first-hit pass on a group's render target: member 0 renders the caller's whole share (as chunky_render_preview does), so the
+// images are the one-context images without an exchange (the pass's other entry points forward to member 0).  Runs under the lock.
+template <class Passes>
+static int on_first_member(const char* who, chunky_render* r, Passes passes) {
+    if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
+    std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
+    if (r->parts.empty()) return passes(r, r->shard);
+    ShardView t;  // the caller's share of the image, all of it on member 0
+    if (!make_shard_view(r->width, r->height, r->outer.rank, r->outer.world, r->outer.tile, &t))
+        return fail(CHUNKY_E_INVALID, "%s: the group's share needs more than 2^31 pixel slots", who);
+    return passes(r->parts[0], t);
+}
+
 // ------------------------------------------------------------------------------------ helpers that cross files
 #pragma GCC visibility push(hidden)  // internal to the library: none of these is part of its surface
 void group_close_rccl(chunky_ctx* g, bool abort);                                       // capi_group.hip
@@ -261,5 +295,7 @@ int scene_view(chunky_scene* s, SceneView* v, bool want_emitters = false);
 int launch_pass_cap(const ShardView& T, int width, int height, size_t budget, int most);  // capi_render.hip
 int check_extended_opts(const char* who, const chunky_render* r, const SceneView& S);
 int read_floats(const char* who, chunky_render* r, const void* src, void* out, int64_t n, int64_t need);
+int first_hit_kernel_time(chunky_render* r, FirstHitPass chunky_render::*pass, float* total_ms, int* launches);  // capi_aov.hip
+int first_hit_kernel_info(const char* who, chunky_render* r, FirstHitPass chunky_render::*pass, int32_t out4[4]);
 int device_gamma_table(chunky_ctx* ctx, const float** out);                             // capi_filter.hip
 #pragma GCC visibility pop

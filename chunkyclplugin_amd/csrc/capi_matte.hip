@@ -6,8 +6,6 @@ constexpr int kMattePlanes = 2 * CHUNKY_MATTE_SLOTS + 1;  // six of ids, six of 
 static size_t matte_plane_bytes(const chunky_render* r) { return (size_t)r->width * r->height * 4; }
 static size_t matte_bytes(const chunky_render* r) { return matte_plane_bytes(r) * kMattePlanes; }
 
-// On a group's render target member 0 renders the caller's whole share (as for the AOV): the planes are then the one-context planes
-// without an exchange, and every entry point below forwards to member 0.
 static int matte_ensure(chunky_render* r) {
     if (r->matte.p) return CHUNKY_OK;
     const size_t bytes = matte_bytes(r) + 256;  // the planes, the claim counter
@@ -23,43 +21,24 @@ static int matte_passes(chunky_render* r, ShardView T, const int32_t* seeds, int
     if (!r->have_camera) return fail(CHUNKY_E_STATE, "matte_passes before set_camera");
     if (int rc = matte_ensure(r)) return rc;
     if (n > INT32_MAX - r->matte_passes) return fail(CHUNKY_E_INVALID, "matte_passes: %d more passes after %d exceed 2^31 - 1", n, r->matte_passes);
-    r->matte_last_launches = 0;
+    r->matte_pass.last_launches = 0;
     if (n == 0) return CHUNKY_OK;
     r->matte_passes += n;  // (a rank that owns nothing keeps its planes empty, and they read as such after any number of passes)
     if (T.n_local <= 0) return CHUNKY_OK;
     SceneView S;
     if (int rc = scene_view(r->scene, &S)) return rc;
     S.bvh_cull = r->opts.bvh_cull;
-    if (r->matte_clock.full())
-        if (int rc = r->matte_clock.collect()) return rc;
     int* planes = (int*)r->matte.p;
     int* counter = (int*)((char*)r->matte.p + matte_bytes(r));
-    for (int done = 0; done < n;) {  // launches of at most kMaxPassesPerLaunch: each continues the counts where the last left them
-        PassSeeds ps;
-        ps.n = (n - done) < kMaxPassesPerLaunch ? (n - done) : kMaxPassesPerLaunch;
-        ps.first_spp = 0;
-        memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
-        if (int rc = r->matte_clock.open(r->ctx->stream)) return rc;
-        HIP_TRY(launch_matte(r->kernel_variant, S, r->cam, r->opts, T, ps, planes, counter, r->ctx->stream, &r->matte_choice));
-        if (int rc = r->matte_clock.close(r->ctx->stream)) return rc;
-        r->matte_last_launches += 1;
-        done += ps.n;
-    }
-    return CHUNKY_OK;
+    return first_hit_launches(r, r->matte_pass, seeds, n, 0, [&](const PassSeeds& ps) {  // (each continues the counts)
+        HIP_TRY(launch_matte(r->kernel_variant, S, r->cam, r->opts, T, ps, planes, counter, r->ctx->stream, &r->matte_pass.choice));
+        return (int)CHUNKY_OK;
+    });
 }
 
 extern "C" int chunky_render_matte_passes(chunky_render* r, const int32_t* seeds, int n) {
     if (n < 0 || (n > 0 && !seeds)) return fail(CHUNKY_E_INVALID, "matte_passes: bad arguments");
-    if (r && !r->parts.empty()) {
-        std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
-        ShardView t;  // the caller's share of the image, all of it on member 0
-        if (!make_shard_view(r->width, r->height, r->outer.rank, r->outer.world, r->outer.tile, &t))
-            return fail(CHUNKY_E_INVALID, "matte_passes: the group's share needs more than 2^31 pixel slots");
-        return matte_passes(r->parts[0], t, seeds, n);
-    }
-    if (!r || !r->ctx) return fail(CHUNKY_E_INVALID, "NULL render");
-    std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
-    return matte_passes(r, r->shard, seeds, n);
+    return on_first_member("matte_passes", r, [&](chunky_render* m, const ShardView& t) { return matte_passes(m, t, seeds, n); });
 }
 
 extern "C" int chunky_render_matte_reset(chunky_render* r) {
@@ -152,18 +131,9 @@ extern "C" int chunky_render_matte_extract(chunky_render* r, const int32_t* set,
 }
 
 extern "C" int chunky_render_matte_kernel_time(chunky_render* r, float* total_ms, int* launches) {
-    if (r && !r->parts.empty()) return chunky_render_matte_kernel_time(r->parts[0], total_ms, launches);
-    LOCK_RENDER(r);
-    return r->matte_clock.take(total_ms, launches);
+    return first_hit_kernel_time(r, &chunky_render::matte_pass, total_ms, launches);
 }
 
 extern "C" int chunky_render_matte_kernel_info(chunky_render* r, int32_t out4[4]) {
-    if (r && !r->parts.empty()) return chunky_render_matte_kernel_info(r->parts[0], out4);
-    LOCK_RENDER(r);
-    if (!out4) return fail(CHUNKY_E_INVALID, "matte_kernel_info: NULL output");
-    out4[0] = r->matte_choice.tree;
-    out4[1] = r->matte_choice.bvh;
-    out4[2] = r->matte_choice.blocks;
-    out4[3] = r->matte_last_launches;
-    return CHUNKY_OK;
+    return first_hit_kernel_info("matte_kernel_info", r, &chunky_render::matte_pass, out4);
 }

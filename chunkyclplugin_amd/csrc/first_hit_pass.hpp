@@ -1,0 +1,174 @@
+// first_hit_pass.hpp — the one kernel behind the passes that fold the FIRST hit of every pass's camera ray into per-pixel images: the
+// AOV and AOV-ex passes (aov.hip) and the ID mattes (matte.hip).  Everything here is shared; what a pass has of its own is a Fold.
+//
+// The sample of pass k at pixel gid is the first trace of reference pass k: RNG state seed + gid, Random_nextState, the camera ray
+// (K/rayTracer.cl:55-91), one closestIntersect (K/kernel.h:14-24).
+//
+// Kernel: a persistent grid sized from the CU count; each wave claims kFirstHitUnit pixel slots at a time — a quarter of one of
+// render_pool's 16 x 16 tiles (pool_slot_gid: the same tiles, sub-blocks and shard forms), so the rays of a wave are coherent and
+// tiles that are mostly sky do not leave CUs idle.  A lane owns one pixel for every pass of the launch and folds in registers: each
+// word of the pass's images is read once and written once per launch.
+//
+// A Fold is a struct with
+//   struct Out             the device pointers of its images (the tail of the launch arguments)
+//   (members)              the pixel's running values, in registers
+//   waves(bvh)             waves per SIMD the kernel is held to (constexpr)
+//   kParts                 whether absorb is told WHICH part of closestIntersect won (an int, first_hit_part) or only whether one did
+//   load(a, gid, n_pixels) read the pixel; `a` is the argument pointer of the claim
+//   absorb(part, h, r, k, first_spp)  fold the sample of pass k: the trace's answer and record, the camera ray, and the samples
+//                          folded before the launch (first_buffer_spp)
+//   store(gid, n_pixels)   write the pixel
+#pragma once
+#include "path_state.hpp"
+
+namespace chunky {
+
+template <class Out>
+struct FirstHitArgs {
+    SceneView S;
+    CameraView C;
+    ShardView T;
+    PassSeeds P;
+    int draw_depth;
+    int n_units;   // claims of kFirstHitUnit pixel slots: the rank's tiles x 4
+    int* counter;  // next unclaimed unit (zeroed before every launch)
+    Out out;
+};
+constexpr int kFirstHitUnit = 64;  // pixel slots per claim: one wave's worth, a quarter of a 16 x 16 tile (16 x 4 pixels)
+
+// The launch arguments are read through the kernel-argument segment pointer, and that pointer is made opaque again before each stage
+// of a pass (the camera ray, the trace, a fold's sky term and its store): the scalars each stage needs are loaded where they are used
+// instead of being hoisted out of the loops and kept alive in spilled SGPRs (path_state.hpp fresh_args does the same for render_pool).
+template <class Out>
+DEV auto first_hit_args() {
+    return opaque_args<FirstHitArgs<Out>>();
+}
+
+// closestIntersect (path_state.hpp closest_hit) without the hit point, with the entity-BVH walk present only where the scene has
+// entities.  PARTS: which part won — 0 nothing, 1 the octree's block, 2 a world-BVH triangle, 3 an actor-BVH triangle (bvh_hit returns
+// true only where a triangle passed triangle_hit's `tt < best`, so a later part that answers true has won).  Otherwise a bool, in the
+// form the AOV kernels always had: asked for the part and tested against 0, their walks compile to other code (EXPERIMENTS.md R1).
+template <int TREE, bool BVH, bool PARTS>
+DEV auto first_hit_part(const SceneView& S, f3 o, f3 d, int draw_depth, Hit& h, LdsStack& stack) {
+    if constexpr (PARTS) {
+        int part = octree_hit<TREE>(S, o, d, draw_depth, h) ? 1 : 0;
+        if (BVH) {
+            if (!S.world_bvh_empty && bvh_hit(S, S.world_bvh, o, d, h, stack)) part = 2;
+            if (!S.actor_bvh_empty && bvh_hit(S, S.actor_bvh, o, d, h, stack)) part = 3;
+        }
+        return part;
+    } else {
+        bool hit = octree_hit<TREE>(S, o, d, draw_depth, h);
+        if (BVH) {
+            if (!S.world_bvh_empty) hit |= bvh_hit(S, S.world_bvh, o, d, h, stack);
+            if (!S.actor_bvh_empty) hit |= bvh_hit(S, S.actor_bvh, o, d, h, stack);
+        }
+        return hit;
+    }
+}
+
+// PROJ: a projected camera (projector types 1-5, 7, 8, rt_device.hpp projected_ray), instantiated apart so that the other cameras
+// keep their code.
+template <class Fold, int TREE, bool BVH, bool PROJ>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fold::waves(BVH)))) first_hit_kernel(FirstHitArgs<typename Fold::Out>) {
+    static_assert(sizeof(FirstHitArgs<typename Fold::Out>) <= 4096, "launch arguments must fit the 4 KB kernel-argument segment");
+    extern __shared__ int lds[];
+    LdsStack stack{lds + threadIdx.x, (int)blockDim.x};
+    const int lane = (int)(threadIdx.x & 63);
+    for (;;) {
+        auto a = first_hit_args<typename Fold::Out>();
+        const int width = a->C.width, height = a->C.height, n_pixels = width * height;
+        // every lane of the wave is here (the exit below is wave-uniform): lane 0 claims, the others take its value
+        int unit = 0;
+        if (lane == 0) unit = atomicAdd(a->counter, 1);
+        unit = __builtin_amdgcn_readfirstlane(unit);
+        if (unit >= a->n_units) break;
+        const int gid = pool_slot_gid(arg_copy(&a->T), width, height, unit * kFirstHitUnit + lane);
+        if (gid < n_pixels) {  // (not a padding slot)
+            Fold f;
+            f.load(a, gid, n_pixels);
+            const int px = gid % width, py = gid / width;
+            const int n_passes = a->P.n, first_spp = a->P.first_spp;
+            for (int k = 0; k < n_passes; k++) {
+                auto b = first_hit_args<typename Fold::Out>();
+                const unsigned seed = (unsigned)b->P.seed[k];
+                unsigned rng = seed + (unsigned)gid;  // K/rayTracer.cl:54-56
+                rt_pcg_next(&rng);
+                const RayOD r = primary_ray<PROJ>(arg_copy(&b->C), seed, gid, rng, false, px, py);
+                Hit h;
+                h.distance = rt_inf();
+                h.material = 0;
+                h.normal = mk3(0, 0, 0);
+                h.color = f4{0, 0, 0, 0};
+                h.emittance = 0;
+                h.spec = 0;
+                auto t = first_hit_args<typename Fold::Out>();
+                const auto part = first_hit_part<TREE, BVH, Fold::kParts>(arg_copy(&t->S), r.o, r.d, t->draw_depth, h, stack);
+                f.absorb(part, h, r, k, first_spp);
+            }
+            f.store(gid, n_pixels);
+        }
+    }
+}
+
+// The lookup form: the one launch_render's render_pool picks for the scene (tree_form; with entity BVHs the dense tops of one and
+// two levels, else the generic walk), so that a first-hit pass and a render pass of a view read the octree the same way.
+inline int first_hit_tree(int variant, const SceneView& S, bool bvh) {
+    const int tree = tree_form(variant, S);
+    if (tree == 0) return 0;
+    if (bvh) return (tree == 17 || tree == 18) ? tree : -1;
+    return (tree >= 16 && tree <= 19) ? tree : -1;
+}
+
+// the instantiation for the tree form and the camera
+template <class Fold, bool PROJ>
+void (*first_hit_instance(int tree, bool bvh))(FirstHitArgs<typename Fold::Out>) {
+    if (bvh) {
+        switch (tree) {
+            case 0: return first_hit_kernel<Fold, 0, true, PROJ>;
+            case 17: return first_hit_kernel<Fold, 17, true, PROJ>;
+            case 18: return first_hit_kernel<Fold, 18, true, PROJ>;
+            default: return first_hit_kernel<Fold, -1, true, PROJ>;
+        }
+    } else {
+        switch (tree) {
+            case 0: return first_hit_kernel<Fold, 0, false, PROJ>;
+            case 16: return first_hit_kernel<Fold, 16, false, PROJ>;
+            case 17: return first_hit_kernel<Fold, 17, false, PROJ>;
+            case 18: return first_hit_kernel<Fold, 18, false, PROJ>;
+            case 19: return first_hit_kernel<Fold, 19, false, PROJ>;
+            default: return first_hit_kernel<Fold, -1, false, PROJ>;
+        }
+    }
+}
+
+template <class Fold>
+hipError_t launch_first_hit(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
+                            const typename Fold::Out& out, int* counter, hipStream_t stream, AovChoice* chosen) {
+    if (P.n <= 0 || T.n_local <= 0) return hipSuccess;
+    if (P.n > kMaxPassesPerLaunch) return hipErrorInvalidValue;
+    const bool bvh = !S.world_bvh_empty || !S.actor_bvh_empty;
+    const int tree = first_hit_tree(variant, S, bvh);
+    auto k = C.projector_type > 0 ? first_hit_instance<Fold, true>(tree, bvh) : first_hit_instance<Fold, false>(tree, bvh);
+    const int block = 256;
+    const size_t lds = stack_lds_bytes(S, block);
+    int n_cu = 0, occ = 0;
+    hipError_t e = current_device_cus(&n_cu);
+    if (e != hipSuccess) return e;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, block, lds);
+    if (e != hipSuccess) return e;
+    const long long n_units = pool_tiles(T, C.width, C.height) * (kSampleTile / kFirstHitUnit);
+    const long long want = (n_units + block / 64 - 1) / (block / 64);  // no more workgroups than one claim per wave
+    long long grid = (long long)n_cu * (occ > 0 ? occ : 1);
+    if (grid > want) grid = want;
+    if (chosen) *chosen = AovChoice{tree, bvh ? 1 : 0, (int)grid};
+    e = hipMemsetAsync(counter, 0, sizeof(int), stream);
+    if (e != hipSuccess) return e;
+    FirstHitArgs<typename Fold::Out> A{S, C, T, P, O.draw_depth, (int)n_units, counter, out};
+    A.T.list = nullptr;  // (pool_slot_gid maps every shard form itself)
+    A.T.n_list = 0;
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(block), lds, stream, A);
+    return hipGetLastError();
+}
+
+}  // namespace chunky

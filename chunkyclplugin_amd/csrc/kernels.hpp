@@ -117,7 +117,7 @@ struct AovChoice {
 // pixel slots of shard T; `counter` is one int of device memory the launch claims its work from.
 hipError_t launch_aov(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
                       float* albedo, float* normal, int* counter, hipStream_t stream, AovChoice* chosen);
-// The seven images of chunky_render_aov_passes_ex (aov.hip aov_ex_kernel): albedo, normal and position 3 * width * height floats, the
+// The seven images of chunky_render_aov_passes_ex (aov.hip AovExFold): albedo, normal and position 3 * width * height floats, the
 // others width * height words
 struct AovExImages {
     float *albedo, *normal, *alpha, *depth, *position, *emittance;

@@ -546,11 +546,14 @@ DEV T arg_copy(const T __attribute__((address_space(4))) * p) {
 #endif
 }
 
-DEV WaveArgPtr fresh_args() {
-    WaveArgPtr a = (WaveArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+// the kernel-argument segment as an A, through a pointer the optimiser cannot see through (no instruction)
+template <typename A>
+DEV const A __attribute__((address_space(4))) * opaque_args() {
+    const A __attribute__((address_space(4)))* a = (const A __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(a));
     return a;
 }
+DEV WaveArgPtr fresh_args() { return opaque_args<WaveArgs>(); }
 
 // A scalar argument word that has to be in its register HERE (no instruction): the optimiser cannot sink the word's load to the basic
 // block of its first use, so the loads of words pinned side by side are issued together and waited for once.

@@ -820,7 +820,7 @@ DEV RayOD projected_ray(const CameraView& C, unsigned seed, int gid, int px, int
                                      C.aperture, C.lens_focus, px, py, seed, gid);
     return RayOD{mk3(r.ox, r.oy, r.oz), mk3(r.dx, r.dy, r.dz)};
 }
-// PROJ: a compile-time choice of the kernels whose registers are budgeted (render_pool, aov_kernel): their pinhole / pre-generated
+// PROJ: a compile-time choice of the kernels whose registers are budgeted (render_pool, first_hit_kernel): their pinhole / pre-generated
 // instantiations compile exactly the code above
 template <bool PROJ>
 DEV RayOD primary_ray(const CameraView& C, unsigned seed, int gid, unsigned& rng, bool unit_dir, int px, int py) {

@@ -89,6 +89,22 @@ def embedded_any() -> scenes.PackedScene:
     return scenes.embed_deeper(make("outdoor"), 15, siblings={(0, 2): scenes.ANY_TYPE})
 
 
+RAGGED_VIEW = (33, 17)   # 3 x 2 tiles of 16 x 16 with the edge tiles padded on both axes: 24 claims of 64 slots, fewer workgroups than a full grid
+
+
+def form_cases(ragged=False):
+    """(key, builder, (tree form, entity-BVH walk)) of the scenes that walk a first-hit kernel (AOV, AOV-ex, ID mattes) through the
+    lookup forms no 64 x 48 golden scene runs: 17 / 18 / 19 / 0 without entities, and 18 with the BVH walk.  `ragged`: the form-19
+    case at RAGGED_VIEW instead, the smallest view that reaches the kernel's padding test, its wave-uniform exit and its grid cap."""
+    yield "deep-" + DEEP_NAMES[0], (lambda: make(DEEP_NAMES[0], DEEP_CHUNKS)), (17, False)
+    for depth, form in ((11, 18), (15, 19), (16, 0)):
+        if ragged and form == 19:
+            yield f"outdoor-embedded-{depth}-33x17", (lambda d=depth: embedded("outdoor", d).with_view(*RAGGED_VIEW)), (form, False)
+        else:
+            yield f"outdoor-embedded-{depth}", (lambda d=depth: embedded("outdoor", d)), (form, False)
+    yield "entities-embedded-11", (lambda: embedded("entities", 11)), (18, True)
+
+
 def embed_cases():
     """(key in deep.npz, scene) of every image the file holds."""
     for name in EMBED_SCENES:

@@ -1,6 +1,6 @@
 """The denoiser's auxiliary images on the device (chunky_render_aov_passes, csrc/aov.hip) against their specification restated on
 the oracles (aov_spec.expected_aov: record 0 of the reference's own sample, folded with its running mean), bit for bit: the golden
-scenes whole, the timed views on whole rows with the instantiation the render kernel runs there, the launch cut, the line-up with
+scenes whole, every tree form, the timed views on whole rows with the instantiation the render kernel runs there, the launch cut, the line-up with
 render passes, shards, the BVH cull option, isolation from the render target's own buffers, the ABI's errors and groups."""
 import ctypes as C
 
@@ -67,6 +67,26 @@ def test_golden_scene_whole_images_equal_the_reference(gpu_instance, ref, name):
 @pytest.mark.parametrize("name", gs.NAMES)
 def test_golden_scene_whole_images_equal_the_port(gpu_instance, port, name):
     whole_image_case(gpu_instance, port, name)
+
+
+FORM_CASES = list(gs.form_cases(ragged=True))
+
+
+@pytest.mark.parametrize("key,build,kernel", FORM_CASES, ids=[c[0] for c in FORM_CASES])
+def test_tree_forms(gpu_instance, port, key, build, kernel):
+    """The lookup forms 17 / 18 / 19 / 0 and the entity form 18 with the walk, whole images; the form-19 case at 33 x 17."""
+    sc = build()
+    seeds = native.java_random_ints(gs.N_PASSES)
+    loader, r = make(gpu_instance, sc)
+    r.render_aov(seeds)
+    info = r.aov_info()
+    assert (info["tree"], info["bvh"]) == kernel, info
+    if (sc.width, sc.height) == gs.RAGGED_VIEW:
+        assert info["blocks"] == 6   # 24 claims, one per wave of four-wave workgroups: the grid cap, not the device's size
+    gids = np.arange(sc.width * sc.height)
+    assert_same(images(r), expected_aov(port, binding.SceneHandle(sc), seeds, gids), gids, key)
+    r.close()
+    loader.close()
 
 
 def timed_scene(name):

@@ -1,8 +1,8 @@
-"""chunky_render_aov_passes_ex / _read_ex (csrc/aov.hip aov_ex_kernel) and chunky_filter_frame_alpha on the device, bit for bit
+"""chunky_render_aov_passes_ex / _read_ex (csrc/aov.hip AovExFold) and chunky_filter_frame_alpha on the device, bit for bit
 against their specification restated on the C restatement of the reference (aov_ex_spec.expected_aov_ex: record 0 of the sample,
 seven images folded from it; tests/test_aov_ex_cpu.py shows the restatement means the same on the reference build): the golden
-scenes whole, a call split in two, the launch cut, a projected camera with a lens, shards, a group, the BVH cull option, the timed
-instantiations on whole rows, the line-up with chunky_render_aov_passes, the untouched beauty buffer, the ABI's errors, and the
+scenes whole, every tree form, a call split in two, the launch cut, a projected camera with a lens, shards, a group, the BVH cull
+option, the timed instantiations on whole rows, the line-up with chunky_render_aov_passes, the untouched beauty buffer, the ABI's errors, and the
 tone map's alpha byte."""
 import dataclasses
 
@@ -91,6 +91,24 @@ def test_golden_scene_whole_images(gpu_instance, golden, name):
     hit = got["alpha"][:, 0] > 0
     assert hit.any() and (got["depth"][hit] > 0).all()
     close(r, loader, plain, lp)
+
+
+FORM_CASES = list(gs.form_cases(ragged=True))
+
+
+@pytest.mark.parametrize("key,build,kernel", FORM_CASES, ids=[c[0] for c in FORM_CASES])
+def test_tree_forms(gpu_instance, port, key, build, kernel):
+    """The lookup forms 17 / 18 / 19 / 0 and the entity form 18 with the walk, whole images; the form-19 case at 33 x 17."""
+    sc = build()
+    loader, r = make(gpu_instance, sc)
+    r.render_aov_ex(SEEDS)
+    info = r.aov_info()
+    assert (info["tree"], info["bvh"]) == kernel, info
+    if (sc.width, sc.height) == gs.RAGGED_VIEW:
+        assert info["blocks"] == 6   # 24 claims, one per wave of four-wave workgroups: the grid cap, not the device's size
+    gids = np.arange(sc.width * sc.height)
+    assert_same(images(r), expected_aov_ex(port, binding.SceneHandle(sc), SEEDS, gids), gids, key)
+    close(r, loader)
 
 
 def test_two_calls_equal_one(gpu_instance, golden):

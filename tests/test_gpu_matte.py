@@ -93,14 +93,7 @@ def test_golden_scene_whole_state(gpu_instance, port, name):
 
 
 # ---- 2. the tree forms ---------------------------------------------------------------------------------------------------------------
-def form_cases():
-    yield "deep-" + gs.DEEP_NAMES[0], (lambda: gs.make(gs.DEEP_NAMES[0], gs.DEEP_CHUNKS)), (17, False)
-    for depth, form in ((11, 18), (15, 19), (16, 0)):
-        yield f"outdoor-embedded-{depth}", (lambda d=depth: gs.embedded("outdoor", d)), (form, False)
-    yield "entities-embedded-11", (lambda: gs.embedded("entities", 11)), (18, True)
-
-
-@pytest.mark.parametrize("key,build,kernel", list(form_cases()), ids=[c[0] for c in form_cases()])
+@pytest.mark.parametrize("key,build,kernel", list(gs.form_cases()), ids=[c[0] for c in gs.form_cases()])
 def test_tree_forms(gpu_instance, port, key, build, kernel):
     sc = build()
     want = expected(port, key, sc, SEEDS)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/kernel_resources.py [out.json] — registers, spills and occupancy of every render_pool / fold_kernel instantiation, of the
-denoise kernels, of the adaptive-sampling kernels, of the AOV kernels (aov_kernel, aov_ex_kernel) and of the ID-matte kernels as hipcc reports them for gfx950
+denoise kernels, of the adaptive-sampling kernels, of the first-hit pass kernels (first_hit_kernel with the AOV, AOV-ex and ID-matte folds) and of the matte read-outs as hipcc reports them for gfx950
 (-Rpass-analysis=kernel-resource-usage on csrc/render_pool.hip, csrc/render_pool_bvh.hip (the entity-BVH instantiations),
 csrc/denoise.hip, csrc/adaptive.hip, csrc/aov.hip and csrc/matte.hip with the library's flags).  CPU only."""
 import json
