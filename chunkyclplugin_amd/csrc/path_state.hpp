@@ -624,14 +624,16 @@ DEV void part_end(PartTimers* pt, int which) {  // charges the time since the la
     }
 }
 
-// SHADE, part 1: everything from the end of a trace to the start of the next one on the same path.
+// SHADE, part 1: everything from the end of a trace to the start of the next one on the same path, as three pieces: (a) the sky
+// request, (b) the continuation (path_continue.inc), (c) sky_finish.
 // Returns ST_SETUP (a ray is ready to be traced) or ST_NEXT (the path is finished).
 template <int TREE, bool BVH, bool PROF = false>
 DEV int shade_phase(const SceneView& S, const RenderOpts& O, LaneState& L, LdsStack& stack, PartTimers* pt = nullptr) {
     part_begin<PROF>(pt);
     const bool hit = BVH ? L.trace_hit : L.oct_hit;  // closestIntersect (K/kernel.h:14-24) is complete
-    // Each block below appears once, so a shade round issues it once however the lanes split.
+    // Each block appears once, so a shade round issues it once however the lanes split.
     const bool main_trace = !L.shadow;
+    // (a) the sky request
     SkyTexels sky_q;
     f3 sky_d = mk3(0, 0, 0);
     float sky_e = 0;
@@ -639,7 +641,7 @@ DEV int shade_phase(const SceneView& S, const RenderOpts& O, LaneState& L, LdsSt
         // a shadow ray's record.emittance is the |dot(sun dir, normal)| stored at its start (K/sky.h:90) and nothing writes it during
         // the trace — nor L.d or the normal: it is evaluated here, from the same operands, instead of being carried through the trace
         // (render_pool's six-word parked record has no place for it while 1/d and the distance marched are alive)
-        // Only the four texel reads are issued here (sky_fetch); the disc test and the blend follow the sampling block below, which reads
+        // Only the four texel reads are issued here (sky_fetch); the disc test and the blend follow the continuation below, which reads
         // nothing the sky produces and runs while the texels are on their way.  A lane that ends in the sky keeps its throughput and its
         // radiance through that block (only a main ray's hit changes them), but a shadow ray that missed bounces there and overwrites
         // L.d: the direction looked up, and e with it, are taken first.
@@ -648,66 +650,11 @@ DEV int shade_phase(const SceneView& S, const RenderOpts& O, LaneState& L, LdsSt
         sky_q = sky_fetch(S, L.d);
     }
     part_end<PROF>(pt, PT_SKY);
-    // one exit: a main ray that reached the sky is finished; every other lane goes on below
+    // (b) one exit: a main ray that reached the sky is finished; every other lane goes on
     bool finished = !hit && main_trace;
-    bool to_sun = false;  // start a shadow ray towards the sun; otherwise bounce
-    if (finished) {
-    } else if (main_trace) {
-        // the hit point (K/kernel.h:21-23) becomes the origin of the shadow ray and stays there until the bounce
-        L.o = L.o + L.d * (L.h.distance - kOffset);
-        // applyRayColor (K/kernel.h:33-44)
-        f3 c = mk3(L.h.color.x, L.h.color.y, L.h.color.z);
-        L.throughput = L.throughput * c;
-        L.radiance = L.radiance + (c * (L.h.emittance * O.emitter_scale)) * L.throughput;
-        if (S.sun_flags & 1) to_sun = true;
-    } else {
-        L.shadow = false;
-    }
-    // Sun_sampleDirection (K/sky.h:68-93) for the lanes that start a shadow ray, nextPath (K/kernel.h:46-98)
-    // for the lanes that bounce.  A lane does one or the other, and both have the same skeleton — two draws,
-    // sin/cos of 2*pi*x2, a square root, a vector, its reciprocal length — so the expensive steps are issued
-    // once for both kinds of lane and only the cheap vector algebra in between is specific.
-    if (!finished) {
-        const float x1 = rt_pcg_float(&L.rng), x2 = rt_pcg_float(&L.rng);
-        float sn, cs;
-        rt_sincos(2 * RT_PI_F * x2, &sn, &cs);
-        const float cos_a = 1 - x1 + x1 * S.sun_radius_cos;          // sun: cosine of the angle off the sun axis
-        const float root = rt_sqrt(to_sun ? 1 - cos_a * cos_a : x1);  // sun: sin_a; bounce: r
-        const f3 n = L.h.normal;
-        f3 a;        // sun: the unnormalised direction; bounce: the unnormalised tangent u
-        float len2;  // its squared length, each written as the reference writes it
-        if (to_sun) {
-            const f3 u = S.su * (cs * root), v = S.sv * (sn * root), w = S.sw * cos_a;
-            a = (u * v) + w;  // component-wise product, as the reference has it
-            len2 = dot(a, a);
-        } else {
-            float xx, xy, xz = 0;
-            if ((double)rt_fabs(n.x) > 0.1) {
-                xx = 0;
-                xy = 1;
-            } else {
-                xx = 1;
-                xy = 0;
-            }
-            a = mk3(xy * n.z - xz * n.y, xz * n.x - xx * n.z, xx * n.y - xy * n.x);
-            len2 = a.x * a.x + a.y * a.y + a.z * a.z;
-        }
-        const float rl = rcp_exact(rt_sqrt(len2));
-        a = a * rl;
-        if (to_sun) {
-            L.d = a;
-            L.shadow = true;  // (record.emittance = |dot(L.d, n)|, K/sky.h:90: evaluated where it is read, above)
-        } else {
-            const float tx = root * cs, ty = root * sn, tz = rt_sqrt(1 - x1);
-            const float vx = a.y * n.z - a.z * n.y, vy = a.z * n.x - a.x * n.z, vz = a.x * n.y - a.y * n.x;
-            L.d = f3{a.x * tx + vx * ty + n.x * tz, a.y * tx + vy * ty + n.y * tz, a.z * tx + vz * ty + n.z * tz};
-            L.o = L.o + L.d * kOffset;
-            L.depth += 1;
-            L.h.distance = rt_inf();
-            finished = !(L.depth < O.max_depth);
-        }
-    }
+#include "path_continue.inc"
     part_end<PROF>(pt, PT_SAMPLING);
+    // (c)
     if (!hit) L.radiance = L.radiance + sky_finish(S, sky_q, sky_d, L.throughput, sky_e);
     part_end<PROF>(pt, PT_SKY);
     return finished ? ST_NEXT : ST_SETUP;

@@ -11,6 +11,7 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
     // candidates sorted into full cubes (ST_BLOCK) and model blocks (ST_MODEL); not instantiated with entity BVHs or the extended
     // integrator (their pools are small: measured -4 % / -2 %)
     constexpr bool SPLIT = SORT;
+    constexpr bool CONTINUES = CHUNKY_BLOCK_CONTINUES && !BVH && !EXT;  // the block test goes on where it hits (render_pool.hip block_continues)
     static_assert(!SORT || (TREE != 0 && !BVH && !EXT), "sorted block tests: the plain kernel on the re-laid-out tree only");
     extern __shared__ int lds[];
     const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
@@ -200,6 +201,7 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
             const SceneView S = arg_copy(&fresh_args()->S);
             if (st == ST_BLOCK) {
                 st = block_phase<TREE, END, false, SPLIT ? kBlockCubes : kBlockAny, WORDS == 6>(S, L);
+                if constexpr (CONTINUES) block_continues<END, WORDS>(S, L, st);  // a hit starts its shadow ray or bounce here (render_pool.hip)
             }
         }
         CHUNKY_PHASE_END(X, "block");
@@ -210,6 +212,7 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
             asm volatile("; chunky-mark models");  // (comments in the compiled kernel: tools/isa_scratch.py finds the model blocks' phase by them)
             if (st == ST_MODEL) {
                 st = block_phase<TREE, END, false, kBlockModels, WORDS == 6>(S, L);
+                if constexpr (CONTINUES) block_continues<END, WORDS>(S, L, st);
             }
             asm volatile("; chunky-mark models-end");
         }

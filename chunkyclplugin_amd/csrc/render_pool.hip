@@ -25,6 +25,9 @@
 #ifndef CHUNKY_STAGING_STORE
 #define CHUNKY_STAGING_STORE 0  // how finished samples reach the staging array: 0 = non-temporal (measured best), 1-3: see the deposit site
 #endif
+#ifndef CHUNKY_BLOCK_CONTINUES
+#define CHUNKY_BLOCK_CONTINUES 1  // the block test starts the shadow ray or bounce where it hits (block_continues below); 0 (tuning builds): every trace that ends goes to SHADE
+#endif
 
 namespace chunky {
 
@@ -447,6 +450,44 @@ DEV void march_loop(const SceneView& Sm, const RenderOpts& Om, LaneState& L, Lan
         marching = live & ~cand;
         nm = __popcll(marching);
     } while (nm >= stay);
+}
+
+// BLOCK starts the shadow ray or the bounce where its test hits.  A trace that ends goes to SHADE, but for a hit SHADE only colours the
+// throughput, draws the two numbers of the sun direction or the bounce and runs trace_setup: no sky, no deposit, no new sample — and the
+// whole wave executes SHADE for it.  So the block test (the plain kernels: no entity BVHs, not the extended integrator) runs that
+// continuation itself, path_continue.inc and trace_setup, for every lane whose test just reported a hit and whose path is
+// known to go on: a main ray's hit (the shadow ray) and a shadow ray's hit (the bounce).  A bounce that reaches the depth limit ends
+// the path — known from the depth alone, before a number is drawn — and stays SHADE's, as does every miss, the deposit and the
+// hand-out of samples.  The lane leaves as a marcher (or, as from SHADE's trace_setup, for SHADE when the new ray misses the world).
+// A path runs the same helpers on the same values in the same order, its own RNG draws included: the image does not change, only which
+// lanes run together — one SHADE visit, one loop iteration and one swap round less per hit.
+// Only in scenes with the sun on (S.sun_flags & 1, wave-uniform: the word comes with the block test's own scene words).  With the sun
+// off a vertex has one trace, and in a closed room the paths of a wave go BLOCK -> SHADE -> MARCH together, 63.6 lanes per execution
+// and no swap in between; taking the hits over there splits every fifth lane off (the bounce at the depth limit) and the march runs
+// emptier: the indoor room lost 5.6 % (EXPERIMENTS 8.1), so such scenes keep the flow in which every trace that ends goes to SHADE.
+// The other scene and option words are read here, behind the test, through fresh_args: none of them lives in the loop's SGPRs.
+// (So of the included text the branch "a main ray's hit bounces" never runs here: a main ray's hit always starts the shadow ray.)
+// -DCHUNKY_BLOCK_CONTINUES=0 (tuning builds, tools/variants.sh; the default is set at the top of this file) restores that flow everywhere.
+template <int END, int WORDS>
+DEV void block_continues(const SceneView& Sb, LaneState& L, int& st) {  // for the lanes the block test just ran for: st is what it returned
+    static_assert(END == ST_SHADE, "the plain kernels only: with entity BVHs a trace does not end at the octree");
+    if (!(Sb.sun_flags & 1)) return;
+    asm volatile("; chunky-mark block-continues" : "+v"(st));  // (opaque: nothing below is started above the test)
+    const bool hit_now = st == END;
+    WaveArgPtr A = fresh_args();
+    const SceneView S = arg_copy(&A->S);
+    const RenderOpts O = arg_copy(&A->O);
+    const bool main_trace = !L.shadow;
+    // (a shadow ray is started whatever the depth; a bounce makes the depth L.depth + 1, which SHADE checks against the limit)
+    // (the sun flag is on here — the early return above — and is named again all the same: without it one proj:: instantiation spills 8 bytes)
+    const bool takes = hit_now && ((main_trace && (S.sun_flags & 1)) || (int)L.depth + 1 < O.max_depth);
+    if (takes) {
+        // the hit's colour and emittance are consumed first: with the six-word record they sit where trace_setup writes 1/d and the distance
+        if (WORDS == 6) march_registers_to_hit(L);
+        bool finished = false;  // (stays false: a shadow ray never ends a path, and the bounce is below the depth limit)
+#include "path_continue.inc"
+        st = trace_setup<END, false>(S, L);
+    }
 }
 
 // Between two phases of the kernel's loop: the phase chosen, as a value the optimiser cannot see through (no instruction) — it cannot
