@@ -157,7 +157,7 @@ struct chunky_render {
     DevBuf staging;  // render_pool: one launch's samples, [tile of 256 slots][pass][slot][3] floats
     DevBuf block_list;  // block shards under a kernel without the block mapping: this rank's pixels (ShardView::list)
     float* fb = nullptr;
-    std::vector<hipEvent_t> free_events;  // the one pool the five clocks below borrow from
+    std::vector<hipEvent_t> free_events;  // the one pool the six clocks below borrow from
     LaunchClock clock{&free_events};      // the render launches (chunky_render_kernel_time)
     KernelChoice last_choice{0, 0, 0, 0, -1, 0};  // what the most recent launch ran (chunky_render_kernel_info)
     int launch_cap = 0;  // most passes one launch carries here (staging size); 0 = not determined yet
@@ -190,6 +190,10 @@ struct chunky_render {
     DevBuf matte, matte_work, matte_set;
     FirstHitPass matte_pass{LaunchClock(&free_events)};
     int32_t matte_passes = 0;     // passes folded since the last reset
+    // chunky_render_occlusion_passes: the AO image, the SUN image (width * height floats each), then the kernel's claim counter;
+    // allocated (and zeroed) by the first occlusion call.  Record and counter are its own: no other call sees them
+    DevBuf occlusion;
+    FirstHitPass occlusion_pass{LaunchClock(&free_events)};
     // chunky_render_denoise: the filter's workspace (kept between calls) and its timing, apart from the render and AOV launches'
     DevBuf dn_work, dn_out;
     LaunchClock dn_clock{&free_events};  // (a bracket holds all launches of one call: their number is its weight)

@@ -1,5 +1,5 @@
 // kernels.hpp — host-visible launch interface of the kernel translation units (render_pool.hip, render_fallback.hip,
-// aux_kernels.hip, filter.hip, aov.hip, matte.hip, denoise.hip, adaptive.hip).
+// aux_kernels.hip, filter.hip, aov.hip, occlusion.hip, matte.hip, denoise.hip, adaptive.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -126,6 +126,10 @@ struct AovExImages {
 // launch_aov with the five first-hit images folded from the same trace
 hipError_t launch_aov_ex(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
                          const AovExImages& I, int* counter, hipStream_t stream, AovChoice* chosen);
+// Sun-shadow and ambient-occlusion passes (occlusion.hip): P.n <= kMaxPassesPerLaunch; ao / sun are width * height
+// floats each, folded in place over the pixel slots of shard T; ao_distance > 0 (+inf allowed); `counter` as launch_aov's.
+hipError_t launch_occlusion(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
+                            float* ao, float* sun, float ao_distance, int* counter, hipStream_t stream, AovChoice* chosen);
 // ID-matte passes (matte.hip; specification: matte_spec.h): P.n <= kMaxPassesPerLaunch; `planes` is 13 * width * height ints (six planes of
 // ids, six of counts, `other`), updated in place over the pixel slots of shard T; `counter` as launch_aov's.  The choice record is the AOV's.
 hipError_t launch_matte(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,

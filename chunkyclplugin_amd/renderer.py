@@ -385,6 +385,36 @@ class HipPathTracingRenderer:
         check(native.lib().chunky_render_aov_read_ex(self._h, int(which), ptr(out), out.size))
         return out
 
+    # --- sun shadow and ambient occlusion of the beauty sample's rays (chunky_render_occlusion_*) ------
+    def render_occlusion(self, seeds, ao_distance: float, first_buffer_spp: int = 0, sync: bool = True) -> None:
+        """Occlusion passes: pass k follows the render pass with seeds[k] through its sun ray and its first bounce ray and folds "the sun
+        ray was free" and "the bounce ray met nothing within ao_distance" (> 0; inf allowed) into two images."""
+        s = np.ascontiguousarray(seeds, np.int32)
+        check(native.lib().chunky_render_occlusion_passes(self._h, ptr(s), s.size, first_buffer_spp, float(ao_distance)))
+        if sync:
+            self.sync()
+
+    def read_occlusion(self, which: int) -> np.ndarray:
+        """One of the two images (native.AOV_AO or native.AOV_SUN) as a (height, width) float32 array."""
+        out = np.empty((self.height, self.width), np.float32)
+        check(native.lib().chunky_render_occlusion_read(self._h, int(which), ptr(out), out.size))
+        return out
+
+    def reset_occlusion(self) -> None:
+        check(native.lib().chunky_render_occlusion_reset(self._h))
+
+    def occlusion_time(self):
+        """(milliseconds, launches) of the occlusion kernel since the last call."""
+        ms, n = C.c_float(), C.c_int()
+        check(native.lib().chunky_render_occlusion_kernel_time(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def occlusion_info(self) -> dict:
+        """The instantiation the last occlusion launch ran: tree form, entity-BVH walk, workgroups, launches of the last call."""
+        out = np.zeros(4, np.int32)
+        check(native.lib().chunky_render_occlusion_kernel_info(self._h, ptr(out)))
+        return {"tree": int(out[0]), "bvh": bool(out[1]), "blocks": int(out[2]), "launches": int(out[3])}
+
     # --- antialiased ID mattes (chunky_render_matte_*) ------------------------------------------------
     def render_matte(self, seeds, sync: bool = True) -> None:
         """Matte passes: pass k traces the first ray of the render pass with seeds[k] and counts the id it hits, per pixel."""

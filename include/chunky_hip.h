@@ -438,6 +438,51 @@ int chunky_render_aov_passes_ex(chunky_render* r, const int32_t* seeds, int n, i
  * wrong count. */
 int chunky_render_aov_read_ex(chunky_render* r, int which, void* out, int64_t n_words);
 
+/* ---- two images of the light at that first surface, from the beauty sample's own rays: how much of the sun the surface sees, and how
+ * open it is to its surroundings (ambient occlusion).  The sample of pass k at pixel gid is the reference's pass-k sample cut off
+ * after its first bounce trace: RNG state seeds[k] + gid, Random_nextState, the camera ray of the target's camera (with its aperture
+ * or lens), then up to three closestIntersect calls, each with the target's draw depth and CHUNKY_OPT_BVH_CULL_BEHIND.  rec[i] is
+ * record i of chunky_render_trace_records for that (seed, gid); `sun` is bit 0 of the PackedSun flags of the scene:
+ *
+ *   image            words per pixel   first trace misses   first trace hits
+ *   CHUNKY_AOV_SUN   1 float           1.0f                 sun ? (rec[1].hit ? 0 : 1) : 0
+ *   CHUNKY_AOV_AO    1 float           1.0f                 with b = rec[sun ? 2 : 1]: (b.hit && b.distance < ao_distance) ? 0 : 1
+ *
+ * Both are folded like the AOV: (img * spp + v) / (spp + 1) in float, in pass order, spp = first_buffer_spp + k.  A miss folds 1 — a
+ * sky pixel is neither shadowed nor occluded — so either image multiplies straight over the beauty image and antialiased silhouettes
+ * come out right; the mean over the samples that hit is (image - (1 - ALPHA)) / ALPHA with the coverage CHUNKY_AOV_ALPHA of
+ * chunky_render_aov_passes_ex over the same seeds (where ALPHA > 0).
+ * The sun trace is the reference's (K/rayTracer.cl:101-106), quirks included: direction normalize(u * v + w) (K/sky.h:86), origin
+ * rec[0].point with no offset, and its record is a copy of the first hit's, distance included, so only occluders nearer than the first
+ * hit count.  SUN is therefore "the shadow the beauty image has", not a geometric visibility.  With the sun flag off there is no sun
+ * ray and no RNG draw for it: SUN folds 0 on hits, and the bounce uses the two draws right after the camera's, as the reference does.
+ * The pass follows the scene's sun flag (chunky_scene_set_sun), not CHUNKY_OPT_SUN_SAMPLING; CHUNKY_OPT_MAX_DEPTH and the
+ * experimental light-transport options are ignored, as for the AOV.
+ * The bounce trace is nextPath's (K/kernel.h:46-98): one cosine-weighted direction about rec[0].normal, origin rec[0].point + d *
+ * OFFSET, the record's distance reset to +inf — so AO is the usual cosine-weighted estimator, "the share of bounce rays that meet
+ * nothing within ao_distance".  `b.distance < ao_distance` is one strict float compare: a negative distance (which occurs) counts as
+ * occluded, a NaN distance as clear.  ao_distance is in the unit of the bounce direction (a unit vector to float rounding: blocks),
+ * > 0, and +inf is allowed: AO is then the share of bounce rays that reach the sky.
+ * The two images are allocated, zeroed, by the first chunky_render_occlusion_passes on a target.  Render, AOV, matte, denoise and
+ * adaptive calls never see them (chunky_render_aov_reset does not touch them), and these calls never touch theirs.  A set shard limits
+ * the passes to the rank's pixels; the others stay 0.  On a group's render target member 0 renders the caller's whole share, as for
+ * the AOV.  A scene update between two calls (chunky_scene_set_sun, ...) takes effect in the next one.  The Java binding does not
+ * reach these calls. */
+#define CHUNKY_AOV_AO 7
+#define CHUNKY_AOV_SUN 8
+/* Enqueue n passes over both images (asynchronous; cut into launches of at most 256 passes, which changes no bit; n = 0 is legal).
+ * CHUNKY_E_STATE before chunky_render_set_camera; CHUNKY_E_INVALID for ao_distance zero, negative or NaN. */
+int chunky_render_occlusion_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp, float ao_distance);
+/* Blocking read-back of one image (which = CHUNKY_AOV_AO or CHUNKY_AOV_SUN), width*height floats.  CHUNKY_E_STATE before the first
+ * chunky_render_occlusion_passes; CHUNKY_E_INVALID for an unknown image or a wrong count. */
+int chunky_render_occlusion_read(chunky_render* r, int which, float* out, int64_t n_floats);
+/* Zero both images. */
+int chunky_render_occlusion_reset(chunky_render* r);
+/* Device time of the occlusion launches enqueued since the last call (as chunky_render_aov_kernel_time; no other timer sees them). */
+int chunky_render_occlusion_kernel_time(chunky_render* r, float* total_ms, int* launches);
+/* The instantiation the most recent occlusion launch ran: the four words of chunky_render_aov_kernel_info. */
+int chunky_render_occlusion_kernel_info(chunky_render* r, int32_t out4[4]);
+
 /* ---- antialiased ID mattes (no reference counterpart; the idea of Cryptomatte): per pixel a short list of (id, the number of passes
  * that saw it), counted over the same camera rays the beauty passes use, so that a mask for any set of ids is a sum of shares and
  * lines up with the antialiased image.  The exact arithmetic is chunkyclplugin_amd/csrc/matte_spec.h, which the kernels and the
