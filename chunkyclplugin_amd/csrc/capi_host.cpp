@@ -130,6 +130,28 @@ extern "C" int chunky_widetree_lookup(const int32_t* tree, int64_t n_ints, int d
     return CHUNKY_OK;
 }
 
+extern "C" int chunky_widetree_hit_top(const int32_t* tree, int64_t n_ints, int depth, const int32_t* level_bits, int n_levels,
+                                       const int32_t* blocks, int64_t n_block_ints, int32_t* hit_top) {
+    if (int rc = check_ints(tree, n_ints, "widetree_hit_top")) return rc;
+    if (int rc = check_ints(blocks, n_block_ints, "widetree_hit_top palette")) return rc;
+    if (n_ints < 1 || !hit_top) return fail(CHUNKY_E_INVALID, "widetree_hit_top: bad arguments");
+    int bits[kWideMaxLevels];
+    int nlev;
+    if (level_bits) {
+        if (n_levels < 1 || n_levels > kWideMaxLevels) return fail(CHUNKY_E_INVALID, "widetree_hit_top: 1..%d levels", kWideMaxLevels);
+        nlev = n_levels;
+        for (int i = 0; i < nlev; i++) bits[i] = level_bits[i];
+    } else {
+        nlev = default_wide_levels(depth, bits);
+    }
+    WideTree wt;
+    const char* why = "";
+    if (!build_wide_tree(tree, n_ints, depth, bits, nlev, &wt, &why)) return fail(CHUNKY_E_INVALID, "wide tree: %s", why);
+    annotate_wide_tree(&wt, blocks, n_block_ints);
+    *hit_top = wt.hit_top;
+    return CHUNKY_OK;
+}
+
 // ------------------------------------------------------------------------------------ tone map
 // The last steps of the GAMMA and ACES curves for one channel value (post_processing_filter.cl:24-27, rgba.h:9-14) on the
 // host, with the rt_pow the kernels and the checkers share: pow(c, 1/2.2) * 255 + 0.5 -> (uint), saturating -> min(255).

@@ -489,7 +489,17 @@ extern "C" int chunky_render_phase_stats(chunky_render* r, uint64_t* out24, int 
     if (!out24) return fail(CHUNKY_E_INVALID, "phase_stats: NULL output");
     HIP_TRY(hipStreamSynchronize(r->ctx->stream));
     HIP_TRY(hipMemcpy(out24, (char*)r->work_counter.p + 8, 192, hipMemcpyDeviceToHost));
-    if (reset) HIP_TRY(hipMemset((char*)r->work_counter.p + 8, 0, 192));
+    if (reset) HIP_TRY(hipMemset((char*)r->work_counter.p + 8, 0, 200));  // (with the word of chunky_render_march_above behind the 24)
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_march_above(chunky_render* r, uint64_t* out1, int reset) {
+    if (r && !r->parts.empty()) return chunky_render_march_above(r->parts[0], out1, reset);
+    LOCK_RENDER(r);
+    if (!out1) return fail(CHUNKY_E_INVALID, "march_above: NULL output");
+    HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    HIP_TRY(hipMemcpy(out1, (char*)r->work_counter.p + 200, 8, hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(hipMemset((char*)r->work_counter.p + 200, 0, 8));
     return CHUNKY_OK;
 }
 

@@ -381,10 +381,22 @@ int scene_view(chunky_scene* s, SceneView* v, bool want_emitters) {
     }
     v->wide = s->wide_meta.nlev > 0 ? (const uint32_t*)s->wide.p : nullptr;
     v->wide_nlev = s->wide_meta.nlev;
+    // (annotated above whenever the octree or the block palette changed; with no wide tree the world's own top: nothing is capped)
+    v->hit_top = s->wide_meta.nlev > 0 ? s->wide_meta.hit_top : (int)(1u << (s->octree_depth < 31 ? s->octree_depth : 30));
     for (int i = 0; i < 6; i++) {
         v->wide_shift[i] = s->wide_meta.shift[i];
         v->wide_bits[i] = s->wide_meta.bits[i];
     }
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_scene_hit_top(chunky_scene* scene, int32_t* hit_top) {
+    if (scene && !scene->replicas.empty()) return chunky_scene_hit_top(scene->replicas[0], hit_top);  // replicas agree
+    LOCK_SCENE(scene);
+    if (!hit_top) return fail(CHUNKY_E_INVALID, "scene_hit_top: NULL");
+    SceneView v;
+    if (int rc = scene_view(scene, &v, false)) return rc;
+    *hit_top = v.hit_top;
     return CHUNKY_OK;
 }
 

@@ -416,13 +416,29 @@ DEV unsigned world_edge(const SceneView& S) {
     asm("" : "+s"(edge));
     return edge;
 }
-template <int TREE, bool GUARD = true>
+// The cap (CAP, render_pool's plain kernels): a ray that runs upwards (inv.y > 0) and stands at or above S.hit_top — 1 + the highest
+// cell any leaf that can be hit reaches (widetree.hpp) — can find nothing any more: its y does not decrease along the march (rounding
+// is monotonic, every step is >= kOffset > 0, po lies inside its leaf), so every later cell is one where no block test runs, and the
+// trace ends as the miss it would have ended as at the world's edge, the draw depth or the distance limit; nothing of the march is
+// read after a miss (trace_setup starts the next one).  `ybias` is 2^depth - hit_top for such a lane and 0 for every other (march_ybias,
+// once per entry into the loop): by + ybias >= 2^depth exactly when by >= hit_top, so the cap is one add and one more OR in the
+// in-world test.  `by` itself stays in the OR: a negative by (an upward ray entering through the bottom face) plus ybias may be a small
+// positive number, and the lane would read the tree at a negative index; INT_MAX (a NaN) plus ybias wraps negative: outside either way.
+DEV int march_ybias(const SceneView& S, const LaneState& L, unsigned edge) { return L.inv.y > 0 ? (int)(edge - (unsigned)S.hit_top) : 0; }
+// `above` (the profiling build): counts the lane-steps of upward rays at or above hit_top, capped or not
+template <int TREE, bool GUARD = true, bool CAP = false>
 DEV void march_step(const SceneView& S, const RenderOpts& O, LaneState& L, LaneMask marching, LaneMask& cand_out,
-                    LaneMask& live_out, int& data, int& level, const unsigned edge, const LaneMask* far_masks = nullptr, int* entry = nullptr) {
+                    LaneMask& live_out, int& data, int& level, const unsigned edge, const LaneMask* far_masks = nullptr, int* entry = nullptr,
+                    int ybias = 0, unsigned long long* above = nullptr) {
     f3 pos = L.o + L.d * L.dist_march;
     f3 po = pos + L.d * kOffset;
     int bx = floor_to_int(po.x), by = floor_to_int(po.y), bz = floor_to_int(po.z);
-    const bool inside = (unsigned)(bx | by | bz) < edge;  // every coordinate in [0, 2^depth): one compare (a negative one has the top bit set)
+    // every coordinate in [0, 2^depth): one compare (a negative one has the top bit set)
+    // (the add in unsigned arithmetic: it may wrap)
+    const bool inside = CAP ? ((unsigned)(bx | by | bz) | ((unsigned)by + (unsigned)ybias)) < edge : (unsigned)(bx | by | bz) < edge;
+    if (above)
+        *above += (unsigned long long)__popcll(marching & __ballot(L.steps < O.draw_depth) & __ballot(!(L.dist_march > L.h.distance)) &
+                                               __ballot((unsigned)(bx | by | bz) < edge && L.inv.y > 0 && by >= S.hit_top));
     const LaneMask live = marching & __ballot(L.steps < O.draw_depth) & __ballot(!(L.dist_march > L.h.distance)) & __ballot(inside);
     int kind;
     leaf_lookup<TREE>(S, bx, by, bz, data, level, kind, inside, entry);

@@ -12,6 +12,8 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
     // integrator (their pools are small: measured -4 % / -2 %)
     constexpr bool SPLIT = SORT;
     constexpr bool CONTINUES = CHUNKY_BLOCK_CONTINUES && !BVH && !EXT;  // the block test goes on where it hits (render_pool.hip block_continues)
+    // upward rays end their march above the highest leaf that can be hit (path_state.hpp march_step): the plain kernels on the re-laid-out tree
+    constexpr bool CAP = CHUNKY_MARCH_CAP && TREE != 0 && !BVH && !EXT;
     static_assert(!SORT || (TREE != 0 && !BVH && !EXT), "sorted block tests: the plain kernel on the re-laid-out tree only");
     extern __shared__ int lds[];
     const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
@@ -63,6 +65,7 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
     L.bvh_dist = 0;
     unsigned long long prof[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long swap_rounds = 0, swapped = 0;
+    unsigned long long above = 0;  // (STATS) march lane-steps of upward rays at or above S.hit_top
     PartTimers parts{{0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, 0};
     unsigned long long t_begin = 0;
     if (STATS) t_begin = __builtin_amdgcn_s_memtime();
@@ -182,9 +185,9 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
             const float ninf = -rt_inf();
             const bool guard = ((__ballot(L.inv.x == ninf) | __ballot(L.inv.y == ninf) | __ballot(L.inv.z == ninf)) & entered) != 0;  // (masks on the scalar unit)
             if (guard)
-                march_loop<TREE, true, STATS>(Sm, Om, L, marching, to_block, data, level, nm, stay, far_masks, prof, SPLIT ? &entry : nullptr);
+                march_loop<TREE, true, STATS, CAP>(Sm, Om, L, marching, to_block, data, level, nm, stay, far_masks, prof, SPLIT ? &entry : nullptr, &above);
             else
-                march_loop<TREE, false, STATS>(Sm, Om, L, marching, to_block, data, level, nm, stay, far_masks, prof, SPLIT ? &entry : nullptr);
+                march_loop<TREE, false, STATS, CAP>(Sm, Om, L, marching, to_block, data, level, nm, stay, far_masks, prof, SPLIT ? &entry : nullptr, &above);
             const bool found = in_mask(to_block);
             L.cand_data = found ? data : L.cand_data;
             L.cand_level = found ? level : L.cand_level;
@@ -370,5 +373,6 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
         atomicAdd(&stats[12], swap_rounds);
         atomicAdd(&stats[13], swapped);
         for (int k = 0; k < 10; k++) atomicAdd(&stats[14 + k], parts.t[k]);
+        atomicAdd(&stats[24], above);  // chunky_render_march_above
     }
 }

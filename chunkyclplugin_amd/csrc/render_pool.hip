@@ -28,6 +28,9 @@
 #ifndef CHUNKY_BLOCK_CONTINUES
 #define CHUNKY_BLOCK_CONTINUES 1  // the block test starts the shadow ray or bounce where it hits (block_continues below); 0 (tuning builds): every trace that ends goes to SHADE
 #endif
+#ifndef CHUNKY_MARCH_CAP
+#define CHUNKY_MARCH_CAP 1  // an upward ray's march ends above the highest leaf that can be hit (path_state.hpp march_step); 0 (tuning builds): at the world's edge only
+#endif
 
 namespace chunky {
 
@@ -374,7 +377,7 @@ constexpr int kSampleBatch = 256;  // sample indices a wave claims per atomic (m
 // the fullest range instead of the next 5.77; tile groups dealt round-robin to the XCDs instead of stripes: groups of 1-8
 // tiles -0.6 ... +0.9 %, 16-240 tiles +3 %.
 constexpr int kXcdRanges = 8;  // one range per XCD (16 / 32 / 64 ranges measured -0.3 / -0.9 / -1.7 %)
-constexpr int kXcdCounters = 64;  // the range counters sit at work_counter[64 ...] (behind the claim counter and the 24 profile words)
+constexpr int kXcdCounters = 64;  // the range counters sit at work_counter[64 ...] (behind the claim counter and the 25 profile words)
 DEV int xcd_id() {
     unsigned x;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
@@ -435,17 +438,20 @@ DEV unsigned xcd_claim(int* counters, XcdClaim& c, int& tried, bool need, unsign
 // walk), SHADE; [9..11] wave lifetimes; [12] swap rounds, [13] paths swapped; [14..] parts of SHADE.
 // The march loop of one entry into MARCH: steps while `stay` lanes or more are marching.  Who found a candidate accumulates in
 // `to_block`; `data` / `level` are the leaf every lane looked at last.
-template <int TREE, bool GUARD, bool STATS>
+// CAP: upward rays end their march above the highest leaf that can be hit (path_state.hpp march_step); `above` counts, in the profiling
+// build, the lane-steps that the cap ends or would end.
+template <int TREE, bool GUARD, bool STATS, bool CAP>
 DEV void march_loop(const SceneView& Sm, const RenderOpts& Om, LaneState& L, LaneMask& marching, LaneMask& to_block, int& data, int& level,
-                    int& nm, int stay, const LaneMask* far_masks, unsigned long long* prof, int* entry = nullptr) {
+                    int& nm, int stay, const LaneMask* far_masks, unsigned long long* prof, int* entry = nullptr, unsigned long long* above = nullptr) {
     const unsigned edge = world_edge(Sm);
+    const int ybias = CAP ? march_ybias(Sm, L, edge) : 0;  // one more register for the length of the loop; not part of a parked path
     do {
         if (STATS) {
             prof[0] += 1;
             prof[1] += (unsigned long long)nm;
         }
         LaneMask cand, live;
-        march_step<TREE, GUARD>(Sm, Om, L, marching, cand, live, data, level, edge, far_masks, entry);
+        march_step<TREE, GUARD, CAP>(Sm, Om, L, marching, cand, live, data, level, edge, far_masks, entry, ybias, STATS ? above : nullptr);
         to_block |= cand;
         marching = live & ~cand;
         nm = __popcll(marching);

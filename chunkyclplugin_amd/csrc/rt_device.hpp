@@ -108,6 +108,10 @@ struct SceneView {
     const int4* __restrict__ tri_rec;  // = bvh_rec + tri_off bytes: one allocation, so either kind of record is a 32-bit offset off one base
     unsigned tri_off;
     int world_root, actor_root;  // reference of each BVH's root
+    // 1 + the highest cell y of any leaf that can be hit (widetree.hpp WideTree::hit_top; 2^depth for a scene with no wide tree: no
+    // cap).  render_pool ends an upward ray's march there (path_state.hpp march_step).  It stands in what was four bytes of padding
+    // ahead of the next pointer: no other member moved, and the kernels that do not read it are the kernels they were.
+    int hit_top;
     // emitter next-event estimation (extension): every emitter leaf of the octree as {x, y, z, level << 25 | block pointer},
     // in pre-order — the list of oracle/port.c port_list_emitters
     const int4* __restrict__ emitters;

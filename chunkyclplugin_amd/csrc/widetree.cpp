@@ -122,17 +122,43 @@ bool build_wide_tree(const int32_t* oct, int64_t n, int depth, const int* level_
 }
 
 void annotate_wide_tree(WideTree* t, const int32_t* blocks, int64_t n) {
-    for (uint32_t& e : t->data) {
-        if (!(e & kWideLeaf)) continue;
-        const uint32_t ptr = e & kWidePtrMask;
-        if (ptr == kWidePtrMask) continue;  // ANY_TYPE: marked when the tree was built
-        uint32_t kind = 2;
-        if (ptr != 0 && (int64_t)ptr + 1 < n) {
-            const int32_t type = blocks[ptr];
-            kind = type == 1 ? 0u : ((type == 2 || type == 3) ? 1u : 2u);
+    // node by node from the top, so that every entry's y is known: (offset of the node, its level, y of its first cell)
+    struct Node {
+        size_t base;
+        int level, y0;
+    };
+    int top = 0;
+    std::vector<Node> todo;
+    if (t->nlev > 0 && !t->data.empty()) todo.push_back(Node{0, 0, 0});
+    while (!todo.empty()) {
+        const Node nd = todo.back();
+        todo.pop_back();
+        const int b = t->bits[nd.level], sh = t->shift[nd.level];
+        const size_t count = (size_t)1 << (3 * b);
+        if (nd.base + count > t->data.size()) continue;  // (a tree the builder did not make)
+        for (size_t i = 0; i < count; i++) {
+            uint32_t& e = t->data[nd.base + i];
+            const int y = nd.y0 + (int)(((i >> b) & (((size_t)1 << b) - 1)) << sh);
+            if (!(e & kWideLeaf)) {
+                if (nd.level + 1 < t->nlev) todo.push_back(Node{(size_t)e, nd.level + 1, y});
+                continue;
+            }
+            const uint32_t ptr = e & kWidePtrMask;
+            if (ptr == kWidePtrMask) continue;  // ANY_TYPE: marked when the tree was built
+            uint32_t kind = 2;
+            if (ptr != 0 && (int64_t)ptr + 1 < n) {
+                const int32_t type = blocks[ptr];
+                kind = type == 1 ? 0u : ((type == 2 || type == 3) ? 1u : 2u);
+            }
+            e = (e & ~(kWideNoHit | kWideKindLow)) | ((kind & 2u) ? kWideNoHit : 0u) | ((kind & 1u) ? kWideKindLow : 0u);
+            if (!(kind & 2u)) {
+                // the entry's cells end where its octree leaf ends or below it (a leaf larger than the node's cells fills several entries)
+                const int end = y + (1 << sh);
+                top = end > top ? end : top;
+            }
         }
-        e = (e & ~(kWideNoHit | kWideKindLow)) | ((kind & 2u) ? kWideNoHit : 0u) | ((kind & 1u) ? kWideKindLow : 0u);
     }
+    t->hit_top = top;
 }
 
 }  // namespace chunky

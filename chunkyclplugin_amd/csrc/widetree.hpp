@@ -36,6 +36,9 @@ struct WideTree {
     int nlev = 0;
     int shift[kWideMaxLevels] = {0};
     int bits[kWideMaxLevels] = {0};
+    // 1 + the highest cell y of any leaf that can be hit (0: none can; 2^depth: one reaches the world's top): set by
+    // annotate_wide_tree.  A ray that runs upwards from there on can hit nothing any more (path_state.hpp march_step).
+    int hit_top = 0;
 };
 
 // Returns false (with *why set) when the octree cannot be expressed: depth > 15, a block pointer
@@ -43,7 +46,7 @@ struct WideTree {
 bool build_wide_tree(const int32_t* oct, int64_t n_ints, int depth, const int* level_bits, int nlev, WideTree* out,
                      const char** why);
 
-// Sets the kind bits of every leaf from the block palette (2 ints per block: modelType, pointer).
+// Sets the kind bits of every leaf from the block palette (2 ints per block: modelType, pointer), and t->hit_top.
 void annotate_wide_tree(WideTree* t, const int32_t* block_palette, int64_t n_ints);
 
 // Default split: ceil(depth/3) levels of 3 bits each (top level padded), see widetree.cpp.

@@ -287,6 +287,9 @@ def lib() -> C.CDLL:
             "chunky_widetree_lookup": [vp, i64, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(i64)],
             "chunky_addr32_word": [vp, vp, C.c_int, C.POINTER(C.c_uint32)],
             "chunky_scene_addr32": [vp, C.POINTER(C.c_uint32)],
+            "chunky_widetree_hit_top": [vp, i64, C.c_int, vp, C.c_int, vp, i64, C.POINTER(i32)],
+            "chunky_scene_hit_top": [vp, C.POINTER(i32)],
+            "chunky_render_march_above": [vp, vp, C.c_int],
         }
         for name, args in sig.items():
             if not hasattr(L, name) and os.environ.get("CHUNKY_HIP_LIB") and os.environ.get("CHUNKY_HIP_LIB_EARLIER") == "1":
@@ -347,6 +350,18 @@ def widetree_lookup(tree: np.ndarray, depth: int, xyz: np.ndarray, level_bits=No
                                        0 if lb is None else lb.size, ptr(xyz), len(xyz), ptr(data), ptr(level),
                                        C.byref(n_entries)))
     return data, level, n_entries.value
+
+
+def widetree_hit_top(tree: np.ndarray, depth: int, blocks: np.ndarray, level_bits=None) -> int:
+    """chunky_widetree_hit_top: 1 + the highest cell y of any leaf of the re-laid-out octree that can be hit under the block
+    palette `blocks` (0: none can; 2^depth: one reaches the world's top)."""
+    tree = np.ascontiguousarray(tree, np.int32)
+    blocks = np.ascontiguousarray(blocks, np.int32)
+    lb = None if level_bits is None else np.ascontiguousarray(level_bits, np.int32)
+    top = C.c_int32()
+    check(lib().chunky_widetree_hit_top(ptr(tree), tree.size, depth, None if lb is None else ptr(lb), 0 if lb is None else lb.size,
+                                        ptr(blocks) if blocks.size else None, blocks.size, C.byref(top)))
+    return top.value
 
 
 ADDR32_ATLAS, ADDR32_SKY, ADDR32_RECORDS = 1, 2, 4  # chunky_addr32_word / chunky_scene_addr32 (csrc/addr32.h)

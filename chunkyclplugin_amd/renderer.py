@@ -196,6 +196,12 @@ class HipSceneLoader:
         check(native.lib().chunky_scene_addr32(self._h, C.byref(word)))
         return word.value
 
+    def hit_top(self) -> int:
+        """chunky_scene_hit_top: 1 + the highest cell y of any leaf that can be hit, as the next launch carries it."""
+        top = C.c_int32()
+        check(native.lib().chunky_scene_hit_top(self._h, C.byref(top)))
+        return top.value
+
     def selftest_helpers(self, which: int, rows, tree: int = 1):
         """chunky_selftest_helpers: the device counterpart of reference helper `which` on rows of 32 floats; returns
         (rows of 12 floats, tree form used for row kind 14)."""
@@ -324,6 +330,12 @@ class HipPathTracingRenderer:
         # render_pool's sorted instantiation: the model blocks' phase ("block" is then the full cubes alone)
         d["model"] = {"execs": int(out[22]) >> 40, "lanes": int(out[22]) & ((1 << 40) - 1), "cycles": int(out[23])}
         return d
+
+    def march_above(self, reset: bool = True) -> int:
+        """chunky_render_march_above: of the march lanes of phase_stats, the lane-steps of upward rays at or above hit_top."""
+        out = np.zeros(1, np.uint64)
+        check(native.lib().chunky_render_march_above(self._h, ptr(out), 1 if reset else 0))
+        return int(out[0])
 
     def preview(self) -> np.ndarray:
         out = np.empty(self.width * self.height, np.int32)

@@ -342,6 +342,9 @@ int chunky_render_kernel_info(chunky_render* r, int32_t out8[8]);
  * new sample; then, of the pool kernel's phase for model blocks — where it tests them apart from the full cubes, CHUNKY_OPT_KERNEL
  * bit 8 — lanes (executions in bits 40 up) and cycles): 24 values in all. */
 int chunky_render_phase_stats(chunky_render* r, uint64_t* out24, int reset);
+/* One more count of the same profile (pool kernel only): of the MARCH lanes counted above, the lane-steps taken at or above the
+ * scene's hit_top (chunky_scene_hit_top) by a ray that runs upwards — steps that can find nothing.  Reset by either call. */
+int chunky_render_march_above(chunky_render* r, uint64_t* out1, int reset);
 
 /* Preview kernel (K/rayTracer.cl:115-217; OpenClPreviewRenderer.java:47-115): width*height ARGB ints. */
 int chunky_render_preview(chunky_render* r, int32_t* argb_out);
@@ -874,6 +877,14 @@ int chunky_filter_frame_device(chunky_ctx* ctx, int64_t n_pixels, float exposure
  * uses the default split.  *n_entries receives the size of the re-laid-out array. */
 int chunky_widetree_lookup(const int32_t* tree, int64_t n_ints, int depth, const int32_t* level_bits, int n_levels,
                            const int32_t* xyz /* 3n */, int n, int32_t* data_out, int32_t* level_out, int64_t* n_entries);
+/* The same tree annotated with the block palette `blocks` (as the upload does): *hit_top = 1 + the highest cell y of any leaf that
+ * can be hit — 0 when none can, 2^depth when one reaches the world's top.  render_pool ends the march of a ray that runs upwards
+ * once it is at or above that height. */
+int chunky_widetree_hit_top(const int32_t* tree, int64_t n_ints, int depth, const int32_t* level_bits, int n_levels,
+                            const int32_t* blocks, int64_t n_block_ints, int32_t* hit_top);
+/* The hit_top the next launch on this scene carries (needs a complete scene, as a launch does; 2^depth for a scene whose octree has
+ * no wide tree).  On a group: member 0's. */
+int chunky_scene_hit_top(chunky_scene* scene, int32_t* hit_top);
 
 /* ---- host-side verification hook for how the kernels address scene arrays (no device needed).  At upload the library decides, per
  * array, whether kernels may read it as "base + 32-bit unsigned byte offset" (DESIGN.md section 5).  chunky_addr32_word is that

@@ -34,6 +34,7 @@ r.phase_stats(reset=True)
 r.kernel_time()
 r.render_passes(seeds[passes:], first_buffer_spp=passes)
 ms, n = r.kernel_time()
+above = r.march_above(reset=False)  # (read first: phase_stats resets both)
 st = r.phase_stats()
 samples = sc.width * sc.height * passes // world
 w = st.pop("waves")
@@ -47,6 +48,8 @@ for k, v in st.items():
               "cycles_per_exec": v["cycles"] / max(v["execs"], 1), "time_share": v["cycles"] / max(tot, 1)}
 info = r.kernel_info()
 out["kernel"] = info
+if info["pool"] >= 0:  # upward rays at or above the highest leaf that can be hit: with the cap (the default build) each trace's last step, without it (-DCHUNKY_MARCH_CAP=0) every step it takes up there
+    out["march_above_hit_top"] = {"hit_top": loader.hit_top(), "lane_steps": above, "share_of_march_lanes": above / max(st["march"]["lanes"], 1)}
 if info["pool"] >= 0:  # render_pool: the two counters are swap rounds and paths swapped
     out["swaps"] = {"rounds_per_sample": ho["execs"] * 64 / samples, "paths_per_round": ho["cycles"] / max(ho["execs"], 1),
                     "paths_swapped_per_sample": ho["cycles"] / samples}
