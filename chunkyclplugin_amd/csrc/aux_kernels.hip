@@ -285,11 +285,11 @@ hipError_t launch_trace_records(int variant, const SceneView& S, const CameraVie
     const int block = 256;
     int grid = (n + block - 1) / block;
     if (grid <= 0) return hipSuccess;
-    if (use_wide(variant, S))
-        hipLaunchKernelGGL(trace_records_kernel<-1>, dim3(grid), dim3(block), stack_lds_bytes(S, block), stream, S, C, O,
+    if (use_wide(variant, scene_facts(S)))
+        hipLaunchKernelGGL(trace_records_kernel<-1>, dim3(grid), dim3(block), stack_lds_bytes(scene_facts(S), block), stream, S, C, O,
                            seed, gids_dev, n, out, counts, radiance);
     else
-        hipLaunchKernelGGL(trace_records_kernel<0>, dim3(grid), dim3(block), stack_lds_bytes(S, block), stream, S, C, O,
+        hipLaunchKernelGGL(trace_records_kernel<0>, dim3(grid), dim3(block), stack_lds_bytes(scene_facts(S), block), stream, S, C, O,
                            seed, gids_dev, n, out, counts, radiance);
     return hipGetLastError();
 }
@@ -298,10 +298,10 @@ hipError_t launch_preview(int variant, const SceneView& S, const CameraView& C, 
                           hipStream_t stream) {
     const int block = 256;
     int grid = (C.width * C.height + block - 1) / block;
-    if (use_wide(variant, S))
-        hipLaunchKernelGGL(preview_lanes<-1>, dim3(grid), dim3(block), stack_lds_bytes(S, block), stream, S, C, O, argb);
+    if (use_wide(variant, scene_facts(S)))
+        hipLaunchKernelGGL(preview_lanes<-1>, dim3(grid), dim3(block), stack_lds_bytes(scene_facts(S), block), stream, S, C, O, argb);
     else
-        hipLaunchKernelGGL(preview_lanes<0>, dim3(grid), dim3(block), stack_lds_bytes(S, block), stream, S, C, O, argb);
+        hipLaunchKernelGGL(preview_lanes<0>, dim3(grid), dim3(block), stack_lds_bytes(scene_facts(S), block), stream, S, C, O, argb);
     return hipGetLastError();
 }
 
@@ -374,7 +374,7 @@ hipError_t launch_math_selftest(int which, int n, const float* a, const float* b
 hipError_t launch_helpers_selftest(const SceneView& S, int which, int tree, int n, const float* in, float* out, int* tree_used, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     if (which == 18 && !(S.bvh_rec && S.tri_rec && S.mat8)) return hipErrorNotSupported;
-    int t = tree ? tree_form(0, S) : 0;
+    int t = tree ? tree_form(0, scene_facts(S)) : 0;
     typedef void (*Kernel)(SceneView, int, int, const float*, float*);
     Kernel k;
     switch (t) {

@@ -23,8 +23,9 @@ static int adaptive_state(const char* who, chunky_render* r, SceneView* S) {
     if (!r->have_camera) return fail(CHUNKY_E_STATE, "%s before set_camera", who);
     if (int rc = scene_view(r->scene, S, r->opts.nee != 0)) return rc;
     S->bvh_cull = r->opts.bvh_cull;
-    if (int rc = check_extended_opts(who, r, *S)) return rc;
-    if (!pool_kernel_applies(r->kernel_variant, *S, r->opts, r->work_counter.p != nullptr))
+    const RenderPlan plan = render_plan(r, *S);
+    if (int rc = check_extended_opts(who, plan)) return rc;
+    if (plan.family != KernelFamily::pool)
         return fail(CHUNKY_E_STATE, "%s: the scene or the options send this target to the fallback kernels, which stage no samples", who);
     return CHUNKY_OK;
 }

@@ -297,7 +297,8 @@ int group_gather(chunky_render* r);
 void scene_unref(chunky_scene* s);                                                      // capi_scene.hip
 int scene_view(chunky_scene* s, SceneView* v, bool want_emitters = false);
 int launch_pass_cap(const ShardView& T, int width, int height, size_t budget, int most);  // capi_render.hip
-int check_extended_opts(const char* who, const chunky_render* r, const SceneView& S);
+RenderPlan render_plan(const chunky_render* r, const SceneView& S);                      // what plan_render decides for r's passes over S
+int check_extended_opts(const char* who, const RenderPlan& plan);
 int read_floats(const char* who, chunky_render* r, const void* src, void* out, int64_t n, int64_t need);
 int first_hit_kernel_time(chunky_render* r, FirstHitPass chunky_render::*pass, float* total_ms, int* launches);  // capi_aov.hip
 int first_hit_kernel_info(const char* who, chunky_render* r, FirstHitPass chunky_render::*pass, int32_t out4[4]);

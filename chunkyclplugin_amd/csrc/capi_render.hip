@@ -304,19 +304,17 @@ int launch_pass_cap(const ShardView& T, int width, int height, size_t budget, in
     return (int)(cap > most ? most : cap);
 }
 
+// What launch_render is going to run for r's passes over S (launch_plan.hpp), as far as it is known before a launch's pass count is:
+// the kernel family, whether a block shard needs the pixel list, the most passes per launch, the answer to the extended options
+RenderPlan render_plan(const chunky_render* r, const SceneView& S) {
+    return plan_render(r->kernel_variant, scene_facts(S), r->opts, r->cam.projector_type, r->shard, 0, r->work_counter.p != nullptr, false, false);
+}
+
 // the extended light-transport options exist in render_pool's default instantiations only: CHUNKY_E_STATE where r's kernel
 // option, scene or max depth would send it elsewhere
-int check_extended_opts(const char* who, const chunky_render* r, const SceneView& S) {
-    if (!opts_extended(r->opts)) return CHUNKY_OK;
-    const bool bvh = !S.world_bvh_empty || !S.actor_bvh_empty;
-    if ((r->kernel_variant & (1 | 2 | 4 | 8)) || (bvh && !(S.bvh_rec && S.tri_rec && S.mat8)))
-        return fail(CHUNKY_E_STATE, "%s: the extended light-transport options need the default kernel (CHUNKY_OPT_KERNEL 0)", who);
-    if (!S.wide)  // their instantiations walk the re-laid-out tree only (an octree deeper than 15 levels has none)
-        return fail(CHUNKY_E_STATE, "%s: the extended light-transport options need an octree the wide re-layout takes (depth <= 15)", who);
-    // the fallback kernels never read these options: a set render_pool refuses (max depth 255) would render the reference's transport
-    if (!pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr))
-        return fail(CHUNKY_E_STATE, "%s: the extended light-transport options need max depth <= 254 (CHUNKY_OPT_MAX_DEPTH)", who);
-    return CHUNKY_OK;
+int check_extended_opts(const char* who, const RenderPlan& plan) {
+    if (plan.ext_refusal == ExtRefusal::none) return CHUNKY_OK;
+    return fail(CHUNKY_E_STATE, "%s: %s", who, ext_refusal_text(plan.ext_refusal));
 }
 
 // a device-to-host read-back of exactly `need` 4-byte values on r's stream; src == nullptr: nothing has been rendered into it yet
@@ -336,13 +334,13 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
     SceneView S;
     if (int rc = scene_view(r->scene, &S, r->opts.nee != 0)) return rc;
     S.bvh_cull = r->opts.bvh_cull;
-    if (int rc = check_extended_opts("render_passes", r, S)) return rc;
+    const RenderPlan plan = render_plan(r, S);
+    if (int rc = check_extended_opts("render_passes", plan)) return rc;
     r->ad_resumable = false;  // the call is accepted: it writes the framebuffer (chunky_render_run / _run_ex end it here and in chunky_render_reset)
     if (r->clock.full())
         if (int rc = r->clock.collect()) return rc;
     if (r->shard.n_local <= 0) return CHUNKY_OK;  // this rank (or group member) owns no tile of so small an image: nothing to render
-    if (r->shard.world != 1 && r->shard.tile == 0 && !r->shard.list &&
-        !pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr)) {
+    if (plan.needs_list && !r->shard.list) {
         // a share of 16 x 16 blocks (every group member has one) and a scene / option set render_pool does not take: the
         // fallback kernels render the same pixels from a list
         const std::vector<int32_t> px = block_pixel_list(r->width, r->height, r->shard);
@@ -352,7 +350,7 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
         r->shard.n_list = (int)px.size();
     }
     // render_pool takes up to kMaxPoolPasses per launch, the other kernels what the kernel-argument segment holds
-    const int most = pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr) ? kMaxPoolPasses : kMaxPassesPerLaunch;
+    const int most = plan.most;
     if (r->launch_cap <= 0 || r->launch_cap_most != most) {
         r->launch_cap = std::max(1, launch_pass_cap(r->shard, r->width, r->height, kStagingBytes, most));  // sized by the tiles THIS rank renders
         r->launch_cap_most = most;
@@ -477,7 +475,7 @@ extern "C" int chunky_render_kernel_info(chunky_render* r, int32_t out8[8]) {
     } else {  // before the first launch: what chunky_render_passes is going to decide for this scene and option set
         SceneView S;
         int most = kMaxPassesPerLaunch;
-        if (scene_view(r->scene, &S, false) == CHUNKY_OK && pool_kernel_applies(r->kernel_variant, S, r->opts, r->work_counter.p != nullptr)) most = kMaxPoolPasses;
+        if (scene_view(r->scene, &S, false) == CHUNKY_OK) most = render_plan(r, S).most;
         out8[6] = std::max(1, launch_pass_cap(r->shard, r->width, r->height, kStagingBytes, most));
     }
     return CHUNKY_OK;

@@ -19,6 +19,8 @@
 //                          folded before the launch (first_buffer_spp)
 //   store(gid, n_pixels)   write the pixel
 #pragma once
+#include <type_traits>
+
 #include "path_state.hpp"
 
 namespace chunky {
@@ -111,64 +113,50 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fold::
     }
 }
 
-// The lookup form: the one launch_render's render_pool picks for the scene (tree_form; with entity BVHs the dense tops of one and
-// two levels, else the generic walk), so that a first-hit pass and a render pass of a view read the octree the same way.
-inline int first_hit_tree(int variant, const SceneView& S, bool bvh) {
-    const int tree = tree_form(variant, S);
-    if (tree == 0) return 0;
-    if (bvh) return (tree == 17 || tree == 18) ? tree : -1;
-    return (tree >= 16 && tree <= 19) ? tree : -1;
+// The instantiation of a first-hit kernel for a tree form and the entity BVHs (launch_plan.hpp plan_first_hit and
+// CHUNKY_FIRST_HIT_INSTANCES): pick(tree constant, BVH constant) names the kernel; null when the list has no such form.
+template <class Kernel, class Pick>
+Kernel first_hit_lookup(const FirstHitPlan& plan, Pick pick) {
+#define CHUNKY_FIRST_HIT_CASE(TREE, BVH) \
+    if (plan.tree == (TREE) && plan.bvh == (BVH)) return pick(std::integral_constant<int, TREE>(), std::integral_constant<bool, BVH>());
+    CHUNKY_FIRST_HIT_INSTANCES(CHUNKY_FIRST_HIT_CASE)
+#undef CHUNKY_FIRST_HIT_CASE
+    return nullptr;
 }
 
-// the instantiation for the tree form and the camera
-template <class Fold, bool PROJ>
-void (*first_hit_instance(int tree, bool bvh))(FirstHitArgs<typename Fold::Out>) {
-    if (bvh) {
-        switch (tree) {
-            case 0: return first_hit_kernel<Fold, 0, true, PROJ>;
-            case 17: return first_hit_kernel<Fold, 17, true, PROJ>;
-            case 18: return first_hit_kernel<Fold, 18, true, PROJ>;
-            default: return first_hit_kernel<Fold, -1, true, PROJ>;
-        }
-    } else {
-        switch (tree) {
-            case 0: return first_hit_kernel<Fold, 0, false, PROJ>;
-            case 16: return first_hit_kernel<Fold, 16, false, PROJ>;
-            case 17: return first_hit_kernel<Fold, 17, false, PROJ>;
-            case 18: return first_hit_kernel<Fold, 18, false, PROJ>;
-            case 19: return first_hit_kernel<Fold, 19, false, PROJ>;
-            default: return first_hit_kernel<Fold, -1, false, PROJ>;
-        }
-    }
+// A launch of a kernel that takes FirstHitArgs<Out> (first_hit_kernel, occlusion.hip's occlusion_kernel): a persistent grid, no more
+// workgroups than one claim per wave.  pick(tree constant, BVH constant, PROJ constant) names the instantiation.
+template <class Out, class Pick>
+hipError_t launch_first_hit_args(Pick pick, int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
+                                 const PassSeeds& P, const Out& out, int* counter, hipStream_t stream, AovChoice* chosen) {
+    if (P.n <= 0 || T.n_local <= 0) return hipSuccess;
+    if (P.n > kMaxPassesPerLaunch) return hipErrorInvalidValue;
+    const FirstHitPlan plan = plan_first_hit(variant, scene_facts(S));
+    typedef void (*Kernel)(FirstHitArgs<Out>);
+    const Kernel k = C.projector_type > 0 ? first_hit_lookup<Kernel>(plan, [&](auto tree, auto bvh) { return pick(tree, bvh, std::true_type()); })
+                                          : first_hit_lookup<Kernel>(plan, [&](auto tree, auto bvh) { return pick(tree, bvh, std::false_type()); });
+    if (!k) return hipErrorInvalidDeviceFunction;  // a plan outside the list: an error, never another kernel
+    const int block = kLaunchBlock;
+    const size_t lds = stack_lds_bytes(scene_facts(S), block);
+    const long long n_units = pool_tiles(T, C.width, C.height) * (kSampleTile / kFirstHitUnit);
+    int grid = 0;
+    if (hipError_t e = persistent_grid(k, block, lds, (n_units + block / 64 - 1) / (block / 64), &grid)) return e;
+    if (chosen) *chosen = AovChoice{plan.tree, plan.bvh ? 1 : 0, grid};
+    hipError_t e = hipMemsetAsync(counter, 0, sizeof(int), stream);
+    if (e != hipSuccess) return e;
+    FirstHitArgs<Out> A{S, C, T, P, O.draw_depth, (int)n_units, counter, out};
+    A.T.list = nullptr;  // (pool_slot_gid maps every shard form itself)
+    A.T.n_list = 0;
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(block), lds, stream, A);
+    return hipGetLastError();
 }
 
 template <class Fold>
 hipError_t launch_first_hit(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
                             const typename Fold::Out& out, int* counter, hipStream_t stream, AovChoice* chosen) {
-    if (P.n <= 0 || T.n_local <= 0) return hipSuccess;
-    if (P.n > kMaxPassesPerLaunch) return hipErrorInvalidValue;
-    const bool bvh = !S.world_bvh_empty || !S.actor_bvh_empty;
-    const int tree = first_hit_tree(variant, S, bvh);
-    auto k = C.projector_type > 0 ? first_hit_instance<Fold, true>(tree, bvh) : first_hit_instance<Fold, false>(tree, bvh);
-    const int block = 256;
-    const size_t lds = stack_lds_bytes(S, block);
-    int n_cu = 0, occ = 0;
-    hipError_t e = current_device_cus(&n_cu);
-    if (e != hipSuccess) return e;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, block, lds);
-    if (e != hipSuccess) return e;
-    const long long n_units = pool_tiles(T, C.width, C.height) * (kSampleTile / kFirstHitUnit);
-    const long long want = (n_units + block / 64 - 1) / (block / 64);  // no more workgroups than one claim per wave
-    long long grid = (long long)n_cu * (occ > 0 ? occ : 1);
-    if (grid > want) grid = want;
-    if (chosen) *chosen = AovChoice{tree, bvh ? 1 : 0, (int)grid};
-    e = hipMemsetAsync(counter, 0, sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    FirstHitArgs<typename Fold::Out> A{S, C, T, P, O.draw_depth, (int)n_units, counter, out};
-    A.T.list = nullptr;  // (pool_slot_gid maps every shard form itself)
-    A.T.n_list = 0;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(block), lds, stream, A);
-    return hipGetLastError();
+    return launch_first_hit_args<typename Fold::Out>(
+        [](auto tree, auto bvh, auto proj) -> void (*)(FirstHitArgs<typename Fold::Out>) { return first_hit_kernel<Fold, decltype(tree)::value, decltype(bvh)::value, decltype(proj)::value>; },
+        variant, S, C, O, T, P, out, counter, stream, chosen);
 }
 
 }  // namespace chunky

@@ -6,6 +6,7 @@
 
 #include <atomic>
 
+#include "launch_plan.hpp"  // RenderOpts, the launch limits, pool_tiles: what the launch planner shares with the launchers
 #include "shard_map.hpp"  // ShardView, FastDiv: the host arithmetic of the shard-to-pixel map
 
 struct DnCoeffs;  // denoise_spec.h
@@ -14,10 +15,8 @@ namespace chunky {
 
 struct SceneView;
 struct CameraView;
-struct RenderOpts;
 
 constexpr int kMaxTraces = 10;        // 5 path segments x (main + shadow trace)
-constexpr int kBvhStackEntries = 64;  // K/bvh.h:38
 
 // Layout shared with include/chunky_hip.h (chunky_hit_record) and oracle/oracle_scene.h.
 struct HitRecord {
@@ -33,10 +32,7 @@ struct HitRecord {
 // Seeds of the passes one launch runs, passed by value in the kernel-argument segment (wave-uniform
 // scalar loads, no per-launch host->device copy): pass k uses seed[k] and bufferSpp first_spp + k
 // (OpenClPathTracingRenderer.java:106-109).
-constexpr int kMaxPassesPerLaunch = 256;  // seeds travel in the kernel-argument segment (4 KB in all); the pass index is 8 bits
-// render_pool takes longer launches when the staged samples fit (a share of the image on several GPUs: fewer end-of-launch tails):
-// the seeds then travel in device memory (launch_render's seeds_dev)
-constexpr int kMaxPoolPasses = 1024;
+// (kMaxPassesPerLaunch, and render_pool's kMaxPoolPasses: launch_plan.hpp)
 struct PassSeeds {
     int n, first_spp;
     int seed[kMaxPassesPerLaunch];
@@ -53,15 +49,9 @@ struct KernelChoice {
     int ext;     // the extended integrator (CHUNKY_OPT_SUN_SAMPLING / _EMITTERS / _BSDF / _EMITTER_NEE at non-default values)
     int sorted;  // render_pool: full cubes and model blocks tested in phases of their own
 };
-// render_pool's tiles of 256 pixel slots: the image's 16 x 16-pixel blocks with one rank (edge blocks padded), the rank's own
-// blocks or 256-slot runs with several (path_state.hpp pool_slot_gid)
-inline long long pool_tile_count(const ShardView& T, int width, int height) {
-    if (T.world != 1) return ((long long)T.n_local + 255) / 256;
-    return (long long)((width + 15) / 16) * ((height + 15) / 16);
-}
 // staging floats render_pool needs for a launch of n passes over this rank's tiles
 inline size_t staging_floats(const ShardView& T, int width, int height, int n_passes) {
-    return 3 * (size_t)pool_tile_count(T, width, height) * 256 * (size_t)n_passes;
+    return 3 * (size_t)pool_tiles(T, width, height) * kSampleTile * (size_t)n_passes;
 }
 
 // compute units of the CURRENT device (cached per device index: members of a group and threads of a host may sit on different GPUs)
@@ -82,8 +72,18 @@ inline hipError_t current_device_cus(int* n_cu) {
     *n_cu = n;
     return hipSuccess;
 }
-// true when launch_render will run render_pool for this scene / option set (else launch_fallback: render_waves, render_lanes)
-bool pool_kernel_applies(int variant, const SceneView& S, const RenderOpts& O, bool have_queue_and_staging);
+// A persistent grid: as many workgroups as the device holds at once (its compute units x the kernel's occupancy at this block size
+// and LDS), and no more than `want`, what the work can feed
+template <class Kernel>
+inline hipError_t persistent_grid(Kernel k, int block, size_t lds, long long want, int* grid) {
+    int n_cu = 0, occ = 0;
+    if (hipError_t e = current_device_cus(&n_cu)) return e;
+    if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, block, lds)) return e;
+    const long long fits = (long long)n_cu * (occ > 0 ? occ : 1);
+    *grid = (int)(fits > want ? want : fits);
+    return hipSuccess;
+}
+// Which kernel a launch runs is decided by plan_render (launch_plan.hpp), here and in the C API alike.
 // P.n <= kMaxPassesPerLaunch with the seeds in P.seed, or (render_pool only) up to kMaxPoolPasses with the seeds in seeds_dev
 hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                          const PassSeeds& P, float* res, int* work_counter, hipStream_t stream,
@@ -94,8 +94,8 @@ hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, c
 hipError_t launch_render_stats(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                                const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
                                float* staging, const int* seeds_dev, float* fold_stats);
-// the kernels behind render_pool (render_fallback.hip): render_waves, render_lanes
-hipError_t launch_fallback(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
+// the kernels behind render_pool (render_fallback.hip): render_waves, render_lanes, as `plan` names them
+hipError_t launch_fallback(const RenderPlan& plan, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                            const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen);
 // read-back exchange of a multi-GPU group: pack = true copies the pixels of this shard's slots from the image `fb` to `packed`
 // (3 floats per slot, padding slots skipped), pack = false scatters them back into an image

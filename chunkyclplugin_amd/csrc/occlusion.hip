@@ -175,55 +175,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(occlus
     }
 }
 
-// the instantiation for the tree form and the camera (first_hit_instance's table)
-template <bool PROJ>
-static void (*occlusion_instance(int tree, bool bvh))(OcclusionArgs) {
-    if (bvh) {
-        switch (tree) {
-            case 0: return occlusion_kernel<0, true, PROJ>;
-            case 17: return occlusion_kernel<17, true, PROJ>;
-            case 18: return occlusion_kernel<18, true, PROJ>;
-            default: return occlusion_kernel<-1, true, PROJ>;
-        }
-    } else {
-        switch (tree) {
-            case 0: return occlusion_kernel<0, false, PROJ>;
-            case 16: return occlusion_kernel<16, false, PROJ>;
-            case 17: return occlusion_kernel<17, false, PROJ>;
-            case 18: return occlusion_kernel<18, false, PROJ>;
-            case 19: return occlusion_kernel<19, false, PROJ>;
-            default: return occlusion_kernel<-1, false, PROJ>;
-        }
-    }
-}
-
-// (launch_first_hit's arithmetic: a persistent grid from the CU count and the occupancy, no more workgroups than one claim per wave)
+// (first_hit_pass.hpp launch_first_hit_args: the first-hit passes' tree forms and launch arithmetic)
 hipError_t launch_occlusion(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
                             float* ao, float* sun, float ao_distance, int* counter, hipStream_t stream, AovChoice* chosen) {
-    if (P.n <= 0 || T.n_local <= 0) return hipSuccess;
-    if (P.n > kMaxPassesPerLaunch) return hipErrorInvalidValue;
-    const bool bvh = !S.world_bvh_empty || !S.actor_bvh_empty;
-    const int tree = first_hit_tree(variant, S, bvh);
-    auto k = C.projector_type > 0 ? occlusion_instance<true>(tree, bvh) : occlusion_instance<false>(tree, bvh);
-    const int block = 256;
-    const size_t lds = stack_lds_bytes(S, block);
-    int n_cu = 0, occ = 0;
-    hipError_t e = current_device_cus(&n_cu);
-    if (e != hipSuccess) return e;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, block, lds);
-    if (e != hipSuccess) return e;
-    const long long n_units = pool_tiles(T, C.width, C.height) * (kSampleTile / kFirstHitUnit);
-    const long long want = (n_units + block / 64 - 1) / (block / 64);
-    long long grid = (long long)n_cu * (occ > 0 ? occ : 1);
-    if (grid > want) grid = want;
-    if (chosen) *chosen = AovChoice{tree, bvh ? 1 : 0, (int)grid};
-    e = hipMemsetAsync(counter, 0, sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    OcclusionArgs A{S, C, T, P, O.draw_depth, (int)n_units, counter, OcclusionOut{ao, sun, ao_distance}};
-    A.T.list = nullptr;  // (pool_slot_gid maps every shard form itself)
-    A.T.n_list = 0;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(block), lds, stream, A);
-    return hipGetLastError();
+    return launch_first_hit_args<OcclusionOut>(
+        [](auto tree, auto bvh, auto proj) -> void (*)(OcclusionArgs) { return occlusion_kernel<decltype(tree)::value, decltype(bvh)::value, decltype(proj)::value>; },
+        variant, S, C, O, T, P, OcclusionOut{ao, sun, ao_distance}, counter, stream, chosen);
 }
 
 }  // namespace chunky

@@ -226,7 +226,7 @@ DEV int shard_gid(const ShardView& T, int local) {
 // scene: L1 / L2 hits) — all of them with one rank, every world-th with several (chunky_render_set_shard with tile 0); with a
 // run length given instead, a tile is one of the rank's runs of consecutive pixel indices.  Returns width * height for a
 // padding slot.
-constexpr int kTileLog = 4, kTileEdge = 1 << kTileLog, kSampleTile = kTileEdge * kTileEdge;  // tiles of 16 x 16 pixels: pixel slots per tile
+// (kTileLog, kTileEdge, kSampleTile — tiles of 16 x 16 pixels, pixel slots per tile — and pool_tiles: launch_plan.hpp)
 // Inside a tile the samples are ordered (sub-block of kSubBlock pixel slots, pass, slot in the sub-block): the 256 samples a
 // wave claims at a time are 256 / kSubBlock consecutive passes of one small block of pixels — 64 passes of 2 x 2 pixels — so
 // the paths a wave starts together begin as nearly the same ray: their march steps read the same tree entries (L1 hits,
@@ -276,10 +276,6 @@ DEV SlotPixel pool_slot_pixel(const ShardView& T, int width, int height, int slo
     const int x = (bx << kTileLog) + (sb % (kTileEdge / kSubW)) * kSubW + px % kSubW,
               y = (by << kTileLog) + (sb / (kTileEdge / kSubW)) * kSubH + px / kSubW;
     return SlotPixel{(x < width && y < height) ? y * width + x : width * height, x, y};
-}
-__host__ __device__ inline long long pool_tiles(const ShardView& T, int width, int height) {
-    if (T.world != 1) return ((long long)T.n_local + kSampleTile - 1) / kSampleTile;  // runs of T.tile pixels, or (T.tile == 0) the rank's blocks
-    return (long long)((width + kTileEdge - 1) >> kTileLog) * ((height + kTileEdge - 1) >> kTileLog);
 }
 // lanes of the wave for which p holds, as a 32-bit scalar: one s_bcnt1_i32_b64 (the result is cast to int at once — kept as the
 // 64-bit value __builtin_popcountll returns, the comparisons that follow would be 64-bit ones, which the scalar unit lacks)
@@ -714,21 +710,5 @@ DEV f3 cosine_direction(f3 n, float x1, float x2) {
 #define CHUNKY_W_SHADE 4
 #endif
 constexpr int kWMarch = CHUNKY_W_MARCH, kWBlock = CHUNKY_W_BLOCK, kWShade = CHUNKY_W_SHADE;
-
-// variant bit 0 set = force the reference-layout octree walk (K/octree.h:81-89 as written)
-inline bool use_wide(int variant, const SceneView& S) { return S.wide != nullptr && !(variant & 1); }
-// the form of leaf_lookup for a scene: 0 reference layout, 16 + n dense top over n levels of 8x8x8 nodes, -1 any other wide split
-inline int tree_form(int variant, const SceneView& S) {
-    if (!use_wide(variant, S)) return 0;
-    int tree = S.wide_nlev <= 4 ? 16 + S.wide_nlev - 1 : -1;
-    for (int i = 1; i < S.wide_nlev; i++)
-        if (S.wide_bits[i] != 3) tree = -1;
-    return tree;
-}
-inline size_t stack_lds_bytes(const SceneView& S, int block) {
-    bool need = !S.world_bvh_empty || !S.actor_bvh_empty;
-    int entries = S.bvh_stack_entries > 0 && S.bvh_stack_entries < kBvhStackEntries ? S.bvh_stack_entries : kBvhStackEntries;
-    return need ? (size_t)entries * block * sizeof(int) : 0;
-}
 
 }  // namespace chunky

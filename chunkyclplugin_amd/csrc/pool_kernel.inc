@@ -3,10 +3,10 @@
 // rt_device.hpp projected_ray).  One text, two kernels: the timed instantiations keep their code and registers exactly, and the
 // projected camera runs every form they run.
 // SORT: full cubes and model blocks are tested in phases of their own (on the re-laid-out tree, whose leaf entries say which a block is);
-// launch_pool picks it for scenes with many model blocks
+// plan_render (launch_plan.cpp) picks it for scenes with many model blocks
 template <int TREE, int K, bool STATS, bool BVH = false, bool EXT = false, bool SORT = false>
 __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_BVH_WAVES : CHUNKY_POOL_WAVES))) render_pool(WaveArgs unused_by_name) {
-    constexpr int WORDS = EXT ? 9 : (BVH ? 8 : CHUNKY_POOL_WORDS);  // 16-byte words of a parked path (pool_pack)
+    constexpr int WORDS = pool_words(EXT, BVH);  // 16-byte words of a parked path (pool_pack; launch_plan.hpp: the launch sizes the LDS with the same two functions)
     constexpr int END = BVH ? ST_TRACED : ST_SHADE;  // where a lane goes when the octree part of a trace ends
     // candidates sorted into full cubes (ST_BLOCK) and model blocks (ST_MODEL); not instantiated with entity BVHs or the extended
     // integrator (their pools are small: measured -4 % / -2 %)
@@ -22,7 +22,7 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
     {
         // per wave: K parked records, their tag / list scratch, then (BVH) one to-visit stack per path of the pool
         const unsigned depth = BVH ? fresh_args()->stack_bytes : 0u;  // entries per stack
-        char* base = (char*)lds + wave * (K * 16 * WORDS + K * 8 + (64 + K) * depth * 4);
+        char* base = (char*)lds + wave * pool_wave_lds_bytes(K, WORDS, depth);
         P.park = (uint4*)base;
         P.tags = (int*)(base + K * 16 * WORDS);
         P.list = P.tags + K;

@@ -257,9 +257,8 @@ DEV int next_sample_single(const SceneView& S, const CameraView& C, const ShardV
 // the image is bit-identical for every G.  Two pixels are open per group — passes are issued from
 // the newer one while the older one waits for its last paths — so a group never drains between pixels.
 constexpr int kHandoverBatch = 8;
-// parked radiances per open pixel (a pass is issued only inside fold + ring): two per lane of the group; the rings
-// of a workgroup take 18 KB of LDS either way, which leaves room for five workgroups per CU
-constexpr int ring_size(int group) { return 2 * group; }
+// parked radiances per open pixel (a pass is issued only inside fold + ring): two per lane of the group, ring_size (launch_plan.hpp:
+// the launch sizes the LDS with it); the rings of a workgroup take 18 KB of LDS either way, which leaves room for five workgroups per CU
 struct GroupLds {
     float4* rad;  // [2][kRing] {r, g, b, tag}
     int* hdr;     // [2][8]  {gid, fold, issue, serial, mean.x, mean.y, mean.z, -}
@@ -515,66 +514,39 @@ __global__ void __launch_bounds__(256, (BVH ? 4 : 5)) render_waves(WaveArgs unus
     }
 }
 
-// variant bit 1 set = render_lanes; otherwise render_waves with variant bits 4-5 forcing its lanes per pixel (1 / 8 / 16).
-// The fallback kernels exist for the reference octree layout (0) and the generic wide tree (-1) only.
-hipError_t launch_fallback(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
+// The fallback kernels as planned (launch_plan.cpp plan_fallback: render_lanes or render_waves, the lanes per pixel, the tree
+// form — the reference octree layout (0) and the generic wide tree (-1) only).
+hipError_t launch_fallback(const RenderPlan& plan, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                            const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen) {
-    const bool has_bvh = !S.world_bvh_empty || !S.actor_bvh_empty;
-    const int block = 256;
-    const int tree = use_wide(variant, S) ? -1 : 0;
-    if (!(variant & 2) && work_counter) {
+    const int block = kLaunchBlock;
+    if (plan.family == KernelFamily::waves) {
         // wave-scheduled persistent kernel: one resident grid, lanes pull pixels from a counter
-        int n_cu = 0;
-        if (hipError_t e = current_device_cus(&n_cu)) return e;
-        const size_t stack = stack_lds_bytes(S, block);
-        size_t lds = stack;
-        // lanes per pixel (see next_sample): 8; 16 or 32 when this GPU owns few pixels (multi-GPU tile split: the fewer
-        // pixels per group, the longer the tail of the launch)
-        int group = T.n_local < (3 << 17) ? 32 : (T.n_local < (3 << 18) ? 16 : 8);
-        while (group > 8 && P.n < 2 * group) group /= 2;  // a group needs a few passes per lane to stay busy
-        if (P.n < 2 * group) group = 1;
-        switch ((variant >> 4) & 3) {  // variant bits 4-5 force the group size (tests cover all three)
-            case 1: group = 1; break;
-            case 2: group = 8; break;
-            case 3: group = 16; break;
-            default: break;
-        }
-        if (group == 32 && has_bvh) group = 16;
         typedef void (*Kernel)(WaveArgs);
-        Kernel k;
-#define WAVES_KERNEL(G) (has_bvh ? (tree == 0 ? render_waves<0, G, true> : render_waves<-1, G, true>) \
-                                 : (tree == 0 ? render_waves<0, G, false> : render_waves<-1, G, false>))
-        switch (group) {
-            case 1: k = WAVES_KERNEL(1); break;
-            case 16: k = WAVES_KERNEL(16); break;
-            case 32: k = tree == 0 ? render_waves<0, 32, false> : render_waves<-1, 32, false>; break;
-            default: group = 8; k = WAVES_KERNEL(8); break;
-        }
-#undef WAVES_KERNEL
-        if (group > 1) lds += (size_t)(block / group) * (2 * ring_size(group) * 16 + 64);
-        int occ = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, block, lds);
-        if (e != hipSuccess) return e;
-        int bpc = occ > 0 ? occ : 1;
+        Kernel k = nullptr;
+#define CHUNKY_WAVES_CASE(TREE, G, BVH) \
+        if (plan.tree == (TREE) && plan.group == (G) && plan.bvh == (BVH)) k = render_waves<TREE, G, BVH>;
+        CHUNKY_WAVES_INSTANCES(CHUNKY_WAVES_CASE)
+#undef CHUNKY_WAVES_CASE
+        if (!k) return hipErrorInvalidDeviceFunction;  // a plan outside the list: an error, never another kernel
         // a pixel keeps `group` lanes busy (one pass each), so that many lanes per pixel are worth launching
-        const long long want = ((long long)T.n_local * group + block - 1) / block;
-        int grid = n_cu * bpc;
-        if ((long long)grid > want) grid = (int)want;
+        const long long want = ((long long)T.n_local * plan.group + block - 1) / block;
+        int grid = 0;
+        if (hipError_t e = persistent_grid(k, block, plan.lds, want, &grid)) return e;
         if (grid <= 0 || P.n <= 0) return hipSuccess;
-        if (chosen) *chosen = KernelChoice{tree, group, has_bvh ? 1 : 0, grid, -1, 0};
-        e = hipMemsetAsync(work_counter, 0, sizeof(int), stream);
+        if (chosen) *chosen = KernelChoice{plan.tree, plan.group, plan.bvh ? 1 : 0, grid, -1, 0};
+        hipError_t e = hipMemsetAsync(work_counter, 0, sizeof(int), stream);
         if (e != hipSuccess) return e;
-        const WaveArgs A = make_wave_args(S, C, O, T, P, work_counter, res, (unsigned long long*)(work_counter + 2), (unsigned)stack);
-        hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, stream, A);
+        const WaveArgs A = make_wave_args(S, C, O, T, P, work_counter, res, (unsigned long long*)(work_counter + 2), (unsigned)((size_t)plan.depth * block * sizeof(int)));  // (the to-visit stacks' bytes: the rings lie behind them)
+        hipLaunchKernelGGL(k, dim3(grid), dim3(block), plan.lds, stream, A);
         return hipGetLastError();
     }
     int grid = (T.n_local + block - 1) / block;
     if (grid <= 0 || P.n <= 0) return hipSuccess;
-    if (chosen) *chosen = KernelChoice{tree, 0, has_bvh ? 1 : 0, grid, -1, 0};
-    if (tree != 0)
-        hipLaunchKernelGGL(render_lanes<-1>, dim3(grid), dim3(block), stack_lds_bytes(S, block), stream, S, C, O, T, P, res);
-    else
-        hipLaunchKernelGGL(render_lanes<0>, dim3(grid), dim3(block), stack_lds_bytes(S, block), stream, S, C, O, T, P, res);
+    if (chosen) *chosen = KernelChoice{plan.tree, 0, plan.bvh ? 1 : 0, grid, -1, 0};
+#define CHUNKY_LANES_CASE(TREE) \
+    if (plan.tree == (TREE)) hipLaunchKernelGGL(render_lanes<TREE>, dim3(grid), dim3(block), plan.lds, stream, S, C, O, T, P, res);
+    CHUNKY_LANES_INSTANCES(CHUNKY_LANES_CASE)
+#undef CHUNKY_LANES_CASE
     return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // render_pool.hip — the hot path: render_pool (a persistent grid whose waves each run a pool of 64 + K path state machines
 // phase by phase — MARCH / BLOCK / SHADE, plus the entity-BVH walk — voted over the pool, samples claimed per XCD) and
 // fold_kernel (the running mean of K/rayTracer.cl:109-112 over the staged samples, in pass order); the read-back exchange
-// of a multi-GPU group; launch_render.  DESIGN.md section 5 describes the kernel.
+// of a multi-GPU group; launch_render, which runs what launch_plan.cpp planned.  DESIGN.md section 5 describes the kernel.
 //
 // Compiled with -ffp-contract=off (see rt_device.hpp).
 #include <hip/hip_runtime.h>
@@ -9,7 +9,7 @@
 #include <cstdlib>
 
 // This unit's kernels read the atlas, the sky and the record arrays by 32-bit offsets off scalar bases (rt_device.hpp load_at; launch_render
-// starts them only for scenes whose SceneView::addr32 allows all three).  render_pool_bvh.hip, which includes this file, does not: the
+// starts them only for scenes whose SceneView::addr32 allows all three: launch_plan.cpp).  render_pool_bvh.hip, which includes this file, does not: the
 // entity-BVH instantiations keep the 64-bit addresses.  (-DCHUNKY_ADDR32_FORMS=n: experiments, the arrays one at a time.)
 #if !defined(CHUNKY_POOL_BVH_TU) && !defined(CHUNKY_ADDR32_FORMS)
 #define CHUNKY_ADDR32_FORMS 7
@@ -172,7 +172,7 @@ DEV int shade_phase_ext(const SceneView& S, const RenderOpts& O, LaneState& L) {
 // afterwards — the same float recurrence in the same order, so the image is bit-identical, and the pixel groups, LDS
 // rings and hand-over rounds of render_waves (15 % of its time) do not exist here.
 // A lane (or parked slot) that holds no path and wants a sample is "fresh": state ST_SHADE — the SHADE branch serves it — with
-// the path depth 255 (kFreshDepth; launch_pool sends max_depth above 254 to the other kernels).  The states a path can be in
+// the path depth 255 (kFreshDepth; plan_render sends max_depth above 254 to the other kernels).  The states a path can be in
 // between two phase executions are then 0 MARCH, 1 BLOCK, 2 SHADE, 3 DONE (+ ST_BVH / ST_LEAF with entity BVHs, + ST_MODEL where full
 // cubes and model blocks are tested in phases of their own: SORT): the state IS its
 // class, the census is one compare per class, and the vote and the swap need no classification (round 6: a fresh path used to be
@@ -192,7 +192,7 @@ DEV int phase_class(int st) {
 
 // A parked path is WORDS 16-byte words.  6 words without entity BVHs (1/d and the distance marched share their registers, and so
 // their word, with the hit's colour and emittance: pool_pack; the march-step count shares word 0 with the flags —
-// launch_pool sends draw depths above 65535 to render_waves — and the candidate block takes the place of the BVH cursor's
+// plan_render sends draw depths above 65535 to render_waves — and the candidate block takes the place of the BVH cursor's
 // word); 8 with them; 9 for the extended integrator.  The flag bits sit where LaneState's bit-fields have them.
 template <int WORDS>
 DEV void pool_pack(const LaneState& L, uint4 (&v)[WORDS]) {
@@ -334,12 +334,7 @@ DEV int pool_swap(PoolLds P, LaneState& L, int& st, int& ptag, int X, int lane) 
 #ifndef CHUNKY_POOL_BVH_WAVES
 #define CHUNKY_POOL_BVH_WAVES 5
 #endif
-#ifndef CHUNKY_POOL_WORDS
-#define CHUNKY_POOL_WORDS 6   // 16-byte words of a parked path without entity BVHs (7 in tuning builds: 1/d and colour side by side)
-#endif
-#ifndef CHUNKY_POOL_PARK
-#define CHUNKY_POOL_PARK (CHUNKY_POOL_WORDS == 6 ? 64 : 56)   // paths parked per wave (LDS: WORDS x 16 + 8 bytes each; 6 x 4 waves x 64 x 104 B fill 156 of 160 KB)
-#endif
+// (CHUNKY_POOL_WORDS and CHUNKY_POOL_PARK, which the choice of instantiation depends on: launch_plan.hpp)
 #ifndef CHUNKY_POOL_REFILL
 #define CHUNKY_POOL_REFILL 20 // leave the march loop to refill once this many lanes are free and parked marchers exist (round 6, with the new leave rule: 16 / 20 / 24 = 7 504 / 7 526 / 7 510 headline, 4 170 / 4 140 / 4 075 indoor)
 #endif
@@ -352,7 +347,7 @@ DEV int pool_swap(PoolLds P, LaneState& L, int& st, int& ptag, int X, int lane) 
 #ifndef CHUNKY_STAY_LONGER
 #define CHUNKY_STAY_LONGER 16      // ... how many lanes emptier the march then runs before the wave leaves it
 #endif
-constexpr int kPoolPark = CHUNKY_POOL_PARK, kPoolRefill = CHUNKY_POOL_REFILL, kWalkLeave = CHUNKY_WALK_LEAVE;
+constexpr int kPoolRefill = CHUNKY_POOL_REFILL, kWalkLeave = CHUNKY_WALK_LEAVE;
 #ifndef CHUNKY_STAY_LONGER_BVH
 #define CHUNKY_STAY_LONGER_BVH 6   // ... in the kernels with entity BVHs (16 / 10 / 6 / 0 lanes: entities 225.5 / 227 / 225.6 / 223, the city with its entities 851 / 898 / 921 / 914)
 #endif
@@ -512,28 +507,28 @@ namespace proj {
 #include "pool_kernel.inc"
 #undef CHUNKY_POOL_PROJ
 }  // namespace proj
-// the instantiation of either kernel, with the same template arguments
-template <int TREE, int K, bool STATS, bool BVH = false, bool EXT = false, bool SORT = false>
-static void (*pool_kernel(bool projected))(WaveArgs) {
-    return projected ? proj::render_pool<TREE, K, STATS, BVH, EXT, SORT> : render_pool<TREE, K, STATS, BVH, EXT, SORT>;
-}
+// The instantiation a plan names (launch_plan.hpp: the lists are written there, once), of either kernel; null when the list has none.
 // The entity-BVH instantiations are compiled in a translation unit of their own, render_pool_bvh.hip: this file again, up to here, with
-// CHUNKY_IEEE_FORMS (rt_short_forms.h) — those kernels keep the compiler's divisions and roots.  `tree` and `park` as launch_pool settled
-// them (tree 17, 18 or -1; with statistics 17 or -1).  This unit instantiates no kernel with BVH = true, that one none with BVH = false.
+// CHUNKY_IEEE_FORMS (rt_short_forms.h) — those kernels keep the compiler's divisions and roots.  This unit instantiates no kernel with
+// BVH = true, that one none with BVH = false.
 typedef void (*PoolKernel)(WaveArgs);
-PoolKernel pool_kernel_bvh(int tree, int park, bool stats, bool ext, bool proj);
+#define CHUNKY_POOL_CASE(TREE, K, STATS, BVH, EXT, SORT)                                                                        \
+    if (p.tree == (TREE) && p.park == (K) && p.stats == (STATS) && p.bvh == (BVH) && p.ext == (EXT) && p.sorted == (SORT))      \
+        return p.proj ? proj::render_pool<TREE, K, STATS, BVH, EXT, SORT> : render_pool<TREE, K, STATS, BVH, EXT, SORT>;
+PoolKernel pool_kernel_bvh(const RenderPlan& p);
 #ifdef CHUNKY_POOL_BVH_TU
-PoolKernel pool_kernel_bvh(int tree, int park, bool stats, bool ext, bool proj) {
-    if (ext) return tree == 17 ? pool_kernel<17, 16, false, true, true>(proj) : (tree == 18 ? pool_kernel<18, 16, false, true, true>(proj) : pool_kernel<-1, 16, false, true, true>(proj));
-    if (stats) return tree == 17 ? pool_kernel<17, 16, true, true>(proj) : pool_kernel<-1, 16, true, true>(proj);
-#ifdef CHUNKY_POOL_BVH_PARK  // tuning builds (tools/variants.sh): a fixed pool size for the entity kernel, e.g. 8 parked paths at six waves
-    return tree == 17 ? pool_kernel<17, CHUNKY_POOL_BVH_PARK, false, true>(proj) : pool_kernel<-1, CHUNKY_POOL_BVH_PARK, false, true>(proj);
-#endif
-    if (park == 32) return tree == 17 ? pool_kernel<17, 32, false, true>(proj) : (tree == 18 ? pool_kernel<18, 32, false, true>(proj) : pool_kernel<-1, 32, false, true>(proj));
-    return tree == 17 ? pool_kernel<17, 16, false, true>(proj) : (tree == 18 ? pool_kernel<18, 16, false, true>(proj) : pool_kernel<-1, 16, false, true>(proj));
+PoolKernel pool_kernel_bvh(const RenderPlan& p) {
+    CHUNKY_POOL_BVH_INSTANCES(CHUNKY_POOL_CASE)
+    return nullptr;
 }
 }  // namespace chunky
 #else
+static_assert(kPoolAddr32Forms == (unsigned)(CHUNKY_ADDR32_FORMS), "the planner sends scenes here by the address forms these kernels have");
+static PoolKernel pool_kernel(const RenderPlan& p) {
+    if (p.bvh) return pool_kernel_bvh(p);
+    CHUNKY_POOL_INSTANCES(CHUNKY_POOL_CASE)
+    return nullptr;
+}
 
 // The running mean of K/rayTracer.cl:109-112 over the staged samples of a launch, strictly in pass order: one thread per
 // pixel and channel, reads coalesced across pixels ([pass][slot][3]).
@@ -591,109 +586,29 @@ __global__ void __launch_bounds__(256) clear_foreign_kernel(ShardView T, int wid
     a[0] = 0.0f; a[1] = 0.0f; a[2] = 0.0f;
 }
 // ------------------------------------------------------------------------------------ launchers
-// render_pool + fold_kernel.  variant bits 6-7 pick the parked paths per wave: 0 = 64 (default), 1 = none, 2 = 32 (test rigs:
-// the generic tree form only).
-static hipError_t launch_pool(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
+// render_pool + fold_kernel, as planned: look the kernel up, size the persistent grid, fill the arguments, launch, fold.
+static hipError_t launch_pool(const RenderPlan& plan, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
                               float* staging, const int* seeds_dev, float* fold_stats = nullptr) {
-    const int block = 256;
-    int n_cu = 0;
-    if (hipError_t e = current_device_cus(&n_cu)) return e;
-    if (T.n_local <= 0 || P.n <= 0) return hipSuccess;
-    const bool stats = (variant & 4) != 0;
-    int tree = tree_form(variant, S);
-    const bool bvh = !S.world_bvh_empty || !S.actor_bvh_empty;
-    int depth = 0;  // entries per to-visit stack (the reference reserves 64, K/bvh.h:38; here: the height of the taller BVH + 1)
-    if (bvh) depth = S.bvh_stack_entries > 0 && S.bvh_stack_entries < kBvhStackEntries ? S.bvh_stack_entries : kBvhStackEntries;
-    int park = kPoolPark;
-    switch ((variant >> 6) & 3) {
-        case 1: park = 0; break;
-        case 2: park = 32; break;
-        default: break;
-    }
-    PoolKernel k;
-    const bool proj = C.projector_type > 0;  // a projected camera: proj::render_pool, same template arguments
-    const bool ext = opts_extended(O);  // EXPERIMENTAL light-transport options: their own instantiations
-    // Block tests sorted by kind (full cubes / model blocks in phases of their own): for scenes in which model blocks are common
-    // (S.sort_blocks, capi_scene.hip scene_view) — the city gains 2 – 3 %, a scene with hardly any pays 1 % for the bookkeeping; variant bit 8
-    // forces it on, bit 9 off (tests and A/B runs); the plain kernel at its full pool only
-    const bool sorted = ((variant & 256) || S.sort_blocks) && !(variant & 512) && !bvh && !ext && tree != 0 && S.block_info != nullptr;
-    bool sorted_ran = false;
-    int words = bvh ? 8 : CHUNKY_POOL_WORDS;
-    if (ext) {
-        if (tree != 17 && tree != 18) tree = -1;
-        words = 9;
-        park = bvh ? 16 : 32;
-        if (bvh)
-            k = pool_kernel_bvh(tree, park, false, true, proj);
-        else
-            k = tree == 17 ? pool_kernel<17, 32, false, false, true>(proj) : (tree == 18 ? pool_kernel<18, 32, false, false, true>(proj) : pool_kernel<-1, 32, false, false, true>(proj));
-    } else if (bvh) {
-        // every path of the pool owns a to-visit stack in LDS: 32 parked paths when five workgroups per CU still fit, else 16
-        if (tree != 17 && tree != 18) tree = -1;
-        park = 5 * 4 * (32 * 136 + (64 + 32) * depth * 4) <= 160 * 1024 ? 32 : 16;
-        if (stats) {
-            if (tree != 17) tree = -1;
-            park = 16;
-            k = pool_kernel_bvh(tree, park, true, false, proj);
-#ifdef CHUNKY_POOL_BVH_PARK  // tuning builds (tools/variants.sh): a fixed pool size for the entity kernel, e.g. 8 parked paths at six waves
-        } else if (true) {
-            if (tree != 17) tree = -1;
-            park = CHUNKY_POOL_BVH_PARK;
-            k = pool_kernel_bvh(tree, park, false, false, proj);
-#endif
-        } else {
-            k = pool_kernel_bvh(tree, park, false, false, proj);
-        }
-    } else if (stats) {
-        if (tree != 17) tree = -1;
-        park = kPoolPark;
-        if (sorted) k = tree == 17 ? pool_kernel<17, kPoolPark, true, false, false, true>(proj) : pool_kernel<-1, kPoolPark, true, false, false, true>(proj);
-        else k = tree == 17 ? pool_kernel<17, kPoolPark, true>(proj) : pool_kernel<-1, kPoolPark, true>(proj);
-        sorted_ran = sorted;
-    } else if (park != kPoolPark) {
-        if (tree != 0) tree = -1;
-        if (park == 0) k = tree == 0 ? pool_kernel<0, 0, false>(proj) : pool_kernel<-1, 0, false>(proj);
-        else k = tree == 0 ? pool_kernel<0, 32, false>(proj) : pool_kernel<-1, 32, false>(proj);
-    } else if (sorted) {
-        switch (tree) {
-            case 16: k = pool_kernel<16, kPoolPark, false, false, false, true>(proj); break;
-            case 17: k = pool_kernel<17, kPoolPark, false, false, false, true>(proj); break;
-            case 18: k = pool_kernel<18, kPoolPark, false, false, false, true>(proj); break;
-            case 19: k = pool_kernel<19, kPoolPark, false, false, false, true>(proj); break;
-            default: tree = -1; k = pool_kernel<-1, kPoolPark, false, false, false, true>(proj); break;
-        }
-        sorted_ran = true;
-    } else {
-        switch (tree) {
-            case 0: k = pool_kernel<0, kPoolPark, false>(proj); break;
-            case 16: k = pool_kernel<16, kPoolPark, false>(proj); break;
-            case 17: k = pool_kernel<17, kPoolPark, false>(proj); break;
-            case 18: k = pool_kernel<18, kPoolPark, false>(proj); break;
-            case 19: k = pool_kernel<19, kPoolPark, false>(proj); break;
-            default: tree = -1; k = pool_kernel<-1, kPoolPark, false>(proj); break;
-        }
-    }
-    size_t lds = (size_t)(block / 64) * (size_t)(park * 16 * words + park * 8 + (64 + park) * depth * 4);
-    int occ = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, block, lds);
-    if (e != hipSuccess) return e;
-    const int bpc = occ > 0 ? occ : 1;
+    const PoolKernel k = pool_kernel(plan);
+    if (!k) return hipErrorInvalidDeviceFunction;  // a plan outside the list: an error, never another kernel
+    const int block = kLaunchBlock, park = plan.park;
     const long long n_tiles = pool_tiles(T, C.width, C.height);
     const long long n_samples = n_tiles * kSampleTile * P.n;  // tiles at the image's edges are padded
     // a wave keeps 64 + park paths in flight: no more workgroups than the samples can feed
     const long long want = (n_samples + (long long)(block / 64) * (64 + park) - 1) / ((long long)(block / 64) * (64 + park));
-    int grid = n_cu * bpc;
-    if ((long long)grid > want) grid = (int)want;
-    if (chosen) *chosen = KernelChoice{tree, 1, bvh ? 1 : 0, grid, park, ext ? 1 : 0, sorted_ran ? 1 : 0};
-    e = hipMemsetAsync(work_counter, 0, sizeof(int), stream);
+    int grid = 0;  // (for an empty share or no passes `want`, and so the grid, is <= 0: nothing is launched, below)
+    if (hipError_t e = persistent_grid(k, block, plan.lds, want, &grid)) return e;
+    if (T.n_local <= 0 || P.n <= 0) return hipSuccess;  // (behind the device queries: a call on a broken device fails whatever it renders)
+    if (chosen) *chosen = KernelChoice{plan.tree, 1, plan.bvh ? 1 : 0, grid, park, plan.ext ? 1 : 0, plan.sorted ? 1 : 0};
+    hipError_t e = hipMemsetAsync(work_counter, 0, sizeof(int), stream);
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(work_counter + kXcdCounters, 0, kXcdRanges * sizeof(int), stream);  // the per-XCD sample ranges (xcd_claim)
     if (e != hipSuccess) return e;
-    const WaveArgs A = make_wave_args(S, C, O, T, P, work_counter, res, (unsigned long long*)(work_counter + 2), (unsigned)depth, staging, (unsigned)n_samples,
+    const WaveArgs A = make_wave_args(S, C, O, T, P, work_counter, res, (unsigned long long*)(work_counter + 2), (unsigned)plan.depth, staging, (unsigned)n_samples,
                                       (unsigned)((n_tiles + kXcdRanges - 1) / kXcdRanges * kSampleTile * P.n), fast_div((unsigned)P.n * (unsigned)kSubBlock),
                                       fast_div((unsigned)((C.width + kTileEdge - 1) >> kTileLog)), seeds_dev);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, stream, A);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(block), plan.lds, stream, A);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (fold_stats) {  // adaptive sampling: the same running mean, and the pixels' luminance statistic from the same read
@@ -704,21 +619,6 @@ static hipError_t launch_pool(int variant, const SceneView& S, const CameraView&
                        C.width * C.height, C.width, n_tiles * kSampleTile, P.n, P.first_spp);
     return hipGetLastError();
 }
-bool pool_kernel_applies(int variant, const SceneView& S, const RenderOpts& O, bool have_queue_and_staging) {
-    const bool any_bvh = !S.world_bvh_empty || !S.actor_bvh_empty;
-    // render_pool: always without entity BVHs; with them when they could be re-laid out (rt_device.hpp bvh_rec / tri_rec)
-    // (its 6-word parked record counts march steps in 16 bits: a larger draw depth runs render_waves)
-    const bool steps_fit = (any_bvh || opts_extended(O) || O.draw_depth <= 65535) && O.max_depth <= 254;  // (path depth 255 marks a fresh path)
-    // a scene without a wide tree (an octree deeper than 15 levels, a block pointer beyond 25 bits: widetree.cpp) runs render_pool's
-    // reference-layout walk, which only the plain instantiations have (pool_kernel<0, 0 | 32 | 64>): with entity BVHs, the extended
-    // options or phase statistics launch_pool would pick a wide-tree instantiation, so those go to the fallback kernels
-    const bool form0_fits = S.wide != nullptr || (!any_bvh && !opts_extended(O) && !(variant & 4));
-    // the plain instantiations read the atlas, the sky and the records by 32-bit offsets (CHUNKY_ADDR32_FORMS above): a scene whose
-    // arrays are too large for that (scene_records.cpp addr32_word) runs the fallback kernels; the entity-BVH instantiations read any scene
-    const bool addr_fits = any_bvh || (S.addr32 & (unsigned)(CHUNKY_ADDR32_FORMS)) == (unsigned)(CHUNKY_ADDR32_FORMS);
-    return !(variant & 2) && !(variant & 8) && have_queue_and_staging && steps_fit && form0_fits && addr_fits &&
-           (!any_bvh || (S.bvh_rec && S.tri_rec && S.mat8 && !(variant & 1)));
-}
 hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                          const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
                          float* staging, const int* seeds_dev) {
@@ -727,20 +627,20 @@ hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, c
 hipError_t launch_render_stats(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                                const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
                                float* staging, const int* seeds_dev, float* fold_stats) {
-    if (pool_kernel_applies(variant, S, O, work_counter && staging)) {
-        if (P.n > kMaxPoolPasses || (P.n > kMaxPassesPerLaunch && !seeds_dev)) return hipErrorInvalidValue;
-        return launch_pool(variant, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr, fold_stats);
+    const RenderPlan plan = plan_render(variant, scene_facts(S), O, C.projector_type, T, P.n, work_counter && staging, seeds_dev != nullptr, fold_stats != nullptr);
+    switch (plan.status) {
+        case PlanStatus::invalid_value: return hipErrorInvalidValue;
+        case PlanStatus::not_supported: return hipErrorNotSupported;
+        default: break;
     }
-    if (fold_stats) return hipErrorNotSupported;  // only render_pool stages samples
-    if (P.n > kMaxPassesPerLaunch) return hipErrorInvalidValue;
-    if (T.world != 1 && T.tile == 0) {
-        // shards of 16 x 16 blocks are mapped by render_pool only: the other kernels take the rank's pixels as a list
-        if (!T.list) return hipErrorNotSupported;
+    if (plan.family == KernelFamily::pool)
+        return launch_pool(plan, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr, fold_stats);
+    if (plan.needs_list) {  // a shard of 16 x 16 blocks: the fallback kernels take the rank's pixels as a list
         ShardView F = T;
         F.n_local = T.n_list;
-        return launch_fallback(variant, S, C, O, F, P, res, work_counter, stream, chosen);
+        return launch_fallback(plan, S, C, O, F, P, res, work_counter, stream, chosen);
     }
-    return launch_fallback(variant, S, C, O, T, P, res, work_counter, stream, chosen);
+    return launch_fallback(plan, S, C, O, T, P, res, work_counter, stream, chosen);
 }
 
 hipError_t launch_gather(bool pack, const ShardView& T, int width, int height, float* fb, float* packed, hipStream_t stream) {

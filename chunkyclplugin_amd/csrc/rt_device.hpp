@@ -15,6 +15,7 @@
 #include "rt_math.h"
 #include "camera_proj.h"
 #include "addr32.h"
+#include "launch_plan.hpp"  // RenderOpts, SceneFacts
 
 namespace chunky {
 
@@ -131,19 +132,14 @@ struct CameraView {
     float lens_focus;                // projected types: the lens's focus distance (chunky_render_set_lens); nothing else reads it
 };
 
-struct RenderOpts {
-    int draw_depth;       // 256, K/rayTracer.cl:94
-    int max_depth;        // 5,   K/rayTracer.cl:107
-    float emitter_scale;  // 13,  K/rayTracer.cl:99
-    // EXPERIMENTAL light-transport options (specification: oracle/port.c trace_sample_ext).  The
-    // defaults are the reference's behaviour and select the reference kernels.
-    int sun_sampling;     // -1 as the reference (PackedSun flag bit 0), 0 never, 1 always
-    int emitters;         // 1 as the reference; 0 = emittersEnabled false
-    int bsdf;             // 1: specular / metal / roughness from material word 5
-    int nee;              // 1: emitter next-event estimation
-    int bvh_cull;         // 1: CHUNKY_OPT_BVH_CULL_BEHIND (travels to the kernels in SceneView::bvh_cull)
-};
-__host__ __device__ inline bool opts_extended(const RenderOpts& O) { return O.sun_sampling != -1 || O.emitters != 1 || O.bsdf != 0 || O.nee != 0; }
+// (RenderOpts, the other kernel argument, lives in launch_plan.hpp: the launch planner reads it too)
+
+// what the launch planner reads of a scene (launch_plan.hpp)
+inline SceneFacts scene_facts(const SceneView& S) {
+    return SceneFacts{S.wide != nullptr, S.wide_nlev, {S.wide_bits[0], S.wide_bits[1], S.wide_bits[2], S.wide_bits[3], S.wide_bits[4], S.wide_bits[5]},
+                      S.world_bvh_empty != 0, S.actor_bvh_empty != 0, S.bvh_stack_entries, S.bvh_rec && S.tri_rec && S.mat8, S.addr32,
+                      S.sort_blocks != 0, S.block_info != nullptr};
+}
 
 // Per-path state: Pixel + Ray + IntersectionRecord of K/wavefront.h:6-51, flattened.
 struct Hit {
@@ -209,7 +205,7 @@ DEV f4 unpack_unorm8(uint32_t t) {
 // Which form a kernel has is decided when its translation unit is compiled, not in the kernel: CHUNKY_ADDR32_FORMS, defined ahead of
 // every include, names the arrays (kAddr32* bits) that unit's kernels read by 32-bit offsets; without it every array keeps its 64-bit
 // per-lane addresses, the code from before these forms.  render_pool.hip defines it for the plain, sorted, proj:: and extended
-// instantiations of render_pool, and launch_render starts those only for a scene whose word has every bit (pool_kernel_applies); any
+// instantiations of render_pool, and launch_render starts those only for a scene whose word has every bit (launch_plan.cpp plan_render); any
 // other scene runs the fallback kernels, which have the 64-bit forms, as the entity-BVH instantiations do (render_pool_bvh.hip).
 // (A wave-uniform branch inside the kernel was tried first: render_pool<17, 64> stands at its 80 VGPRs, and with the branch and the
 // fences that keep the two arms' loads apart it spilled 16 to 32 bytes per lane, with any one array alone — EXPERIMENTS 7.4.)

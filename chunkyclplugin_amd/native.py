@@ -21,7 +21,7 @@ HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
 SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "matte.hip", "denoise.hip", "adaptive.hip",
            "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_occlusion.hip", "capi_matte.hip", "capi_adaptive.hip", "capi_denoise.hip",
            "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp",
-           "scene_records.cpp", "widetree.cpp"]
+           "scene_records.cpp", "widetree.cpp", "launch_plan.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
 
 MAX_TRACES = 10

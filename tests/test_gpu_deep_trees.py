@@ -21,6 +21,7 @@ from oracle.binding import PortExt
 from test_gpu_camera_projections import equivalent, projected
 from test_gpu_extensions import with_spec_words
 from test_gpu_parity import assert_radiance, bits
+from test_list_route_cpu import scene as list_route_scene
 
 pytestmark = pytest.mark.gpu
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "deep.npz"))
@@ -211,6 +212,22 @@ def test_phase_statistics_without_a_wide_tree(gpu_instance, port):
     info = r.kernel_info()
     assert info["tree"] == 0 and info["pool"] < 0, info
     check_image(r, expected(port, "outdoor", 16, sc), "depth 16 variant 4")
+    r.close()
+    loader.close()
+
+
+@pytest.mark.parametrize("name,form,variant,want", [("outdoor", 17, 4 | 512, (17, 64, False)), ("outdoor", 18, 4 | 512, (-1, 64, False)),
+                                                    ("entities", 17, 4, (17, 16, True)), ("entities", 18, 4, (-1, 16, True))])
+def test_phase_statistics_kernels(gpu_instance, port, name, form, variant, want):
+    """Variant bit 2 on a wide tree: render_pool<17 | -1, 64, STATS> (bit 9: unsorted; the sorted twins run in
+    tests/test_gpu_camera_lens_ods.py) and, with entity BVHs, <17 | -1, 16, STATS, BVH> — the dense top of one level and, for every
+    other form, the generic walk.  40 x 24: tiles padded on both edges; three passes, one launch."""
+    sc = list_route_scene(name, form).with_view(40, 24)  # (the golden scene in the octree that selects the form)
+    loader, r = make_renderer(gpu_instance, sc, variant)
+    r.render_passes(SEEDS)
+    info = r.kernel_info()
+    assert (info["tree"], info["pool"], info["bvh"]) == want and not info["ext"] and not info["sorted"], info
+    assert_radiance(r.read(), port.render_passes(binding.SceneHandle(sc), SEEDS), f"{name} form {form} variant {variant}")
     r.close()
     loader.close()
 
