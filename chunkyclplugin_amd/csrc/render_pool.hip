@@ -53,7 +53,19 @@ DEV int shade_phase_ext(const SceneView& S, const RenderOpts& O, LaneState& L) {
         const f3 base = L.throughput;
         const f3 c = mk3(L.h.color.x, L.h.color.y, L.h.color.z);
         const f3 thr_d = base * c;
-        if (O.emitters && !L.after_nee) L.radiance = L.radiance + (c * (L.h.emittance * O.emitter_scale)) * thr_d;
+        // port.c hit_is_listed: after a vertex that sampled the emitter list a hit loses its emittance only if the list holds it — the
+        // octree part of the trace won (with entity BVHs: no triangle came nearer, so the record's distance is still the one
+        // rbvh_begin copied to bvh_dist), the block is a full cube, its material has flag 2 clear and a non-zero emittance byte.
+        // (L.cand_data is the block the trace ended at; the palette reads sit behind a non-zero emittance: a rare path.)
+        bool listed = false;
+        if (L.after_nee && L.h.emittance != 0 && (!BVH || (L.oct_hit && L.h.distance == L.bvh_dist))) {
+            const int block = L.cand_data;
+            if (S.blocks[block] == 1) {
+                const int* m = S.materials + S.blocks[block + 1];
+                listed = !(m[0] & 2) && (m[4] & 0xFF) != 0;
+            }
+        }
+        if (O.emitters && !listed) L.radiance = L.radiance + (c * (L.h.emittance * O.emitter_scale)) * thr_d;
         L.after_nee = false;
         bool specular = false;
         float metal = 0, rough = 0;

@@ -150,7 +150,7 @@ int chunky_scene_write_atlas_tile(chunky_scene* scene, int x, int y, int layer, 
 /* getSky(): skyTexture RGBA8 [h][w][4] + skyIntensity (ClSky.java:28-30,43-61) */
 int chunky_scene_set_sky(chunky_scene* scene, const uint8_t* rgba, int width, int height, float intensity);
 /* The emitter list CHUNKY_OPT_EMITTER_NEE samples (no reference counterpart): every octree leaf whose block is a full cube
- * with a non-zero emittance byte, in pre-order, 4 ints each {x, y, z, level << 25 | block pointer}.  *count receives the
+ * with a non-zero emittance byte and no emittance texture (material flag 2), in pre-order, 4 ints each {x, y, z, level << 25 | block pointer}.  *count receives the
  * number of emitters; at most `cap` are written. */
 int chunky_scene_emitters(chunky_scene* scene, int32_t* out4, int32_t cap, int32_t* count);
 /* getSun(): flags, textureSize, textureLocation, intensity, altitude, azimuth (PackedSun.java:32-41) */
@@ -269,6 +269,10 @@ typedef enum chunky_option {
     CHUNKY_OPT_EMITTERS = 5,        /* int: 1 (default) / 0 = Chunky emittersEnabled false */
     CHUNKY_OPT_BSDF = 6,            /* int: 0 (default) / 1 = specular, metalness, roughness from material word 5 (PackedMaterial.java:69-71) */
     CHUNKY_OPT_EMITTER_NEE = 7,     /* int: 0 (default) / 1 = next-event estimation towards the scene's emitter blocks */
+    /* (The bounce ray that follows an emitter sample keeps the emittance of what it hits unless the emitter list holds it: the
+     * emittance is dropped only when the octree part of the trace won (no entity triangle nearer), the block's model type is 1,
+     * and its material has flag 2 clear and a non-zero emittance byte — chunky_scene_emitters' own condition.  Emissive model
+     * blocks, cubes with an emittance texture and emissive entity triangles are not sampled, so they keep their implicit light.) */
     /* EXTENSION, not the reference's walk: 1 = in the entity-BVH traversal a child whose box lies entirely BEHIND the ray origin
      * (the far end of the slab test is negative) counts as missed.  The reference's quick test (K/primitives.h:30-48, used by
      * K/bvh.h:72-85) has no such exit: it descends into every box the ray's LINE pierces, and about half of its node visits and

@@ -45,6 +45,12 @@ assert HIT_DTYPE.itemsize == 56
 
 COUNTER_NAMES = ("samples", "traces", "steps", "node", "block", "model_hdr", "aabb", "quad", "mat",
                  "texel", "bvh_inner", "leaf_hdr", "tri", "sky", "hits")
+# the extended path's entries (oracle/port.c Counters, behind the access-stream ones): tests/test_ext_census_cpu.py
+EXT_COUNTER_NAMES = (tuple(f"nee_level{i}" for i in range(4)) + tuple(f"nee_face{i}" for i in range(6))
+                     + ("nee_clamp_k", "nee_clamp_face", "nee_rej_cs", "nee_rej_cl", "nee_rej_dist", "nee_gate",
+                        "nee_occluded", "nee_free", "spec_rough0", "spec_rough", "spec_flip",
+                        "sun_rays_auto", "sun_rays_forced", "sun_off_skipped",
+                        "an_none", "an_listed", "an_model", "an_emit_tex", "an_entity"))
 
 
 def _ptr(a: np.ndarray) -> int:
@@ -319,11 +325,13 @@ class PortLib(_Lib):
     def counters(self, enable: Optional[bool] = None, reset: bool = False) -> dict:
         if enable is not None:
             self.lib.port_counters_enable(1 if enable else 0)
-        out = np.zeros(len(COUNTER_NAMES), np.int64)
+        names = COUNTER_NAMES + EXT_COUNTER_NAMES
+        assert self.lib.port_counters_count() == len(names)
+        out = np.zeros(len(names), np.int64)
         self.lib.port_counters_read(_ptr(out))
         if reset:
             self.lib.port_counters_reset()
-        return dict(zip(COUNTER_NAMES, (int(v) for v in out)))
+        return dict(zip(names, (int(v) for v in out)))
 
 
 def algorithmic_bytes(c: dict) -> float:

@@ -74,8 +74,19 @@ static inline void port_libm_sincos(float x, float* s, float* c) { *s = sinf(x);
 typedef struct {
     int64_t samples, traces, steps, node, block, model_hdr, aabb, quad, mat, texel, bvh_inner,
         leaf_hdr, tri, sky, hits;
+    /* the extended path (trace_sample_ext): what tests/test_ext_census_cpu.py demands of its exhibit world */
+    int64_t nee_level[4];  /* emitter samples drawn, by the level of the emitter's leaf (3: level 3 and above) */
+    int64_t nee_face[6];   /* ... and by the face drawn */
+    int64_t nee_clamp_k, nee_clamp_face;          /* the two index clamps (xk or xf rounded up to 1.0) */
+    int64_t nee_rej_cs, nee_rej_cl, nee_rej_dist; /* rejected by cs <= 0, else by cl <= 0, else by dist <= 0.002 */
+    int64_t nee_gate;                             /* stopped by material_sample(...) && emittance > 0 */
+    int64_t nee_occluded, nee_free;               /* emitter shadow rays */
+    int64_t spec_rough0, spec_rough, spec_flip;   /* specular vertices: rough == 0, rough > 0, and of those the rn < 0 flip */
+    int64_t sun_rays_auto, sun_rays_forced, sun_off_skipped; /* sun shadow rays under sun_sampling -1 and 1; vertices where 0 withheld one the flag asks for */
+    int64_t an_none, an_listed, an_model, an_emit_tex, an_entity; /* hits that arrive with after_nee set, by what was hit */
 } Counters;
-#define N_COUNTERS 15
+#define N_COUNTERS ((int)(sizeof(Counters) / sizeof(int64_t)))
+int port_counters_count(void) { return N_COUNTERS; }
 static Counters g_total;
 static int g_count_enabled = 0;
 static _Thread_local Counters* t_ctr = 0;
@@ -109,6 +120,7 @@ typedef struct {
     v3 normal, point;
     v4 color;
     float emittance;
+    int octree_won; /* EXTENSION bookkeeping, read by trace_sample_ext only: the octree part of the last trace hit and no entity BVH hit nearer */
     int spec; /* material word 5 (spec | metal << 8 | rough << 16, PackedMaterial.java:69-71): read by the extensions only */
 } Record;
 
@@ -493,9 +505,13 @@ static int bvh_intersect(const OracleScene* s, const int32_t* bvh, const Path* p
 static int closest_intersect(const OracleScene* s, const Path* p, Record* rec, int draw_depth) {
     COUNT(traces, 1);
     int hit = 0;
-    hit |= octree_intersect(s, p, rec, draw_depth);
-    hit |= bvh_intersect(s, s->world_bvh, p, rec);
-    hit |= bvh_intersect(s, s->actor_bvh, p, rec);
+    const int oct = octree_intersect(s, p, rec, draw_depth);
+    hit |= oct;
+    const int world = bvh_intersect(s, s->world_bvh, p, rec);
+    hit |= world;
+    const int actor = bvh_intersect(s, s->actor_bvh, p, rec);
+    hit |= actor;
+    rec->octree_won = oct && !world && !actor; /* (a BVH reports a hit only for a triangle nearer than the record's distance) */
     if (hit) rec->point = add3(p->origin, scale3(p->direction, rec->distance - OFFSET));
     return hit;
 }
@@ -853,6 +869,11 @@ static v3 trace_sample(const OracleScene* s, const Sun* sun, int seed, int gid, 
  *                 colour^2 x emittance x emitter_scale (what the implicit path adds on hitting it, K/kernel.h:39-43) is
  *                 added with the area-measure weight cos cos / (pi d^2) x 6 N A.  The bounce ray that follows does not count
  *                 an emitter it hits again; the last vertex of a path (whose bounce ray is never traced) samples none.
+ *                 THE RULE for "an emitter it hits again" (hit_is_listed): a hit that arrives with after_nee set keeps its
+ *                 emittance unless it is one the emitter list holds — it is dropped only when the octree part of the trace
+ *                 won (no entity BVH hit nearer), the block's model type is 1, its material has flag 2 clear and a non-zero
+ *                 emittance byte: exactly list_emitters' condition.  Emissive model blocks, cubes with an emittance texture
+ *                 and emissive entity triangles are never sampled by the list, so their implicit hit is their only light.
  * Random draws per vertex, in this order: [1: specular?  only if max(spec, metal) > 0] then specular: [2 if rough > 0];
  * diffuse: [2 sun if on] [4 emitter if on] 2 bounce. */
 typedef struct {
@@ -917,6 +938,15 @@ static v3 cosine_direction(v3 n, float x1, float x2) {
     return V3(ux * tx + vx * ty + n.x * tz, uy * tx + vy * ty + n.y * tz, uz * tx + vz * ty + n.z * tz);
 }
 
+/* THE RULE of the comment block above: is what `rec` hit an emitter the list holds (list_emitters' own condition)? */
+static int hit_is_listed(const OracleScene* s, const Record* rec) {
+    if (!rec->octree_won) return 0;
+    const int block = rec->material;
+    if (s->block_palette[block] != 1) return 0;
+    const int32_t* m = s->material_palette + s->block_palette[block + 1];
+    return !(m[0] & 2) && (m[4] & 0xFF) != 0;
+}
+
 static v3 trace_sample_ext(const OracleScene* s, const Sun* sun, const Ext* x, int seed, int gid) {
     Path p;
     Record rec;
@@ -938,7 +968,16 @@ static v3 trace_sample_ext(const OracleScene* s, const Sun* sun, const Ext* x, i
         const v3 c = V3(rec.color.x, rec.color.y, rec.color.z);
         const v3 thr_d = mul3(base, c);
         const v3 point = rec.point, n = rec.normal;
-        if (x->emitters && !after_nee)
+        /* (the palette reads of hit_is_listed only behind after_nee and a non-zero emittance: a listed emitter has one) */
+        const int listed = after_nee && rec.emittance != 0 && hit_is_listed(s, &rec);
+        if (after_nee) {
+            if (rec.emittance == 0) COUNT(an_none, 1);
+            else if (listed) COUNT(an_listed, 1);
+            else if (!rec.octree_won) COUNT(an_entity, 1);
+            else if (s->block_palette[rec.material] != 1) COUNT(an_model, 1);
+            else COUNT(an_emit_tex, 1);
+        }
+        if (x->emitters && !listed)
             p.color = add3(p.color, mul3(scale3(c, rec.emittance * g_emitter_scale), thr_d)); /* K/kernel.h:39-43 */
         after_nee = 0;
         int specular = 0;
@@ -960,6 +999,10 @@ static v3 trace_sample_ext(const OracleScene* s, const Sun* sun, const Ext* x, i
                 refl = normalize3(add3(scale3(dd, rough), scale3(refl, 1 - rough)));
                 float rn = dot3(refl, n);
                 if (rn < 0) refl = sub3(refl, scale3(n, 2 * rn));
+                COUNT(spec_rough, 1);
+                if (rn < 0) COUNT(spec_flip, 1);
+            } else {
+                COUNT(spec_rough0, 1);
             }
             p.direction = refl;
             p.origin = add3(point, scale3(refl, OFFSET));
@@ -967,9 +1010,11 @@ static v3 trace_sample_ext(const OracleScene* s, const Sun* sun, const Ext* x, i
             p.throughput = thr_d;
             p.origin = point;
             const int sun_on = x->sun_sampling < 0 ? (sun->flags & 1) : x->sun_sampling;
+            if (x->sun_sampling == 0 && (sun->flags & 1)) COUNT(sun_off_skipped, 1);
             if (sun_on) { /* Sun_sampleDirection + shadow trace, K/sky.h:68-93, K/rayTracer.cl:101-106 */
                 Sun on = *sun;
                 on.flags |= 1;
+                if (x->sun_sampling < 0) COUNT(sun_rays_auto, 1); else COUNT(sun_rays_forced, 1);
                 sun_sample_direction(&on, &p, &rec, &state);
                 Record shadow = rec;
                 shadow.point = rec.normal;
@@ -979,11 +1024,13 @@ static v3 trace_sample_ext(const OracleScene* s, const Sun* sun, const Ext* x, i
             if (x->nee && x->emitters && g_n_emitters > 0 && p.ray_depth + 1 < g_max_depth) {
                 const float xk = rt_pcg_float(&state), xf = rt_pcg_float(&state), xu = rt_pcg_float(&state), xv = rt_pcg_float(&state);
                 int k = (int)(xk * (float)g_n_emitters);
-                if (k > g_n_emitters - 1) k = g_n_emitters - 1;
+                if (k > g_n_emitters - 1) { k = g_n_emitters - 1; COUNT(nee_clamp_k, 1); }
                 int face = (int)(xf * 6.0f);
-                if (face > 5) face = 5;
+                if (face > 5) { face = 5; COUNT(nee_clamp_face, 1); }
                 const int32_t* em = g_emitters + 4 * k;
                 const int level = (em[3] >> 25) & 15, block = em[3] & 0x1FFFFFF;
+                COUNT(nee_level[level < 3 ? level : 3], 1);
+                COUNT(nee_face[face], 1);
                 const float size = (float)(1 << level);
                 const float a = xu * size, b = xv * size;
                 const float fa = a - rt_floor(a), fb = b - rt_floor(b);
@@ -1012,13 +1059,23 @@ static v3 trace_sample_ext(const OracleScene* s, const Sun* sun, const Ext* x, i
                         q.direction = dir;
                         Record sh = rec;
                         sh.distance = dist - 0.001f; /* anything nearer than the emitter's face hides it */
-                        if (!closest_intersect(s, &q, &sh, g_draw_depth)) {
+                        const int occluded = closest_intersect(s, &q, &sh, g_draw_depth);
+                        if (occluded) COUNT(nee_occluded, 1); else COUNT(nee_free, 1);
+                        if (!occluded) {
                             const float w = (cs * cl) / (RT_PI_F * d2) * (6.0f * (float)g_n_emitters * (size * size));
                             const v3 ce = V3(er.color.x, er.color.y, er.color.z);
                             const v3 le = mul3(ce, scale3(ce, er.emittance * g_emitter_scale));
                             p.color = add3(p.color, mul3(thr_d, scale3(le, w)));
                         }
+                    } else {
+                        COUNT(nee_gate, 1);
                     }
+                } else if (!(cs > 0)) {
+                    COUNT(nee_rej_cs, 1);
+                } else if (!(cl > 0)) {
+                    COUNT(nee_rej_cl, 1);
+                } else {
+                    COUNT(nee_rej_dist, 1);
                 }
                 after_nee = 1;
             }
