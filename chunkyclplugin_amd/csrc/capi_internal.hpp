@@ -194,6 +194,11 @@ struct chunky_render {
     // allocated (and zeroed) by the first occlusion call.  Record and counter are its own: no other call sees them
     DevBuf occlusion;
     FirstHitPass occlusion_pass{LaunchClock(&free_events)};
+    // chunky_render_light_passes: the SKY, SUN, EMITTERS and ALL images (3 * width * height floats each), then the kernel's claim
+    // counter; allocated (and zeroed) by the first light call.  light_mix holds a mix on its way to the host.  Record and counter
+    // are its own: no other call sees them
+    DevBuf lights, light_mix;
+    FirstHitPass light_pass{LaunchClock(&free_events)};
     // chunky_render_denoise: the filter's workspace (kept between calls) and its timing, apart from the render and AOV launches'
     DevBuf dn_work, dn_out;
     LaunchClock dn_clock{&free_events};  // (a bracket holds all launches of one call: their number is its weight)

@@ -1,0 +1,78 @@
+// capi_lights.hip — light groups: the sky's, the sun's and the emitters' share of the beauty image (lights.hip).
+#include "capi_internal.hpp"
+
+constexpr int kLightImages = 4;  // CHUNKY_LIGHT_SKY, _SUN, _EMITTERS, _ALL
+static_assert(CHUNKY_LIGHT_SKY == 0 && CHUNKY_LIGHT_SUN == 1 && CHUNKY_LIGHT_EMITTERS == 2 && CHUNKY_LIGHT_ALL == 3, "the images lie in this order");
+
+static float* light_image(const chunky_render* r, int which) { return (float*)((char*)r->lights.p + (size_t)which * aov_image_bytes(r)); }
+
+// the four images, allocated, zeroed, by the first chunky_render_light_passes
+static int lights_ensure(chunky_render* r) {
+    if (r->lights.p) return CHUNKY_OK;
+    const size_t bytes = kLightImages * aov_image_bytes(r) + 256;  // the images, the claim counter
+    HIP_TRY(r->lights.alloc(bytes));
+    HIP_TRY(hipMemsetAsync(r->lights.p, 0, bytes, r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+// n passes over the pixel slots of shard T (a single-device target: its own share; member 0 of a group: the caller's share)
+static int light_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n, int first_buffer_spp) {
+    LOCK_RENDER(r);
+    if (!r->have_camera) return fail(CHUNKY_E_STATE, "light_passes before set_camera");
+    if (opts_extended(r->opts))  // they change what the beauty image is, and this pass walks the reference's path only
+        return fail(CHUNKY_E_STATE, "light_passes: not with CHUNKY_OPT_SUN_SAMPLING, _EMITTERS, _BSDF or _EMITTER_NEE away from their defaults");
+    if (int rc = lights_ensure(r)) return rc;
+    r->light_pass.last_launches = 0;
+    if (n == 0 || T.n_local <= 0) return CHUNKY_OK;
+    SceneView S;
+    if (int rc = scene_view(r->scene, &S)) return rc;
+    S.bvh_cull = r->opts.bvh_cull;
+    float* images[kLightImages];
+    for (int g = 0; g < kLightImages; g++) images[g] = light_image(r, g);
+    int* counter = (int*)light_image(r, kLightImages);
+    return first_hit_launches(r, r->light_pass, seeds, n, first_buffer_spp, [&](const PassSeeds& ps) {  // (each continues the running means)
+        HIP_TRY(launch_lights(r->kernel_variant, S, r->cam, r->opts, T, ps, images, counter, r->ctx->stream, &r->light_pass.choice));
+        return (int)CHUNKY_OK;
+    });
+}
+
+extern "C" int chunky_render_light_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp) {
+    if (n < 0 || (n > 0 && !seeds) || first_buffer_spp < 0) return fail(CHUNKY_E_INVALID, "light_passes: bad arguments");
+    return on_first_member("light_passes", r, [&](chunky_render* m, const ShardView& t) { return light_passes(m, t, seeds, n, first_buffer_spp); });
+}
+
+extern "C" int chunky_render_light_read(chunky_render* r, int which, float* out, int64_t n) {
+    if (r && !r->parts.empty()) return chunky_render_light_read(r->parts[0], which, out, n);
+    LOCK_RENDER(r);
+    if (which < CHUNKY_LIGHT_SKY || which > CHUNKY_LIGHT_ALL) return fail(CHUNKY_E_INVALID, "light_read: unknown image %d", which);
+    const float* src = r->lights.p ? light_image(r, which) : nullptr;  // null before any pass
+    return read_floats("light_read", r, src, out, n, (int64_t)r->width * r->height * 3);
+}
+
+extern "C" int chunky_render_light_mix(chunky_render* r, const float w[3], float* out, int64_t n) {
+    if (r && !r->parts.empty()) return chunky_render_light_mix(r->parts[0], w, out, n);
+    LOCK_RENDER(r);
+    if (!w || !std::isfinite(w[0]) || !std::isfinite(w[1]) || !std::isfinite(w[2])) return fail(CHUNKY_E_INVALID, "light_mix: three finite weights are needed");
+    const int64_t need = (int64_t)r->width * r->height * 3;
+    if (!out || n != need) return fail(CHUNKY_E_INVALID, "light_mix: need %lld floats, got %lld", (long long)need, (long long)n);
+    if (!r->lights.p) return fail(CHUNKY_E_STATE, "light_mix before any light pass");
+    if (!r->light_mix.p) HIP_TRY(r->light_mix.alloc(aov_image_bytes(r)));
+    HIP_TRY(launch_light_mix(light_image(r, CHUNKY_LIGHT_SKY), light_image(r, CHUNKY_LIGHT_SUN), light_image(r, CHUNKY_LIGHT_EMITTERS), w, (float*)r->light_mix.p, need,
+                             r->ctx->stream));
+    return read_floats("light_mix", r, r->light_mix.p, out, n, need);
+}
+
+extern "C" int chunky_render_light_reset(chunky_render* r) {
+    if (r && !r->parts.empty()) return chunky_render_light_reset(r->parts[0]);
+    LOCK_RENDER(r);
+    if (r->lights.p) HIP_TRY(hipMemsetAsync(r->lights.p, 0, kLightImages * aov_image_bytes(r), r->ctx->stream));
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_light_kernel_time(chunky_render* r, float* total_ms, int* launches) {
+    return first_hit_kernel_time(r, &chunky_render::light_pass, total_ms, launches);
+}
+
+extern "C" int chunky_render_light_kernel_info(chunky_render* r, int32_t out4[4]) {
+    return first_hit_kernel_info("light_kernel_info", r, &chunky_render::light_pass, out4);
+}

@@ -1,5 +1,5 @@
 // kernels.hpp — host-visible launch interface of the kernel translation units (render_pool.hip, render_fallback.hip,
-// aux_kernels.hip, filter.hip, aov.hip, occlusion.hip, matte.hip, denoise.hip, adaptive.hip).
+// aux_kernels.hip, filter.hip, aov.hip, occlusion.hip, lights.hip, matte.hip, denoise.hip, adaptive.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -130,6 +130,13 @@ hipError_t launch_aov_ex(int variant, const SceneView& S, const CameraView& C, c
 // floats each, folded in place over the pixel slots of shard T; ao_distance > 0 (+inf allowed); `counter` as launch_aov's.
 hipError_t launch_occlusion(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
                             float* ao, float* sun, float ao_distance, int* counter, hipStream_t stream, AovChoice* chosen);
+// Light-group passes (lights.hip): P.n <= kMaxPassesPerLaunch; images[CHUNKY_LIGHT_SKY .. CHUNKY_LIGHT_ALL] are
+// 3 * width * height floats each, folded in place over the pixel slots of shard T; O.max_depth and O.emitter_scale are the path's;
+// `counter` as launch_aov's.
+hipError_t launch_lights(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
+                         float* const images[4], int* counter, hipStream_t stream, AovChoice* chosen);
+// out[i] = (w[0] * sky[i] + w[1] * sun[i]) + w[2] * emitters[i] for n floats on the device, without fma
+hipError_t launch_light_mix(const float* sky, const float* sun, const float* emitters, const float w[3], float* out, long long n, hipStream_t stream);
 // ID-matte passes (matte.hip; specification: matte_spec.h): P.n <= kMaxPassesPerLaunch; `planes` is 13 * width * height ints (six planes of
 // ids, six of counts, `other`), updated in place over the pixel slots of shard T; `counter` as launch_aov's.  The choice record is the AOV's.
 hipError_t launch_matte(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,

@@ -142,7 +142,7 @@ RenderPlan plan_render(int variant, const SceneFacts& F, const RenderOpts& O, in
 // the message of check_extended_opts for a refusal, with `who` in front
 const char* ext_refusal_text(ExtRefusal r);
 
-// The lookup form of the first-hit passes (first_hit_pass.hpp, occlusion.hip): the one render_pool picks for the scene, so that a
+// The lookup form of the first-hit passes (first_hit_pass.hpp, occlusion.hip, lights.hip): the one render_pool picks for the scene, so that a
 // first-hit pass and a render pass of a view read the octree the same way
 struct FirstHitPlan {
     int tree;
@@ -211,7 +211,7 @@ FirstHitPlan plan_first_hit(int variant, const SceneFacts& F);
     X(0, 16, false) X(-1, 16, false) X(0, 16, true) X(-1, 16, true)                                                                    \
     X(0, 32, false) X(-1, 32, false)
 #define CHUNKY_LANES_INSTANCES(X) X(0) X(-1)
-// X(TREE, BVH) of the first-hit kernels (first_hit_pass.hpp first_hit_kernel, occlusion.hip occlusion_kernel)
+// X(TREE, BVH) of the first-hit kernels (first_hit_pass.hpp first_hit_kernel, occlusion.hip occlusion_kernel, lights.hip light_kernel)
 #define CHUNKY_FIRST_HIT_INSTANCES(X)                                                                                                  \
     X(0, true) X(17, true) X(18, true) X(-1, true)                                                                                     \
     X(0, false) X(16, false) X(17, false) X(18, false) X(19, false) X(-1, false)

@@ -18,8 +18,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("CHUNKY_HIP_LIB") or os.path.join(PKG_DIR, "libchunky_hip.so")  # override: tuning builds (tools/variants.sh)
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
-SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "matte.hip", "denoise.hip", "adaptive.hip",
-           "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_occlusion.hip", "capi_matte.hip", "capi_adaptive.hip", "capi_denoise.hip",
+SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "lights.hip", "matte.hip", "denoise.hip", "adaptive.hip",
+           "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_occlusion.hip", "capi_lights.hip", "capi_matte.hip", "capi_adaptive.hip", "capi_denoise.hip",
            "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp",
            "scene_records.cpp", "widetree.cpp", "launch_plan.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
@@ -38,6 +38,7 @@ AOV_ALBEDO, AOV_NORMAL = 0, 1  # chunky_render_aov_read
 AOV_ALPHA, AOV_DEPTH, AOV_POSITION, AOV_EMITTANCE, AOV_BLOCK = 2, 3, 4, 5, 6  # chunky_render_aov_read_ex (with the two above)
 AOV_WORDS = {AOV_ALBEDO: 3, AOV_NORMAL: 3, AOV_ALPHA: 1, AOV_DEPTH: 1, AOV_POSITION: 3, AOV_EMITTANCE: 1, AOV_BLOCK: 1}  # words per pixel
 AOV_AO, AOV_SUN = 7, 8  # chunky_render_occlusion_read (a float per pixel each)
+LIGHT_SKY, LIGHT_SUN, LIGHT_EMITTERS, LIGHT_ALL = range(4)  # chunky_render_light_read (3 floats per pixel each)
 MATTE_SLOTS = 6  # CHUNKY_MATTE_*: slots per pixel, the ids of a miss and of the two entity BVHs, the id an empty rank reports
 MATTE_SKY, MATTE_WORLD_ENTITY, MATTE_ACTOR_ENTITY, MATTE_EMPTY = -1, -2, -3, -2 ** 31
 DENOISE_DEMODULATE = 1  # chunky_denoise_params.flags
@@ -237,6 +238,12 @@ def lib() -> C.CDLL:
             "chunky_render_occlusion_reset": [vp],
             "chunky_render_occlusion_kernel_time": [vp, C.POINTER(f32), C.POINTER(C.c_int)],
             "chunky_render_occlusion_kernel_info": [vp, vp],
+            "chunky_render_light_passes": [vp, vp, C.c_int, C.c_int],
+            "chunky_render_light_read": [vp, C.c_int, vp, i64],
+            "chunky_render_light_mix": [vp, vp, vp, i64],
+            "chunky_render_light_reset": [vp],
+            "chunky_render_light_kernel_time": [vp, C.POINTER(f32), C.POINTER(C.c_int)],
+            "chunky_render_light_kernel_info": [vp, vp],
             "chunky_render_matte_passes": [vp, vp, C.c_int],
             "chunky_render_matte_reset": [vp],
             "chunky_render_matte_read": [vp, vp, vp, vp, i64, C.POINTER(i32)],

@@ -427,6 +427,45 @@ class HipPathTracingRenderer:
         check(native.lib().chunky_render_occlusion_kernel_info(self._h, ptr(out)))
         return {"tree": int(out[0]), "bvh": bool(out[1]), "blocks": int(out[2]), "launches": int(out[3])}
 
+    # --- light groups: the sky's, the sun's and the emitters' share of the beauty image (chunky_render_light_*) ------
+    def render_lights(self, seeds, first_buffer_spp: int = 0, sync: bool = True) -> None:
+        """Light-group passes: pass k walks the path of the render pass with seeds[k] once and folds its radiance into four images —
+        the sky's, the sun's and the emitters' share, and their sum as the beauty pass adds it."""
+        s = np.ascontiguousarray(seeds, np.int32)
+        check(native.lib().chunky_render_light_passes(self._h, ptr(s), s.size, first_buffer_spp))
+        if sync:
+            self.sync()
+
+    def read_light(self, which: int) -> np.ndarray:
+        """One of the four images (native.LIGHT_SKY, _SUN, _EMITTERS, _ALL) as a (height, width, 3) float32 array."""
+        out = np.empty((self.height, self.width, 3), np.float32)
+        check(native.lib().chunky_render_light_read(self._h, int(which), ptr(out), out.size))
+        return out
+
+    def mix_lights(self, weights) -> np.ndarray:
+        """(w0 * SKY + w1 * SUN) + w2 * EMITTERS, mixed on the device, as a (height, width, 3) float32 array."""
+        w = np.ascontiguousarray(weights, np.float32)
+        if w.shape != (3,):
+            raise ValueError("mix_lights takes three weights: sky, sun, emitters")
+        out = np.empty((self.height, self.width, 3), np.float32)
+        check(native.lib().chunky_render_light_mix(self._h, ptr(w), ptr(out), out.size))
+        return out
+
+    def reset_lights(self) -> None:
+        check(native.lib().chunky_render_light_reset(self._h))
+
+    def lights_time(self):
+        """(milliseconds, launches) of the light-group kernel since the last call."""
+        ms, n = C.c_float(), C.c_int()
+        check(native.lib().chunky_render_light_kernel_time(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def lights_info(self) -> dict:
+        """The instantiation the last light-group launch ran: tree form, entity-BVH walk, workgroups, launches of the last call."""
+        out = np.zeros(4, np.int32)
+        check(native.lib().chunky_render_light_kernel_info(self._h, ptr(out)))
+        return {"tree": int(out[0]), "bvh": bool(out[1]), "blocks": int(out[2]), "launches": int(out[3])}
+
     # --- antialiased ID mattes (chunky_render_matte_*) ------------------------------------------------
     def render_matte(self, seeds, sync: bool = True) -> None:
         """Matte passes: pass k traces the first ray of the render pass with seeds[k] and counts the id it hits, per pixel."""

@@ -490,6 +490,57 @@ int chunky_render_occlusion_kernel_time(chunky_render* r, float* total_ms, int* 
 /* The instantiation the most recent occlusion launch ran: the four words of chunky_render_aov_kernel_info. */
 int chunky_render_occlusion_kernel_info(chunky_render* r, int32_t out4[4]);
 
+/* ---- light groups: the sky's, the sun's and the emitters' share of the beauty image as images of their own, so that a compositor
+ * rebalances the three ("torches warmer, sun down a stop") with a weighted sum of finished images instead of a new render.  The
+ * sample of pass k at pixel gid is the reference's whole sample (K/rayTracer.cl:55-107): RNG state seeds[k] + gid,
+ * Random_nextState, the camera ray of the target's camera (with its aperture or lens), then the traces, the sun rays (bit 0 of the
+ * scene's PackedSun flags) and the bounces up to CHUNKY_OPT_MAX_DEPTH, each trace with the target's draw depth and
+ * CHUNKY_OPT_BVH_CULL_BEHIND.  Its radiance is a sum of terms linear in three scalars, and each image evaluates them with a triple
+ * of its own:
+ *
+ *   image                   sky intensity   sun intensity (PackedSun word 3)   emitter scale (CHUNKY_OPT_EMITTER_SCALE)
+ *   CHUNKY_LIGHT_SKY        the scene's     0                                  0
+ *   CHUNKY_LIGHT_SUN        0               the scene's                        0
+ *   CHUNKY_LIGHT_EMITTERS   0               0                                  the target's
+ *   CHUNKY_LIGHT_ALL        the scene's     the scene's                        the target's
+ *
+ * A group image IS the reference's image under those scalars, bit for bit; the path itself never depends on them and is walked
+ * once.  Per group, in the reference's operation order: at a hit, radiance += (c * (emittance * scale)) * throughput; at a miss or
+ * an unshadowed sun ray, c = blend * sky (blend: the weighted sum of the four sky texels), then c += texel * sun where the direction
+ * is in the sun's disc, then radiance += (c * throughput) * e.  CHUNKY_LIGHT_ALL is the beauty sample itself: the image
+ * chunky_render_passes folds for the same seeds.  The three groups sum to it to rounding (at one pass, within
+ * 4 * (2 * max depth + 3) * 2^-24 relative per float), and a doubled scalar doubles its group bit for bit.  With the sun flag off
+ * there is no sun ray and no RNG draw for it, and CHUNKY_LIGHT_SUN is all zero.
+ * Each image (3 floats per pixel, interleaved like the beauty image) is folded with (img * spp + v) / (spp + 1) in float, in pass
+ * order, spp = first_buffer_spp + k.  The four images are allocated, zeroed, by the first chunky_render_light_passes on a target.
+ * Render, AOV, matte, occlusion, denoise and adaptive calls never see them, and these calls never touch theirs.  A set shard limits
+ * the passes to the rank's pixels; the others stay 0.  On a group's render target member 0 renders the caller's whole share, as for
+ * the AOV.  A scene update between two calls (chunky_scene_set_sky, chunky_scene_set_sun, ...) takes effect in the next one.
+ * The experimental light-transport options (CHUNKY_OPT_SUN_SAMPLING, CHUNKY_OPT_EMITTERS, CHUNKY_OPT_BSDF, CHUNKY_OPT_EMITTER_NEE)
+ * change what the beauty image is; this pass does not implement them and refuses to run with any of them away from its default.
+ * The Java binding does not reach these calls. */
+#define CHUNKY_LIGHT_SKY 0
+#define CHUNKY_LIGHT_SUN 1
+#define CHUNKY_LIGHT_EMITTERS 2
+#define CHUNKY_LIGHT_ALL 3
+/* Enqueue n passes over the four images (asynchronous; cut into launches of at most 256 passes, which changes no bit; n = 0 is
+ * legal).  CHUNKY_E_STATE before chunky_render_set_camera and with an experimental light-transport option set. */
+int chunky_render_light_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp);
+/* Blocking read-back of one image (which = CHUNKY_LIGHT_SKY .. CHUNKY_LIGHT_ALL), 3*width*height floats.  CHUNKY_E_STATE before the
+ * first chunky_render_light_passes; CHUNKY_E_INVALID for an unknown image or a wrong count. */
+int chunky_render_light_read(chunky_render* r, int which, float* out, int64_t n_floats);
+/* A rebalanced image on the device, read back: out = (w[0] * SKY + w[1] * SUN) + w[2] * EMITTERS per float, in that order, each
+ * operation rounded to float (no fma); 3*width*height floats, ready for chunky_filter_frame once widened to double.
+ * CHUNKY_E_INVALID for NULL or non-finite weights, a NULL buffer or a wrong count; CHUNKY_E_STATE before the first
+ * chunky_render_light_passes (there is nothing to mix). */
+int chunky_render_light_mix(chunky_render* r, const float w[3], float* out, int64_t n_floats);
+/* Zero the four images. */
+int chunky_render_light_reset(chunky_render* r);
+/* Device time of the light-group launches enqueued since the last call (as chunky_render_aov_kernel_time; no other timer sees them). */
+int chunky_render_light_kernel_time(chunky_render* r, float* total_ms, int* launches);
+/* The instantiation the most recent light-group launch ran: the four words of chunky_render_aov_kernel_info. */
+int chunky_render_light_kernel_info(chunky_render* r, int32_t out4[4]);
+
 /* ---- antialiased ID mattes (no reference counterpart; the idea of Cryptomatte): per pixel a short list of (id, the number of passes
  * that saw it), counted over the same camera rays the beauty passes use, so that a mask for any set of ids is a sum of shares and
  * lines up with the antialiased image.  The exact arithmetic is chunkyclplugin_amd/csrc/matte_spec.h, which the kernels and the

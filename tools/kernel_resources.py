@@ -2,7 +2,7 @@
 """tools/kernel_resources.py [out.json] — registers, spills and occupancy of every render_pool / fold_kernel instantiation, of the
 denoise kernels, of the adaptive-sampling kernels, of the first-hit pass kernels (first_hit_kernel with the AOV, AOV-ex and ID-matte folds) and of the matte read-outs as hipcc reports them for gfx950
 (-Rpass-analysis=kernel-resource-usage on csrc/render_pool.hip, csrc/render_pool_bvh.hip (the entity-BVH instantiations),
-csrc/denoise.hip, csrc/adaptive.hip, csrc/aov.hip, csrc/matte.hip and csrc/occlusion.hip (occlusion_kernel) with the library's flags).  CPU only."""
+csrc/denoise.hip, csrc/adaptive.hip, csrc/aov.hip, csrc/matte.hip, csrc/occlusion.hip (occlusion_kernel) and csrc/lights.hip (light_kernel, light_mix_kernel) with the library's flags).  CPU only."""
 import json
 import os
 import re
@@ -15,7 +15,7 @@ from chunkyclplugin_amd import native  # noqa: E402
 
 flags = [f for f in native.HIPCC_FLAGS if f not in ("-shared",)]
 err = ""
-for src in ("render_pool.hip", "render_pool_bvh.hip", "denoise.hip", "adaptive.hip", "aov.hip", "matte.hip", "occlusion.hip"):
+for src in ("render_pool.hip", "render_pool_bvh.hip", "denoise.hip", "adaptive.hip", "aov.hip", "matte.hip", "occlusion.hip", "lights.hip"):
     cmd = ["hipcc", *flags, "-x", "hip", "-c", os.path.join(native.CSRC, src), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
     err += subprocess.run(cmd, capture_output=True, text=True).stderr
 out, cur = {}, None
