@@ -52,10 +52,18 @@ struct AovFold {
     DEV void store(int, int) { store3(pa, ma), store3(pn, mn); }
 };
 
+// (aov_biome.hip compiles this file with CHUNKY_BIOME_TINT: the same folds over kernels that tint by position, under names of their own)
+#if CHUNKY_BIOME_TINT
+hipError_t launch_aov_biome(int variant, const SceneView& S, const BiomeMap& B, const CameraView& C, const RenderOpts& O, const ShardView& T,
+                            const PassSeeds& P, float* albedo, float* normal, int* counter, hipStream_t stream, AovChoice* chosen) {
+    return launch_first_hit<AovFold>(variant, S, C, O, T, P, AovFold::Out{albedo, normal}, counter, stream, chosen, &B);
+}
+#else
 hipError_t launch_aov(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
                       float* albedo, float* normal, int* counter, hipStream_t stream, AovChoice* chosen) {
     return launch_first_hit<AovFold>(variant, S, C, O, T, P, AovFold::Out{albedo, normal}, counter, stream, chosen);
 }
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // chunky_render_aov_passes_ex: the same sample, and five more images of its first hit folded beside albedo and
@@ -122,9 +130,16 @@ struct AovExFold {
     }
 };
 
+#if CHUNKY_BIOME_TINT
+hipError_t launch_aov_ex_biome(int variant, const SceneView& S, const BiomeMap& B, const CameraView& C, const RenderOpts& O, const ShardView& T,
+                               const PassSeeds& P, const AovExImages& I, int* counter, hipStream_t stream, AovChoice* chosen) {
+    return launch_first_hit<AovExFold>(variant, S, C, O, T, P, I, counter, stream, chosen, &B);
+}
+#else
 hipError_t launch_aov_ex(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
                          const AovExImages& I, int* counter, hipStream_t stream, AovChoice* chosen) {
     return launch_first_hit<AovExFold>(variant, S, C, O, T, P, I, counter, stream, chosen);
 }
+#endif
 
 }  // namespace chunky

@@ -5,67 +5,10 @@
 #include <hip/hip_runtime.h>
 
 #include "path_state.hpp"
+#include "lane_kernels.hpp"  // trace_records_kernel, preview_lanes
 #include "pool_walk.hpp"
 
 namespace chunky {
-
-template <int TREE>
-__global__ void __launch_bounds__(256) trace_records_kernel(SceneView S, CameraView C, RenderOpts O, int seed,
-                                                             const int* __restrict__ gids, int n,
-                                                             HitRecord* __restrict__ out, int* __restrict__ counts,
-                                                             float* __restrict__ radiance) {
-    extern __shared__ int lds[];
-    LdsStack stack{lds + threadIdx.x, (int)blockDim.x};
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    HitRecord local[kMaxTraces];
-    int cnt = 0;
-    f3 c = sample_path<true, TREE>(S, C, O, seed, gids[i], stack, local, &cnt);
-    for (int k = 0; k < cnt; k++) out[(size_t)i * kMaxTraces + k] = local[k];
-    counts[i] = cnt;
-    radiance[3 * i] = c.x;
-    radiance[3 * i + 1] = c.y;
-    radiance[3 * i + 2] = c.z;
-}
-
-// preview — K/rayTracer.cl:115-217
-template <int TREE>
-__global__ void __launch_bounds__(256) preview_lanes(SceneView S, CameraView C, RenderOpts O, int* __restrict__ argb) {
-    extern __shared__ int lds[];
-    LdsStack stack{lds + threadIdx.x, (int)blockDim.x};
-    int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    int W = C.width, H = C.height;
-    if (gid >= W * H) return;
-    int px = gid % W, py = gid / W;
-    if ((px == W / 2 && (py >= H / 2 - 5 && py <= H / 2 + 5)) || (py == H / 2 && (px >= W / 2 - 5 && px <= W / 2 + 5))) {
-        argb[gid] = (int)0xFFFFFFFFu;
-        return;
-    }
-    unsigned rng = 0;
-    rt_pcg_next(&rng);
-    const RayOD pr = primary_ray_any(C, 0u, gid, rng, true);  // a projected camera: the rays of seed 0
-    const f3 o = pr.o, d = pr.d;
-    Hit h;
-    h.distance = rt_inf();
-    h.material = 0;
-    h.normal = mk3(0, 0, 0);
-    h.color = f4{0, 0, 0, 0};
-    h.emittance = 0;
-    f3 point;
-    f4 c;
-    if (closest_hit<TREE>(S, o, d, O.draw_depth, h, point, stack)) {
-        float shading = dot(h.normal, mk3(0.25f, 0.866f, 0.433f));
-        shading = rt_fmax(0.3f, shading);
-        c = f4{h.color.x * shading, h.color.y * shading, h.color.z * shading, 0};
-    } else {
-        c = sky_color(S, d);
-        sun_disc(S, d, c);
-    }
-    int r = (int)rt_floor(rt_clamp(rt_sqrt(c.x) * 255.0f, 0.0f, 255.0f));
-    int g = (int)rt_floor(rt_clamp(rt_sqrt(c.y) * 255.0f, 0.0f, 255.0f));
-    int b = (int)rt_floor(rt_clamp(rt_sqrt(c.z) * 255.0f, 0.0f, 255.0f));
-    argb[gid] = (int)(0xFF000000u | ((unsigned)r << 16) | ((unsigned)g << 8) | (unsigned)b);
-}
 
 constexpr int kSweepFirst = 40, kSweepRecord = 60;
 

@@ -21,6 +21,7 @@ static int adaptive_ensure(chunky_render* r) {
 static int adaptive_state(const char* who, chunky_render* r, SceneView* S) {
     if (r->shard.world > 1) return fail(CHUNKY_E_STATE, "%s: this target holds rank %d of %d of the image, not all of it", who, r->shard.rank, r->shard.world);
     if (!r->have_camera) return fail(CHUNKY_E_STATE, "%s before set_camera", who);
+    if (int rc = refuse_biome(who, r)) return rc;  // the statistics fold runs on the kernels that do not tint by position
     if (int rc = scene_view(r->scene, S, r->opts.nee != 0)) return rc;
     S->bvh_cull = r->opts.bvh_cull;
     const RenderPlan plan = render_plan(r, *S);

@@ -46,8 +46,12 @@ static int aov_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n
         images.emittance = exf + kAovExOffset[CHUNKY_AOV_EMITTANCE] * plane;
         images.block = (int*)exf + kAovExOffset[CHUNKY_AOV_BLOCK] * plane;
     }
+    BiomeMap biome;
+    const bool tinted = biome_map(r, &biome);  // the albedo is the beauty pass's: tinted by position where that is (aov_biome.hip)
     return first_hit_launches(r, r->aov_pass, seeds, n, first_buffer_spp, [&](const PassSeeds& ps) {  // (each continues the running mean)
-        if (ex) HIP_TRY(launch_aov_ex(r->kernel_variant, S, r->cam, r->opts, T, ps, images, counter, r->ctx->stream, &r->aov_pass.choice));
+        if (tinted && ex) HIP_TRY(launch_aov_ex_biome(r->kernel_variant, S, biome, r->cam, r->opts, T, ps, images, counter, r->ctx->stream, &r->aov_pass.choice));
+        else if (tinted) HIP_TRY(launch_aov_biome(r->kernel_variant, S, biome, r->cam, r->opts, T, ps, images.albedo, images.normal, counter, r->ctx->stream, &r->aov_pass.choice));
+        else if (ex) HIP_TRY(launch_aov_ex(r->kernel_variant, S, r->cam, r->opts, T, ps, images, counter, r->ctx->stream, &r->aov_pass.choice));
         else HIP_TRY(launch_aov(r->kernel_variant, S, r->cam, r->opts, T, ps, images.albedo, images.normal, counter, r->ctx->stream, &r->aov_pass.choice));
         return (int)CHUNKY_OK;
     });

@@ -108,6 +108,9 @@ struct chunky_scene {
     bool have_sun = false, world_empty = true, actor_empty = true;
     bool have_world = false, have_actor = false;
     int world_height = 0, actor_height = 0;  // inner-node levels: bounds the to-visit stack (K/bvh.h:38 uses 64)
+    // chunky_scene_set_biome_tints: three words per cell of a rectangle of the cell grid (rt_device.hpp BiomeMap); no map: biome.p == nullptr
+    DevBuf biome;
+    int biome_x0 = 0, biome_z0 = 0, biome_size_x = 0, biome_size_z = 0;
     int refs = 1;  // owner + render targets
     std::vector<chunky_scene*> replicas;  // on a group: the scene's copy on every member (this object holds no data)
 };
@@ -152,6 +155,7 @@ struct chunky_render {
     DevBuf rays;
     RenderOpts opts{256, 5, 13.0f, -1, 1, 0, 0};
     int kernel_variant = 0;
+    int biome_tint = 1;  // CHUNKY_OPT_BIOME_TINT: 0 = this target ignores the scene's biome map
     ShardView shard{0, 1, 256, 0};
     DevBuf own_fb, work_counter;
     DevBuf staging;  // render_pool: one launch's samples, [tile of 256 slots][pass][slot][3] floats
@@ -304,6 +308,8 @@ int scene_view(chunky_scene* s, SceneView* v, bool want_emitters = false);
 int launch_pass_cap(const ShardView& T, int width, int height, size_t budget, int most);  // capi_render.hip
 RenderPlan render_plan(const chunky_render* r, const SceneView& S);                      // what plan_render decides for r's passes over S
 int check_extended_opts(const char* who, const RenderPlan& plan);
+bool biome_map(const chunky_render* r, BiomeMap* B);  // r tints by position: its scene has a biome map and CHUNKY_OPT_BIOME_TINT is 1 (then *B is the map)
+int refuse_biome(const char* who, const chunky_render* r);  // CHUNKY_E_STATE for a call that does not tint by position while r does
 int read_floats(const char* who, chunky_render* r, const void* src, void* out, int64_t n, int64_t need);
 int first_hit_kernel_time(chunky_render* r, FirstHitPass chunky_render::*pass, float* total_ms, int* launches);  // capi_aov.hip
 int first_hit_kernel_info(const char* who, chunky_render* r, FirstHitPass chunky_render::*pass, int32_t out4[4]);

@@ -21,6 +21,7 @@ static int light_passes(chunky_render* r, ShardView T, const int32_t* seeds, int
     if (!r->have_camera) return fail(CHUNKY_E_STATE, "light_passes before set_camera");
     if (opts_extended(r->opts))  // they change what the beauty image is, and this pass walks the reference's path only
         return fail(CHUNKY_E_STATE, "light_passes: not with CHUNKY_OPT_SUN_SAMPLING, _EMITTERS, _BSDF or _EMITTER_NEE away from their defaults");
+    if (int rc = refuse_biome("light_passes", r)) return rc;  // (before anything is allocated)
     if (int rc = lights_ensure(r)) return rc;
     r->light_pass.last_launches = 0;
     if (n == 0 || T.n_local <= 0) return CHUNKY_OK;

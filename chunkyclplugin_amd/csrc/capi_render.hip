@@ -185,6 +185,10 @@ extern "C" int chunky_render_set_option(chunky_render* r, int option, int32_t va
             if (value != 0 && value != 1) return fail(CHUNKY_E_INVALID, "BVH cull: 0 or 1");
             r->opts.bvh_cull = value;
             break;
+        case CHUNKY_OPT_BIOME_TINT:
+            if (value != 0 && value != 1) return fail(CHUNKY_E_INVALID, "biome tint: 0 or 1");
+            r->biome_tint = value;
+            break;
         default: return fail(CHUNKY_E_INVALID, "unknown option %d", option);
     }
     r->ad_resumable = false;  // (an option was set: a refused call ends nothing)
@@ -317,6 +321,19 @@ int check_extended_opts(const char* who, const RenderPlan& plan) {
     return fail(CHUNKY_E_STATE, "%s: %s", who, ext_refusal_text(plan.ext_refusal));
 }
 
+// Biome tints (chunky_scene_set_biome_tints): does r tint by position, and with which map
+bool biome_map(const chunky_render* r, BiomeMap* B) {
+    const chunky_scene* s = r->scene;
+    if (!r->biome_tint || !s->biome.p) return false;
+    if (B) *B = BiomeMap{(const int*)s->biome.p, s->biome_x0, s->biome_z0, s->biome_size_x, s->biome_size_z};
+    return true;
+}
+// A call whose images hold colour and whose kernels do not tint by position refuses a target that does: it never renders untinted
+int refuse_biome(const char* who, const chunky_render* r) {
+    if (!biome_map(r, nullptr)) return CHUNKY_OK;
+    return fail(CHUNKY_E_STATE, "%s: not with a biome map on the scene (chunky_scene_set_biome_tints); set CHUNKY_OPT_BIOME_TINT to 0 or remove the map", who);
+}
+
 // a device-to-host read-back of exactly `need` 4-byte values on r's stream; src == nullptr: nothing has been rendered into it yet
 int read_floats(const char* who, chunky_render* r, const void* src, void* out, int64_t n, int64_t need) {
     if (!out || n != need) return fail(CHUNKY_E_INVALID, "%s: need %lld floats, got %lld", who, (long long)need, (long long)n);
@@ -334,8 +351,17 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
     SceneView S;
     if (int rc = scene_view(r->scene, &S, r->opts.nee != 0)) return rc;
     S.bvh_cull = r->opts.bvh_cull;
-    const RenderPlan plan = render_plan(r, S);
+    RenderPlan plan = render_plan(r, S);
     if (int rc = check_extended_opts("render_passes", plan)) return rc;
+    BiomeMap biome;
+    const bool tinted = biome_map(r, &biome);
+    if (tinted) {  // the kernels that tint by position (launch_plan.hpp plan_biome), or a refusal that says why: never an untinted image
+        RenderPlan asked = plan;
+        asked.status = PlanStatus::ok;  // (a block shard's pixel list is made below; what a launch cannot carry is refused there)
+        const BiomePlan b = plan_biome(asked);
+        if (b.refusal != BiomeRefusal::none) return fail(CHUNKY_E_STATE, "render_passes: %s", biome_refusal_text(b.refusal));
+        plan.family = b.plan.family;  // (needs_list and most are the fallback families' either way)
+    }
     r->ad_resumable = false;  // the call is accepted: it writes the framebuffer (chunky_render_run / _run_ex end it here and in chunky_render_reset)
     if (r->clock.full())
         if (int rc = r->clock.collect()) return rc;
@@ -413,8 +439,12 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
             seeds_dev = (const int*)r->seed_buf.p;
         }
         if (int rc = r->clock.open(r->ctx->stream)) return rc;
-        HIP_TRY(launch_render(r->kernel_variant, S, r->cam, r->opts, r->shard, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream,
-                              &r->last_choice, (float*)r->staging.p, seeds_dev));
+        if (tinted)
+            HIP_TRY(launch_render_biome(r->kernel_variant, S, biome, r->cam, r->opts, r->shard, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream,
+                                        &r->last_choice, (float*)r->staging.p, seeds_dev));
+        else
+            HIP_TRY(launch_render(r->kernel_variant, S, r->cam, r->opts, r->shard, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream,
+                                  &r->last_choice, (float*)r->staging.p, seeds_dev));
         if (int rc = r->clock.close(r->ctx->stream)) return rc;
         done += ps.n;
     }
@@ -470,6 +500,17 @@ extern "C" int chunky_render_kernel_info(chunky_render* r, int32_t out8[8]) {
     out8[4] = r->last_choice.pool;
     out8[5] = r->last_choice.ext;
     out8[7] = r->last_choice.sorted;
+    if (r->last_choice.blocks == 0 && r->have_camera && biome_map(r, nullptr)) {
+        // before the first launch of a target that tints by position: the biome instantiation its next launch will run
+        SceneView S;
+        if (scene_view(r->scene, &S, false) == CHUNKY_OK) {
+            const BiomePlan b = plan_biome(render_plan(r, S));
+            if (b.plan.status == PlanStatus::ok && b.refusal == BiomeRefusal::none) {
+                const bool pool = b.plan.family == KernelFamily::pool;
+                out8[0] = b.plan.tree, out8[1] = pool ? 1 : 0, out8[2] = b.plan.bvh ? 1 : 0, out8[4] = pool ? b.plan.park : -1, out8[5] = kChoiceBiome;
+            }
+        }
+    }
     if (r->launch_cap > 0) {
         out8[6] = r->launch_cap;  // (of the kernel family that ran last)
     } else {  // before the first launch: what chunky_render_passes is going to decide for this scene and option set
@@ -512,7 +553,11 @@ extern "C" int chunky_render_preview(chunky_render* r, int32_t* argb_out) {
     DevBuf out;
     size_t bytes = (size_t)r->width * r->height * 4;
     HIP_TRY(out.alloc(bytes));
-    HIP_TRY(launch_preview(r->kernel_variant, S, r->cam, r->opts, (int*)out.p, r->ctx->stream));
+    BiomeMap biome;
+    if (biome_map(r, &biome))
+        HIP_TRY(launch_preview_biome(r->kernel_variant, S, biome, r->cam, r->opts, (int*)out.p, r->ctx->stream));
+    else
+        HIP_TRY(launch_preview(r->kernel_variant, S, r->cam, r->opts, (int*)out.p, r->ctx->stream));
     HIP_TRY(hipMemcpyAsync(argb_out, out.p, bytes, hipMemcpyDeviceToHost, r->ctx->stream));
     HIP_TRY(hipStreamSynchronize(r->ctx->stream));
     return CHUNKY_OK;
@@ -538,7 +583,11 @@ extern "C" int chunky_render_trace_records(chunky_render* r, int32_t seed, const
     HIP_TRY(hipMalloc(&dc.p, (size_t)n * 4));
     HIP_TRY(hipMalloc(&dq.p, (size_t)n * 12));
     HIP_TRY(hipMemsetAsync(dr.p, 0, (size_t)n * kMaxTraces * sizeof(HitRecord), st));
-    HIP_TRY(launch_trace_records(r->kernel_variant, S, r->cam, r->opts, seed, (const int*)dg.p, n, (HitRecord*)dr.p, (int*)dc.p, (float*)dq.p, st));
+    BiomeMap biome;
+    if (biome_map(r, &biome))
+        HIP_TRY(launch_trace_records_biome(r->kernel_variant, S, biome, r->cam, r->opts, seed, (const int*)dg.p, n, (HitRecord*)dr.p, (int*)dc.p, (float*)dq.p, st));
+    else
+        HIP_TRY(launch_trace_records(r->kernel_variant, S, r->cam, r->opts, seed, (const int*)dg.p, n, (HitRecord*)dr.p, (int*)dc.p, (float*)dq.p, st));
     HIP_TRY(hipMemcpyAsync(records, dr.p, (size_t)n * kMaxTraces * sizeof(HitRecord), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(counts, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(radiance, dq.p, (size_t)n * 12, hipMemcpyDeviceToHost, st));

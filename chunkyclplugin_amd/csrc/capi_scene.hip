@@ -247,6 +247,26 @@ extern "C" int chunky_scene_set_sun(chunky_scene* scene, const int32_t sun[6]) {
     return CHUNKY_OK;
 }
 
+extern "C" int chunky_scene_set_biome_tints(chunky_scene* scene, const int32_t* rgb3, int x0, int z0, int size_x, int size_z) {
+    FAN_SCENE(scene, chunky_scene_set_biome_tints(m_, rgb3, x0, z0, size_x, size_z));
+    LOCK_SCENE(scene);
+    if (size_x < 0 || size_z < 0) return fail(CHUNKY_E_INVALID, "set_biome_tints: negative size %d x %d", size_x, size_z);
+    if ((size_x == 0) != (size_z == 0)) return fail(CHUNKY_E_INVALID, "set_biome_tints: size %d x %d (both 0 removes the map)", size_x, size_z);
+    if ((rgb3 == nullptr) != (size_x == 0)) return fail(CHUNKY_E_INVALID, "set_biome_tints: NULL colours go with size 0 x 0 and only with it");
+    if ((int64_t)size_x * size_z > CHUNKY_BIOME_MAX_CELLS)
+        return fail(CHUNKY_E_INVALID, "set_biome_tints: %d x %d cells, at most %d", size_x, size_z, (int)CHUNKY_BIOME_MAX_CELLS);
+    if (!rgb3) {
+        HIP_TRY(hipStreamSynchronize(scene->ctx->stream));  // queued launches may still read the map
+        scene->biome.release();
+        scene->biome_x0 = scene->biome_z0 = scene->biome_size_x = scene->biome_size_z = 0;
+        return CHUNKY_OK;
+    }
+    // (in stream order behind the launches that read the old map; the host array is the caller's again on return: DevBuf::upload)
+    HIP_TRY(scene->biome.upload(rgb3, (size_t)size_x * size_z * 3 * sizeof(int32_t), scene->ctx->stream));
+    scene->biome_x0 = x0, scene->biome_z0 = z0, scene->biome_size_x = size_x, scene->biome_size_z = size_z;
+    return CHUNKY_OK;
+}
+
 static int rebuild_derived(chunky_scene* s) {
     const std::vector<int32_t>&B = s->host_blocks, &M = s->host_materials, &A = s->host_aabbs, &Q = s->host_quads;
     hipStream_t st = s->ctx->stream;

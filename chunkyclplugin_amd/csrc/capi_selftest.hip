@@ -18,6 +18,24 @@ extern "C" int chunky_selftest_math(chunky_ctx* ctx, int which, int n, const flo
     return CHUNKY_OK;
 }
 
+extern "C" int chunky_selftest_plan_biome(const int32_t* plans16, int64_t n, int32_t* out16, int32_t* refusal) {
+    if (n < 0 || (n > 0 && (!plans16 || !out16 || !refusal))) return fail(CHUNKY_E_INVALID, "selftest_plan_biome: bad arguments");
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t* v = plans16 + 16 * i;
+        RenderPlan p{};
+        p.family = (KernelFamily)v[0], p.tree = v[1], p.park = v[2], p.words = v[3], p.group = v[4], p.depth = v[5];
+        p.bvh = v[6] != 0, p.ext = v[7] != 0, p.stats = v[8] != 0, p.sorted = v[9] != 0, p.proj = v[10] != 0;
+        p.lds = (size_t)(uint32_t)v[11], p.most = v[12], p.needs_list = v[13] != 0, p.status = (PlanStatus)v[14], p.ext_refusal = (ExtRefusal)v[15];
+        const BiomePlan b = plan_biome(p);
+        const RenderPlan& q = b.plan;
+        const int32_t o[16] = {(int32_t)q.family, q.tree, q.park, q.words, q.group, q.depth, q.bvh, q.ext, q.stats, q.sorted, q.proj,
+                               (int32_t)q.lds, q.most, q.needs_list, (int32_t)q.status, (int32_t)q.ext_refusal};
+        memcpy(out16 + 16 * i, o, sizeof o);
+        refusal[i] = (int32_t)b.refusal;
+    }
+    return CHUNKY_OK;
+}
+
 extern "C" int chunky_selftest_camera_rays(chunky_render* r, int32_t seed, float* out, int64_t n_floats) {
     if (r && !r->parts.empty()) return chunky_selftest_camera_rays(r->parts[0], seed, out, n_floats);
     LOCK_RENDER(r);

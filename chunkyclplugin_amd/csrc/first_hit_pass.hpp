@@ -72,7 +72,7 @@ DEV auto first_hit_part(const SceneView& S, f3 o, f3 d, int draw_depth, Hit& h, 
 // PROJ: a projected camera (projector types 1-5, 7, 8, rt_device.hpp projected_ray), instantiated apart so that the other cameras
 // keep their code.
 template <class Fold, int TREE, bool BVH, bool PROJ>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fold::waves(BVH)))) first_hit_kernel(FirstHitArgs<typename Fold::Out>) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fold::waves(BVH)))) first_hit_kernel(CHUNKY_KERNEL_ARGS_HEAD FirstHitArgs<typename Fold::Out>) {
     static_assert(sizeof(FirstHitArgs<typename Fold::Out>) <= 4096, "launch arguments must fit the 4 KB kernel-argument segment");
     extern __shared__ int lds[];
     LdsStack stack{lds + threadIdx.x, (int)blockDim.x};
@@ -126,13 +126,18 @@ Kernel first_hit_lookup(const FirstHitPlan& plan, Pick pick) {
 
 // A launch of a kernel that takes FirstHitArgs<Out> (first_hit_kernel, occlusion.hip's occlusion_kernel): a persistent grid, no more
 // workgroups than one claim per wave.  pick(tree constant, BVH constant, PROJ constant) names the instantiation.
-template <class Out, class Pick>
+// `biome`: the map that heads the arguments of the kernels of a unit compiled with CHUNKY_BIOME_TINT (rt_device.hpp); no other unit reads it.
+// (BIOME is part of the two launchers' names: a biome unit's instantiations are functions of their own, never merged with another unit's.)
+template <class Out, class Pick, bool BIOME = (CHUNKY_BIOME_TINT != 0)>
 hipError_t launch_first_hit_args(Pick pick, int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
-                                 const PassSeeds& P, const Out& out, int* counter, hipStream_t stream, AovChoice* chosen) {
+                                 const PassSeeds& P, const Out& out, int* counter, hipStream_t stream, AovChoice* chosen,
+                                 const BiomeMap* biome = nullptr) {
     if (P.n <= 0 || T.n_local <= 0) return hipSuccess;
     if (P.n > kMaxPassesPerLaunch) return hipErrorInvalidValue;
     const FirstHitPlan plan = plan_first_hit(variant, scene_facts(S));
-    typedef void (*Kernel)(FirstHitArgs<Out>);
+    typedef void (*Kernel)(CHUNKY_KERNEL_ARGS_HEAD FirstHitArgs<Out>);
+    if (BIOME && !biome) return hipErrorInvalidValue;
+    (void)biome;
     const Kernel k = C.projector_type > 0 ? first_hit_lookup<Kernel>(plan, [&](auto tree, auto bvh) { return pick(tree, bvh, std::true_type()); })
                                           : first_hit_lookup<Kernel>(plan, [&](auto tree, auto bvh) { return pick(tree, bvh, std::false_type()); });
     if (!k) return hipErrorInvalidDeviceFunction;  // a plan outside the list: an error, never another kernel
@@ -141,22 +146,22 @@ hipError_t launch_first_hit_args(Pick pick, int variant, const SceneView& S, con
     const long long n_units = pool_tiles(T, C.width, C.height) * (kSampleTile / kFirstHitUnit);
     int grid = 0;
     if (hipError_t e = persistent_grid(k, block, lds, (n_units + block / 64 - 1) / (block / 64), &grid)) return e;
-    if (chosen) *chosen = AovChoice{plan.tree, plan.bvh ? 1 : 0, grid};
+    if (chosen) *chosen = AovChoice{plan.tree, (plan.bvh ? 1 : 0) | (BIOME ? kChoiceBiome : 0), grid};
     hipError_t e = hipMemsetAsync(counter, 0, sizeof(int), stream);
     if (e != hipSuccess) return e;
     FirstHitArgs<Out> A{S, C, T, P, O.draw_depth, (int)n_units, counter, out};
     A.T.list = nullptr;  // (pool_slot_gid maps every shard form itself)
     A.T.n_list = 0;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(block), lds, stream, A);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(block), lds, stream, CHUNKY_LAUNCH_ARGS_HEAD(*biome) A);
     return hipGetLastError();
 }
 
-template <class Fold>
+template <class Fold, bool BIOME = (CHUNKY_BIOME_TINT != 0)>
 hipError_t launch_first_hit(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
-                            const typename Fold::Out& out, int* counter, hipStream_t stream, AovChoice* chosen) {
+                            const typename Fold::Out& out, int* counter, hipStream_t stream, AovChoice* chosen, const BiomeMap* biome = nullptr) {
     return launch_first_hit_args<typename Fold::Out>(
-        [](auto tree, auto bvh, auto proj) -> void (*)(FirstHitArgs<typename Fold::Out>) { return first_hit_kernel<Fold, decltype(tree)::value, decltype(bvh)::value, decltype(proj)::value>; },
-        variant, S, C, O, T, P, out, counter, stream, chosen);
+        [](auto tree, auto bvh, auto proj) -> void (*)(CHUNKY_KERNEL_ARGS_HEAD FirstHitArgs<typename Fold::Out>) { return first_hit_kernel<Fold, decltype(tree)::value, decltype(bvh)::value, decltype(proj)::value>; },
+        variant, S, C, O, T, P, out, counter, stream, chosen, biome);
 }
 
 }  // namespace chunky

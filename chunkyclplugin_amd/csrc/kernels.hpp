@@ -15,6 +15,7 @@ namespace chunky {
 
 struct SceneView;
 struct CameraView;
+struct BiomeMap;  // rt_device.hpp
 
 constexpr int kMaxTraces = 10;        // 5 path segments x (main + shadow trace)
 
@@ -46,9 +47,10 @@ struct KernelChoice {
     int bvh;     // entity-BVH phases compiled in
     int blocks;  // workgroups launched
     int pool;    // render_pool: paths parked per wave beside the 64 in its lanes; -1 = another kernel
-    int ext;     // the extended integrator (CHUNKY_OPT_SUN_SAMPLING / _EMITTERS / _BSDF / _EMITTER_NEE at non-default values)
+    int ext;     // 1: the extended integrator (CHUNKY_OPT_SUN_SAMPLING / _EMITTERS / _BSDF / _EMITTER_NEE at non-default values); kChoiceBiome: a biome-tint instantiation
     int sorted;  // render_pool: full cubes and model blocks tested in phases of their own
 };
+constexpr int kChoiceBiome = 2;  // KernelChoice::ext, and bit 1 of AovChoice::bvh: the launch ran a kernel compiled with CHUNKY_BIOME_TINT
 // staging floats render_pool needs for a launch of n passes over this rank's tiles
 inline size_t staging_floats(const ShardView& T, int width, int height, int n_passes) {
     return 3 * (size_t)pool_tiles(T, width, height) * kSampleTile * (size_t)n_passes;
@@ -97,6 +99,18 @@ hipError_t launch_render_stats(int variant, const SceneView& S, const CameraView
 // the kernels behind render_pool (render_fallback.hip): render_waves, render_lanes, as `plan` names them
 hipError_t launch_fallback(const RenderPlan& plan, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                            const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen);
+// Biome tints by block position: launch_render for a scene with a biome map — what plan_biome (launch_plan.hpp) makes of
+// plan_render's plan, on the kernels compiled with CHUNKY_BIOME_TINT (render_pool_biome.hip, render_pool_biome_bvh.hip, render_biome.hip);
+// hipErrorNotSupported for what plan_biome refuses.  The twins of launch_trace_records, launch_preview, launch_aov and launch_aov_ex follow.
+hipError_t launch_render_biome(int variant, const SceneView& S, const BiomeMap& B, const CameraView& C, const RenderOpts& O, const ShardView& T,
+                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen, float* staging,
+                               const int* seeds_dev);
+hipError_t launch_lanes_biome(const RenderPlan& plan, const SceneView& S, const BiomeMap& B, const CameraView& C, const RenderOpts& O,
+                              const ShardView& T, const PassSeeds& P, float* res, hipStream_t stream, KernelChoice* chosen);
+hipError_t launch_trace_records_biome(int variant, const SceneView& S, const BiomeMap& B, const CameraView& C, const RenderOpts& O, int seed,
+                                      const int* gids_dev, int n, HitRecord* out, int* counts, float* radiance, hipStream_t stream);
+hipError_t launch_preview_biome(int variant, const SceneView& S, const BiomeMap& B, const CameraView& C, const RenderOpts& O, int* argb,
+                                hipStream_t stream);
 // read-back exchange of a multi-GPU group: pack = true copies the pixels of this shard's slots from the image `fb` to `packed`
 // (3 floats per slot, padding slots skipped), pack = false scatters them back into an image
 hipError_t launch_gather(bool pack, const ShardView& T, int width, int height, float* fb, float* packed, hipStream_t stream);
@@ -126,6 +140,11 @@ struct AovExImages {
 // launch_aov with the five first-hit images folded from the same trace
 hipError_t launch_aov_ex(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
                          const AovExImages& I, int* counter, hipStream_t stream, AovChoice* chosen);
+// launch_aov / launch_aov_ex on the kernels that tint by position (aov_biome.hip); AovChoice::bvh then carries kChoiceBiome beside bit 0
+hipError_t launch_aov_biome(int variant, const SceneView& S, const BiomeMap& B, const CameraView& C, const RenderOpts& O, const ShardView& T,
+                            const PassSeeds& P, float* albedo, float* normal, int* counter, hipStream_t stream, AovChoice* chosen);
+hipError_t launch_aov_ex_biome(int variant, const SceneView& S, const BiomeMap& B, const CameraView& C, const RenderOpts& O, const ShardView& T,
+                               const PassSeeds& P, const AovExImages& I, int* counter, hipStream_t stream, AovChoice* chosen);
 // Sun-shadow and ambient-occlusion passes (occlusion.hip): P.n <= kMaxPassesPerLaunch; ao / sun are width * height
 // floats each, folded in place over the pixel slots of shard T; ao_distance > 0 (+inf allowed); `counter` as launch_aov's.
 hipError_t launch_occlusion(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,

@@ -190,4 +190,41 @@ FirstHitPlan plan_first_hit(int variant, const SceneFacts& F) {
     return FirstHitPlan{(tree >= 16 && tree <= 19) ? tree : -1, bvh};
 }
 
+// Biome tints: the plan of the kernels compiled with CHUNKY_BIOME_TINT (launch_plan.hpp has the table)
+BiomePlan plan_biome(const RenderPlan& in) {
+    BiomePlan b{in, BiomeRefusal::none};
+    RenderPlan& p = b.plan;
+    if (p.status != PlanStatus::ok) return b;  // refused by plan_render: no kernel is named
+    if (p.ext) b.refusal = BiomeRefusal::extended;
+    else if (p.stats) b.refusal = BiomeRefusal::stats;
+    else if (p.proj) b.refusal = BiomeRefusal::projected;
+    if (b.refusal != BiomeRefusal::none) return b;
+    if (p.family == KernelFamily::pool) {
+        if (p.bvh) {
+            if (p.tree != 17) p.tree = -1;
+            if (p.park != 32) p.park = 16;  // (tuning builds' pool sizes included)
+        } else {
+            if (p.tree != 0 && p.tree != 17 && p.tree != 18) p.tree = -1;
+            p.park = kPoolBiomePark;
+        }
+        p.sorted = false;
+        p.lds = (size_t)(kLaunchBlock / 64) * pool_wave_lds_bytes(p.park, p.words, (unsigned)p.depth);
+        return b;
+    }
+    // render_waves and render_lanes: one lane per pixel; of the LDS the to-visit stacks stay (plan_fallback: the rings lay behind them)
+    p.family = KernelFamily::lanes;
+    p.group = 0;
+    p.lds = (size_t)p.depth * kLaunchBlock * sizeof(int);
+    return b;
+}
+
+const char* biome_refusal_text(BiomeRefusal r) {
+    switch (r) {
+        case BiomeRefusal::stats: return "biome tints: the phase-statistics kernels (CHUNKY_OPT_KERNEL bit 2) do not tint by position; set CHUNKY_OPT_BIOME_TINT to 0 or remove the map";
+        case BiomeRefusal::extended: return "biome tints: the extended light-transport options do not tint by position; set CHUNKY_OPT_BIOME_TINT to 0 or remove the map";
+        case BiomeRefusal::projected: return "biome tints: projected cameras are tinted by render_lanes only (CHUNKY_OPT_KERNEL bit 1); or set CHUNKY_OPT_BIOME_TINT to 0 or remove the map";
+        default: return "";
+    }
+}
+
 }  // namespace chunky

@@ -150,6 +150,24 @@ struct FirstHitPlan {
 };
 FirstHitPlan plan_first_hit(int variant, const SceneFacts& F);
 
+// Biome tints by block position: with a biome map on the scene and CHUNKY_OPT_BIOME_TINT at 1 a launch runs a kernel
+// compiled with CHUNKY_BIOME_TINT (rt_device.hpp), and plan_biome maps what plan_render decided onto the instantiations that exist:
+//   render_pool, pinhole and pre-generated cameras: tree forms 0, 17, 18 and -1 without entity BVHs (16 and 19 run -1), 17 and -1 with
+//   them (18 runs -1); unsorted block tests; kPoolBiomePark parked paths without entity BVHs whatever the rig bits say, the plan's 16 or
+//   32 with them (CHUNKY_POOL_BIOME_INSTANCES, CHUNKY_POOL_BIOME_BVH_INSTANCES);
+//   render_waves and render_lanes plans: render_lanes (CHUNKY_LANES_INSTANCES), every camera.
+// Everything else is refused — BiomePlan::refusal says why, the C API answers CHUNKY_E_STATE with biome_refusal_text — never rendered
+// untinted: phase statistics, the extended light-transport options, projected cameras on render_pool.  A plan plan_render refused
+// (status != ok) comes back as it is.
+constexpr int kPoolBiomePark = kPoolPark;
+enum class BiomeRefusal : int { none = 0, stats, extended, projected };
+struct BiomePlan {
+    RenderPlan plan;
+    BiomeRefusal refusal;
+};
+BiomePlan plan_biome(const RenderPlan& p);
+const char* biome_refusal_text(BiomeRefusal r);
+
 }  // namespace chunky
 
 // ---------------------------------------------------------------------------------------------
@@ -211,6 +229,16 @@ FirstHitPlan plan_first_hit(int variant, const SceneFacts& F);
     X(0, 16, false) X(-1, 16, false) X(0, 16, true) X(-1, 16, true)                                                                    \
     X(0, 32, false) X(-1, 32, false)
 #define CHUNKY_LANES_INSTANCES(X) X(0) X(-1)
+// X(TREE, K, STATS, BVH, EXT, SORT) of render_pool compiled with CHUNKY_BIOME_TINT (render_pool_biome.hip, render_pool_biome_bvh.hip):
+// what plan_biome names
+#define CHUNKY_POOL_BIOME_INSTANCES(X)                                                                                                 \
+    X(0, kPoolBiomePark, false, false, false, false)                                                                                   \
+    X(17, kPoolBiomePark, false, false, false, false)                                                                                  \
+    X(18, kPoolBiomePark, false, false, false, false)                                                                                  \
+    X(-1, kPoolBiomePark, false, false, false, false)
+#define CHUNKY_POOL_BIOME_BVH_INSTANCES(X)                                                                                             \
+    X(17, 32, false, true, false, false) X(-1, 32, false, true, false, false)                                                          \
+    X(17, 16, false, true, false, false) X(-1, 16, false, true, false, false)
 // X(TREE, BVH) of the first-hit kernels (first_hit_pass.hpp first_hit_kernel, occlusion.hip occlusion_kernel, lights.hip light_kernel)
 #define CHUNKY_FIRST_HIT_INSTANCES(X)                                                                                                  \
     X(0, true) X(17, true) X(18, true) X(-1, true)                                                                                     \

@@ -561,7 +561,9 @@ DEV T arg_copy(const T __attribute__((address_space(4))) * p) {
 // the kernel-argument segment as an A, through a pointer the optimiser cannot see through (no instruction)
 template <typename A>
 DEV const A __attribute__((address_space(4))) * opaque_args() {
-    const A __attribute__((address_space(4)))* a = (const A __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+    // (kKernelArgsOffset: 0, or in the units compiled with CHUNKY_BIOME_TINT the biome map that heads their kernels' arguments — rt_device.hpp)
+    const A __attribute__((address_space(4)))* a =
+        (const A __attribute__((address_space(4)))*)((const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() + kKernelArgsOffset);
     asm volatile("" : "+s"(a));
     return a;
 }

@@ -5,7 +5,7 @@
 // SORT: full cubes and model blocks are tested in phases of their own (on the re-laid-out tree, whose leaf entries say which a block is);
 // plan_render (launch_plan.cpp) picks it for scenes with many model blocks
 template <int TREE, int K, bool STATS, bool BVH = false, bool EXT = false, bool SORT = false>
-__global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_BVH_WAVES : CHUNKY_POOL_WAVES))) render_pool(WaveArgs unused_by_name) {
+__global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_BVH_WAVES : CHUNKY_POOL_WAVES))) render_pool(CHUNKY_KERNEL_ARGS_HEAD WaveArgs unused_by_name) {
     constexpr int WORDS = pool_words(EXT, BVH);  // 16-byte words of a parked path (pool_pack; launch_plan.hpp: the launch sizes the LDS with the same two functions)
     constexpr int END = BVH ? ST_TRACED : ST_SHADE;  // where a lane goes when the octree part of a trace ends
     // candidates sorted into full cubes (ST_BLOCK) and model blocks (ST_MODEL); not instantiated with entity BVHs or the extended

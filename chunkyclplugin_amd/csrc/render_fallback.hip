@@ -9,30 +9,9 @@
 #include <cstdlib>
 
 #include "path_state.hpp"
+#include "lane_kernels.hpp"  // render_lanes
 
 namespace chunky {
-
-template <int TREE>
-__global__ void __launch_bounds__(256) render_lanes(SceneView S, CameraView C, RenderOpts O, ShardView T, PassSeeds P,
-                                                     float* __restrict__ res) {
-    extern __shared__ int lds[];
-    LdsStack stack{lds + threadIdx.x, (int)blockDim.x};
-    int local = blockIdx.x * blockDim.x + threadIdx.x;
-    if (local >= T.n_local) return;
-    int gid = shard_gid(T, local);
-    if (gid >= C.width * C.height) return;
-    float* px = res + 3 * (size_t)gid;
-    f3 mean = mk3(px[0], px[1], px[2]);
-    for (int k = 0; k < P.n; k++) {
-        f3 c = sample_path<false, TREE>(S, C, O, P.seed[k], gid, stack, nullptr, nullptr);
-        int spp = P.first_spp + k;
-        float fs = (float)spp, fs1 = (float)(spp + 1);
-        mean = f3{(mean.x * fs + c.x) / fs1, (mean.y * fs + c.y) / fs1, (mean.z * fs + c.z) / fs1};
-    }
-    px[0] = mean.x;
-    px[1] = mean.y;
-    px[2] = mean.z;
-}
 
 // ---------------------------------------------------------------------------------------------
 // render_waves — the wave-scheduled form of the same path.

@@ -523,7 +523,30 @@ namespace proj {
 // The entity-BVH instantiations are compiled in a translation unit of their own, render_pool_bvh.hip: this file again, up to here, with
 // CHUNKY_IEEE_FORMS (rt_short_forms.h) — those kernels keep the compiler's divisions and roots.  This unit instantiates no kernel with
 // BVH = true, that one none with BVH = false.
+// The instantiations that tint by position (CHUNKY_BIOME_TINT, rt_device.hpp: the biome map heads their arguments) are compiled in two
+// more units, render_pool_biome.hip and render_pool_biome_bvh.hip: this file up to here once more, for the pinhole and pre-generated cameras.
 typedef void (*PoolKernel)(WaveArgs);
+typedef void (*PoolBiomeKernel)(BiomeMap, WaveArgs);
+PoolBiomeKernel pool_kernel_biome(const RenderPlan& p);
+PoolBiomeKernel pool_kernel_biome_bvh(const RenderPlan& p);
+#if CHUNKY_BIOME_TINT
+#define CHUNKY_POOL_BIOME_CASE(TREE, K, STATS, BVH, EXT, SORT)                                                                   \
+    if (p.tree == (TREE) && p.park == (K) && p.stats == (STATS) && p.bvh == (BVH) && p.ext == (EXT) && p.sorted == (SORT) && !p.proj) \
+        return render_pool<TREE, K, STATS, BVH, EXT, SORT>;
+#ifdef CHUNKY_POOL_BVH_TU
+PoolBiomeKernel pool_kernel_biome_bvh(const RenderPlan& p) {
+    CHUNKY_POOL_BIOME_BVH_INSTANCES(CHUNKY_POOL_BIOME_CASE)
+    return nullptr;
+}
+#else
+PoolBiomeKernel pool_kernel_biome(const RenderPlan& p) {
+    if (p.bvh) return pool_kernel_biome_bvh(p);
+    CHUNKY_POOL_BIOME_INSTANCES(CHUNKY_POOL_BIOME_CASE)
+    return nullptr;
+}
+#endif
+}  // namespace chunky
+#else  // CHUNKY_BIOME_TINT
 #define CHUNKY_POOL_CASE(TREE, K, STATS, BVH, EXT, SORT)                                                                        \
     if (p.tree == (TREE) && p.park == (K) && p.stats == (STATS) && p.bvh == (BVH) && p.ext == (EXT) && p.sorted == (SORT))      \
         return p.proj ? proj::render_pool<TREE, K, STATS, BVH, EXT, SORT> : render_pool<TREE, K, STATS, BVH, EXT, SORT>;
@@ -601,18 +624,20 @@ __global__ void __launch_bounds__(256) clear_foreign_kernel(ShardView T, int wid
 // render_pool + fold_kernel, as planned: look the kernel up, size the persistent grid, fill the arguments, launch, fold.
 static hipError_t launch_pool(const RenderPlan& plan, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
-                              float* staging, const int* seeds_dev, float* fold_stats = nullptr) {
-    const PoolKernel k = pool_kernel(plan);
-    if (!k) return hipErrorInvalidDeviceFunction;  // a plan outside the list: an error, never another kernel
+                              float* staging, const int* seeds_dev, float* fold_stats = nullptr, const BiomeMap* biome = nullptr) {
+    // (biome: a plan of plan_biome's, run by the instantiation that takes the map ahead of the same arguments)
+    const PoolKernel k = biome ? nullptr : pool_kernel(plan);
+    const PoolBiomeKernel kb = biome ? pool_kernel_biome(plan) : nullptr;
+    if (!k && !kb) return hipErrorInvalidDeviceFunction;  // a plan outside the list: an error, never another kernel
     const int block = kLaunchBlock, park = plan.park;
     const long long n_tiles = pool_tiles(T, C.width, C.height);
     const long long n_samples = n_tiles * kSampleTile * P.n;  // tiles at the image's edges are padded
     // a wave keeps 64 + park paths in flight: no more workgroups than the samples can feed
     const long long want = (n_samples + (long long)(block / 64) * (64 + park) - 1) / ((long long)(block / 64) * (64 + park));
     int grid = 0;  // (for an empty share or no passes `want`, and so the grid, is <= 0: nothing is launched, below)
-    if (hipError_t e = persistent_grid(k, block, plan.lds, want, &grid)) return e;
+    if (hipError_t e = kb ? persistent_grid(kb, block, plan.lds, want, &grid) : persistent_grid(k, block, plan.lds, want, &grid)) return e;
     if (T.n_local <= 0 || P.n <= 0) return hipSuccess;  // (behind the device queries: a call on a broken device fails whatever it renders)
-    if (chosen) *chosen = KernelChoice{plan.tree, 1, plan.bvh ? 1 : 0, grid, park, plan.ext ? 1 : 0, plan.sorted ? 1 : 0};
+    if (chosen) *chosen = KernelChoice{plan.tree, 1, plan.bvh ? 1 : 0, grid, park, kb ? kChoiceBiome : (plan.ext ? 1 : 0), plan.sorted ? 1 : 0};
     hipError_t e = hipMemsetAsync(work_counter, 0, sizeof(int), stream);
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(work_counter + kXcdCounters, 0, kXcdRanges * sizeof(int), stream);  // the per-XCD sample ranges (xcd_claim)
@@ -620,7 +645,10 @@ static hipError_t launch_pool(const RenderPlan& plan, const SceneView& S, const 
     const WaveArgs A = make_wave_args(S, C, O, T, P, work_counter, res, (unsigned long long*)(work_counter + 2), (unsigned)plan.depth, staging, (unsigned)n_samples,
                                       (unsigned)((n_tiles + kXcdRanges - 1) / kXcdRanges * kSampleTile * P.n), fast_div((unsigned)P.n * (unsigned)kSubBlock),
                                       fast_div((unsigned)((C.width + kTileEdge - 1) >> kTileLog)), seeds_dev);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(block), plan.lds, stream, A);
+    if (kb)
+        hipLaunchKernelGGL(kb, dim3(grid), dim3(block), plan.lds, stream, *biome, A);
+    else
+        hipLaunchKernelGGL(k, dim3(grid), dim3(block), plan.lds, stream, A);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (fold_stats) {  // adaptive sampling: the same running mean, and the pixels' luminance statistic from the same read
@@ -655,6 +683,24 @@ hipError_t launch_render_stats(int variant, const SceneView& S, const CameraView
     return launch_fallback(plan, S, C, O, T, P, res, work_counter, stream, chosen);
 }
 
+// launch_render for a scene with a biome map (kernels.hpp): plan_render's plan as plan_biome maps it
+hipError_t launch_render_biome(int variant, const SceneView& S, const BiomeMap& B, const CameraView& C, const RenderOpts& O, const ShardView& T,
+                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen, float* staging,
+                               const int* seeds_dev) {
+    const BiomePlan b = plan_biome(plan_render(variant, scene_facts(S), O, C.projector_type, T, P.n, work_counter && staging, seeds_dev != nullptr, false));
+    switch (b.plan.status) {
+        case PlanStatus::invalid_value: return hipErrorInvalidValue;
+        case PlanStatus::not_supported: return hipErrorNotSupported;
+        default: break;
+    }
+    if (b.refusal != BiomeRefusal::none) return hipErrorNotSupported;  // (the C API has refused it with the reason before it came here)
+    if (b.plan.family == KernelFamily::pool)
+        return launch_pool(b.plan, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr, nullptr, &B);
+    ShardView F = T;
+    if (b.plan.needs_list) F.n_local = T.n_list;  // a shard of 16 x 16 blocks: the rank's pixels as a list (launch_render_stats)
+    return launch_lanes_biome(b.plan, S, B, C, O, F, P, res, stream, chosen);
+}
+
 hipError_t launch_gather(bool pack, const ShardView& T, int width, int height, float* fb, float* packed, hipStream_t stream) {
     if (T.n_local <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((T.n_local + 255) / 256);
@@ -674,3 +720,4 @@ hipError_t launch_clear_foreign(const ShardView& T, int width, int height, float
 
 }  // namespace chunky
 #endif  // CHUNKY_POOL_BVH_TU
+#endif  // CHUNKY_BIOME_TINT

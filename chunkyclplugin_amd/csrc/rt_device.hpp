@@ -134,6 +134,52 @@ struct CameraView {
 
 // (RenderOpts, the other kernel argument, lives in launch_plan.hpp: the launch planner reads it too)
 
+// Biome tints by block position (chunky_scene_set_biome_tints): per cell (x, z) of a rectangle of the octree's
+// cell grid three packed words — the foliage, grass and water colours (tint types 1, 2, 3), RGB in the low 24 bits — at
+// rgb3[((z - z0) * size_x + (x - x0)) * 3 + type - 1].  The map is the FIRST kernel argument of the kernels compiled with
+// CHUNKY_BIOME_TINT (one 64-byte line of the argument segment; every other argument follows it unchanged), and of no other kernel.
+struct alignas(64) BiomeMap {
+    const int* __restrict__ rgb3;
+    int x0, z0, size_x, size_z;
+};
+static_assert(sizeof(BiomeMap) == 64, "the biome kernels' other arguments start 64 bytes into the argument segment");
+// Which kernels tint by position is decided when their translation unit is compiled, as CHUNKY_ADDR32_FORMS is (below): a unit that
+// defines CHUNKY_BIOME_TINT 1 ahead of every include compiles kernels that take the map (CHUNKY_KERNEL_ARGS_HEAD in their
+// signatures) and read it where a block's tinted material is evaluated; every other unit compiles the code it always had.
+#ifndef CHUNKY_BIOME_TINT
+#define CHUNKY_BIOME_TINT 0
+#endif
+#if CHUNKY_BIOME_TINT
+#define CHUNKY_KERNEL_ARGS_HEAD BiomeMap biome_unused_by_name,
+#define CHUNKY_LAUNCH_ARGS_HEAD(biome) (biome),
+constexpr int kKernelArgsOffset = (int)sizeof(BiomeMap);  // where the arguments behind the map start (path_state.hpp opaque_args)
+#else
+#define CHUNKY_KERNEL_ARGS_HEAD
+#define CHUNKY_LAUNCH_ARGS_HEAD(biome)
+constexpr int kKernelArgsOffset = 0;
+#endif
+#if CHUNKY_BIOME_TINT
+// The cell of a block test as ONE register: its index in the map, or -1 outside the rectangle (unsigned differences: a cell left of
+// or in front of the origin wraps to a large value and fails the same compare).  The map's words are scalar loads off the head of
+// the argument segment, made where they are used: nothing of the map lives in registers outside a block test.
+DEV int biome_cell(int bx, int bz) {
+    const BiomeMap __attribute__((address_space(4)))* B = (const BiomeMap __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+    const unsigned ux = (unsigned)bx - (unsigned)B->x0, uz = (unsigned)bz - (unsigned)B->z0;
+    return (ux < (unsigned)B->size_x && uz < (unsigned)B->size_z) ? (int)(uz * (unsigned)B->size_x + ux) : -1;
+}
+// the tint word of type tt (1, 2, 3) at a cell of the map (the host caps the map at 2^26 cells: the word index fits 32 bits)
+DEV unsigned biome_tint_word(int cell, unsigned tt) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const BiomeMap __attribute__((address_space(4)))* B = (const BiomeMap __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+    const int __attribute__((address_space(1)))* rgb3 = (const int __attribute__((address_space(1)))*)(unsigned long long)B->rgb3;
+    return 0xFF000000u | ((unsigned)rgb3[(unsigned)cell * 3u + (tt - 1u)] & 0xFFFFFFu);
+#else
+    (void)cell, (void)tt;
+    return 0u;
+#endif
+}
+#endif
+
 // what the launch planner reads of a scene (launch_plan.hpp)
 inline SceneFacts scene_facts(const SceneView& S) {
     return SceneFacts{S.wide != nullptr, S.wide_nlev, {S.wide_bits[0], S.wide_bits[1], S.wide_bits[2], S.wide_bits[3], S.wide_bits[4], S.wide_bits[5]},
@@ -251,19 +297,24 @@ __device__ __constant__ const float kEmittanceLut[256] = {
 
 // K/material.h:31-82.  `shade` = false skips the writes that only matter to the main record
 // (shadow rays need the accept/reject decision only).
+// `cell`: where the material belongs to a block of the octree, the block test's cell in the biome map (biome_cell; -1 outside the map,
+// and for everything that has no cell: entity triangles, emitter samples).  Read by the units compiled with CHUNKY_BIOME_TINT alone.
 DEV bool material_eval(const SceneView& S, unsigned flags, unsigned tint, unsigned tex_size, unsigned color_w,
-                       unsigned ne, float u, float v, Hit& h, int m5 = 0);
-DEV bool material_sample(const SceneView& S, int material, float u, float v, Hit& h) {
+                       unsigned ne, float u, float v, Hit& h, int m5 = 0, int cell = -1);
+DEV bool material_sample(const SceneView& S, int material, float u, float v, Hit& h, int cell = -1) {
     const int* m = S.materials + material;
-    return material_eval(S, m[0], m[1], m[2], m[3], m[4], u, v, h, m[5]);
+    return material_eval(S, m[0], m[1], m[2], m[3], m[4], u, v, h, m[5], cell);
 }
 DEV bool material_eval(const SceneView& S, unsigned flags, unsigned tint, unsigned tex_size, unsigned color_w,
-                       unsigned ne, float u, float v, Hit& h, int m5) {
+                       unsigned ne, float u, float v, Hit& h, int m5, int cell) {
     f4 c = (flags & 4) ? unpack_unorm8(atlas_texel(S, u, v, (int)color_w, (int)tex_size)) : color_from_argb(color_w);
     if (!(c.w > kEps)) return false;
     unsigned tt = tint >> 24;
     if (tt == 0xFF || tt == 1 || tt == 2 || tt == 3) {
         unsigned tc = tt == 0xFF ? tint : (tt == 1 ? 0xFF71A74Du : (tt == 2 ? 0xFF8EB971u : 0xFF3F76E4u));
+#if CHUNKY_BIOME_TINT
+        if (tt != 0xFF && cell >= 0) tc = biome_tint_word(cell, tt);  // the colour is fetched behind the alpha test, for types 1 - 3 inside the map only
+#endif
         f4 t = color_from_argb(tc);
         c = f4{c.x * t.x, c.y * t.y, c.z * t.z, c.w * t.w};
     }
@@ -310,17 +361,17 @@ DEV Face face_map2(const Slabs& s, float tmin, f3 p) {  // AABB_full_intersect_m
 // position `pos` where a direction is expected (K/block.h:52), so the UV point is no + tmin*pos.
 // The material arrives as its 5 words (read from the material palette, or inline in block_info).
 DEV float cube_hit(const SceneView& S, unsigned m0, unsigned m1, unsigned m2, unsigned m3, unsigned m4, f3 no, f3 pos,
-                   f3 inv, Hit& h, int m5 = 0) {
+                   f3 inv, Hit& h, int m5 = 0, int cell = -1) {
     Slabs s = slabs(0, 1, 0, 1, 0, 1, no, inv);
     float tn = slab_near(s), tf = slab_far(s);
     if (tf < tn) return rt_nan();
     Face f = face_unit(s, tn, no + pos * tn);
     h.normal = f.n;  // written before the material test (K/block.h:59-60)
-    return material_eval(S, m0, m1, m2, m3, m4, f.u, f.v, h, m5) ? tn - kOffset : rt_nan();
+    return material_eval(S, m0, m1, m2, m3, m4, f.u, f.v, h, m5, cell) ? tn - kOffset : rt_nan();
 }
 
 // AABB model (type 2) — K/block.h:66-91, K/primitives.h:165-260
-DEV float aabb_model_hit(const SceneView& S, int ptr, f3 no, f3 dir, f3 inv, Hit& h) {
+DEV float aabb_model_hit(const SceneView& S, int ptr, f3 no, f3 dir, f3 inv, Hit& h, int cell = -1) {
     const int* __restrict__ model = S.aabbs + ptr;
     int boxes = model[0];
     float best = rt_inf();
@@ -347,7 +398,7 @@ DEV float aabb_model_hit(const SceneView& S, int ptr, f3 no, f3 dir, f3 inv, Hit
         if (fl & 4) u = 1 - u;
         if (fl & 2) v = 1 - v;
         if (fl & 1) { float t = u; u = v; v = t; }
-        if (material_sample(S, mat, u, v, h)) {
+        if (material_sample(S, mat, u, v, h, cell)) {
             h.normal = f.n;
             best = tn;
             hit = true;
@@ -357,7 +408,7 @@ DEV float aabb_model_hit(const SceneView& S, int ptr, f3 no, f3 dir, f3 inv, Hit
 }
 
 // Quad model (type 3) — K/block.h:92-116, K/primitives.h:263-319
-DEV float quad_model_hit(const SceneView& S, int ptr, f3 no, f3 dir, Hit& h) {
+DEV float quad_model_hit(const SceneView& S, int ptr, f3 no, f3 dir, Hit& h, int cell = -1) {
     const int* __restrict__ model = S.quads + ptr;
     int quads = model[0];
     float best = rt_inf();
@@ -391,7 +442,7 @@ DEV float quad_model_hit(const SceneView& S, int ptr, f3 no, f3 dir, Hit& h) {
         if (!(u >= 0 && u <= 1 && v >= 0 && v <= 1)) continue;
         float tu = as_float(q[9]) + (u * as_float(q[10]));
         float tv = as_float(q[11]) + (v * as_float(q[12]));
-        if (material_sample(S, q[13], tu, tv, h)) {
+        if (material_sample(S, q[13], tu, tv, h, cell)) {
             h.normal = n;
             best = t;
             hit = true;
@@ -400,15 +451,15 @@ DEV float quad_model_hit(const SceneView& S, int ptr, f3 no, f3 dir, Hit& h) {
     return hit ? best : rt_nan();
 }
 
-DEV bool material_sample8(const SceneView& S, int m8, float u, float v, Hit& h) {
+DEV bool material_sample8(const SceneView& S, int m8, float u, float v, Hit& h, int cell = -1) {
     // Stays a signed 64-bit index in every unit: m8 is read out of a record, and a leaf with an odd block pointer (which no upload
     // refuses) makes block_hit find its "record" across two blocks of block_info — what stands there as a material index is anything.
     const int4 a = S.mat8[m8], b = S.mat8[m8 + 1];
-    return material_eval(S, a.x, a.y, a.z, a.w, b.x, u, v, h, b.y);
+    return material_eval(S, a.x, a.y, a.z, a.w, b.x, u, v, h, b.y, cell);
 }
 
 // aabb_model_hit / quad_model_hit on the aligned records (same arithmetic, same order; rec = first record << 8 | count)
-DEV float aabb_model_hit_rec(const SceneView& S, int rec, f3 no, f3 dir, f3 inv, Hit& h) {
+DEV float aabb_model_hit_rec(const SceneView& S, int rec, f3 no, f3 dir, f3 inv, Hit& h, int cell = -1) {
     const int boxes = rec & 0xFF, first = (int)((unsigned)rec >> 8);
     float best = rt_inf();
     bool hit = false;
@@ -439,7 +490,7 @@ DEV float aabb_model_hit_rec(const SceneView& S, int rec, f3 no, f3 dir, f3 inv,
         if (fl & 4) u = 1 - u;
         if (fl & 2) v = 1 - v;
         if (fl & 1) { float t = u; u = v; v = t; }
-        if (material_sample8(S, mat, u, v, h)) {
+        if (material_sample8(S, mat, u, v, h, cell)) {
             h.normal = f.n;
             best = tn;
             hit = true;
@@ -448,7 +499,7 @@ DEV float aabb_model_hit_rec(const SceneView& S, int rec, f3 no, f3 dir, f3 inv,
     return hit ? best : rt_nan();
 }
 
-DEV float quad_model_hit_rec(const SceneView& S, int rec, f3 no, f3 dir, Hit& h) {
+DEV float quad_model_hit_rec(const SceneView& S, int rec, f3 no, f3 dir, Hit& h, int cell = -1) {
     const int quads = rec & 0xFF, first = (int)((unsigned)rec >> 8);
     float best = rt_inf();
     bool hit = false;
@@ -484,7 +535,7 @@ DEV float quad_model_hit_rec(const SceneView& S, int rec, f3 no, f3 dir, Hit& h)
         }
         float tu = as_float(r3.x) + (u * as_float(r3.y));
         float tv = as_float(r3.z) + (v * as_float(r3.w));
-        if (material_eval(S, r5.x, r5.y, r5.z, r5.w, r4.w, tu, tv, h, (int)((unsigned)r4.w >> 8))) {  // r4.w = emittance byte | word 5 << 8
+        if (material_eval(S, r5.x, r5.y, r5.z, r5.w, r4.w, tu, tv, h, (int)((unsigned)r4.w >> 8), cell)) {  // r4.w = emittance byte | word 5 << 8
             h.normal = n;
             best = t;
             hit = true;
@@ -504,26 +555,31 @@ template <int KINDS = kBlockAny>
 DEV float block_hit(const SceneView& S, int block, int bx, int by, int bz, f3 pos, f3 dir, f3 inv, Hit& h) {
     if (KINDS == kBlockAny && block == kAnyType) return rt_nan();
     f3 no = (pos - dir * kOffset) - mk3((float)bx, (float)by, (float)bz);
+#if CHUNKY_BIOME_TINT
+    const int cell = biome_cell(bx, bz);  // (bx, bz): the cell BlockPalette_intersectBlock receives — for a leaf larger than one cell, the march point's
+#else
+    constexpr int cell = -1;
+#endif
     int type, ptr;
     if (KINDS != kBlockAny || S.block_info) {
         // (stays an unsigned index off a 64-bit address: as a 32-bit byte offset it cost render_pool<-1, 0> a spilled register — EXPERIMENTS 7.4)
         const int4 a = S.block_info[(unsigned)block], b = S.block_info[(unsigned)block + 1u];
         type = a.x;
         ptr = a.y;
-        if (KINDS != kBlockModels && type == 1) return cube_hit(S, a.z, a.w, b.x, b.y, b.z, no, pos, inv, h, b.w);  // word 7 of a cube: material word 5
+        if (KINDS != kBlockModels && type == 1) return cube_hit(S, a.z, a.w, b.x, b.y, b.z, no, pos, inv, h, b.w, cell);  // word 7 of a cube: material word 5
         if (KINDS == kBlockCubes) return rt_nan();
-        if (b.w != 0) return type == 2 ? aabb_model_hit_rec(S, b.w, no, dir, inv, h) : quad_model_hit_rec(S, b.w, no, dir, h);
+        if (b.w != 0) return type == 2 ? aabb_model_hit_rec(S, b.w, no, dir, inv, h, cell) : quad_model_hit_rec(S, b.w, no, dir, h, cell);
     } else {
         type = S.blocks[block];
         ptr = S.blocks[block + 1];
         if (type == 1) {
             const int* m = S.materials + ptr;
-            return cube_hit(S, m[0], m[1], m[2], m[3], m[4], no, pos, inv, h, m[5]);
+            return cube_hit(S, m[0], m[1], m[2], m[3], m[4], no, pos, inv, h, m[5], cell);
         }
     }
     switch (type) {
-        case 2: return aabb_model_hit(S, ptr, no, dir, inv, h);
-        case 3: return quad_model_hit(S, ptr, no, dir, h);
+        case 2: return aabb_model_hit(S, ptr, no, dir, inv, h, cell);
+        case 3: return quad_model_hit(S, ptr, no, dir, h, cell);
         default: return rt_nan();
     }
 }

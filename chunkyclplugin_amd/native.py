@@ -18,7 +18,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("CHUNKY_HIP_LIB") or os.path.join(PKG_DIR, "libchunky_hip.so")  # override: tuning builds (tools/variants.sh)
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
-SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "lights.hip", "matte.hip", "denoise.hip", "adaptive.hip",
+SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_pool_biome.hip", "render_pool_biome_bvh.hip", "render_biome.hip", "aov_biome.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "lights.hip", "matte.hip", "denoise.hip", "adaptive.hip",
            "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_occlusion.hip", "capi_lights.hip", "capi_matte.hip", "capi_adaptive.hip", "capi_denoise.hip",
            "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp",
            "scene_records.cpp", "widetree.cpp", "launch_plan.cpp"]
@@ -30,7 +30,9 @@ HIT_DTYPE = np.dtype([("hit", "<i4"), ("material", "<i4"), ("distance", "<f4"), 
 
 PALETTE_BLOCK, PALETTE_MATERIAL, PALETTE_AABB, PALETTE_QUAD, PALETTE_TRIG = range(5)
 BVH_WORLD, BVH_ACTOR = 0, 1
-OPT_DRAW_DEPTH, OPT_MAX_DEPTH, OPT_EMITTER_SCALE, OPT_KERNEL, OPT_SUN_SAMPLING, OPT_EMITTERS, OPT_BSDF, OPT_EMITTER_NEE, OPT_BVH_CULL_BEHIND = range(9)
+OPT_DRAW_DEPTH, OPT_MAX_DEPTH, OPT_EMITTER_SCALE, OPT_KERNEL, OPT_SUN_SAMPLING, OPT_EMITTERS, OPT_BSDF, OPT_EMITTER_NEE, OPT_BVH_CULL_BEHIND, OPT_BIOME_TINT = range(10)
+BIOME_MAX_CELLS = 1 << 26  # CHUNKY_BIOME_MAX_CELLS: the most cells chunky_scene_set_biome_tints takes
+KERNEL_BIOME = 2  # word 5 of chunky_render_kernel_info and bit 1 of word 1 of chunky_render_aov_kernel_info: a biome-tint instantiation
 PEER_LOCAL, PEER_DIRECT, PEER_STAGED = 0, 1, 2
 TRANSPORT_PEER_COPY, TRANSPORT_RCCL_SENDRECV, TRANSPORT_RCCL_REDUCE = 0, 1, 2
 E_INVALID, E_NO_DEVICE, E_HIP, E_STATE, E_ABORTED = -1, -2, -3, -4, -5
@@ -207,6 +209,7 @@ def lib() -> C.CDLL:
             "chunky_scene_write_atlas_tile": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp],
             "chunky_scene_set_sky": [vp, vp, C.c_int, C.c_int, f32],
             "chunky_scene_set_sun": [vp, vp],
+            "chunky_scene_set_biome_tints": [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int],
             "chunky_scene_emitters": [vp, vp, i32, C.POINTER(i32)],
             "chunky_render_create": [vp, vp, C.c_int, C.c_int, C.POINTER(vp)],
             "chunky_render_destroy": [vp],
@@ -269,6 +272,7 @@ def lib() -> C.CDLL:
             "chunky_render_adaptive_noise": [vp, vp, i64],
             "chunky_render_adaptive_kernel_time": [vp, C.POINTER(f32), C.POINTER(C.c_int)],
             "chunky_selftest_render_list": [vp, vp, C.c_int, vp, C.c_int],
+            "chunky_selftest_plan_biome": [vp, i64, vp, vp],
             "chunky_adaptive_host_begin": [C.c_int, C.c_int, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveState), vp, vp, vp, vp],
             "chunky_adaptive_host_resume": [C.POINTER(AdaptiveState), vp, C.c_int, vp, vp, vp, vp],
             "chunky_adaptive_state_check": [C.POINTER(AdaptiveState), vp, vp],
@@ -369,6 +373,19 @@ def widetree_hit_top(tree: np.ndarray, depth: int, blocks: np.ndarray, level_bit
     check(lib().chunky_widetree_hit_top(ptr(tree), tree.size, depth, None if lb is None else ptr(lb), 0 if lb is None else lb.size,
                                         ptr(blocks) if blocks.size else None, blocks.size, C.byref(top)))
     return top.value
+
+
+# the instantiations of the kernels that tint by position (csrc/launch_plan.hpp CHUNKY_POOL_BIOME_INSTANCES, _BIOME_BVH_INSTANCES, CHUNKY_LANES_INSTANCES)
+BIOME_POOL_FORMS, BIOME_POOL_BVH_FORMS, BIOME_LANES_FORMS = (0, 17, 18, -1), (17, -1), (0, -1)
+BIOME_POOL_PARK, BIOME_POOL_BVH_PARKS = 64, (16, 32)
+
+
+def plan_biome(plans16):
+    """chunky_selftest_plan_biome: (plans (n, 16) int32, refusals (n,) int32) for launch plans given as rows of 16 ints (no device needed)."""
+    p = np.ascontiguousarray(plans16, np.int32).reshape(-1, 16)
+    out, why = np.zeros_like(p), np.zeros(len(p), np.int32)
+    check(lib().chunky_selftest_plan_biome(ptr(p), len(p), ptr(out), ptr(why)))
+    return out, why
 
 
 ADDR32_ATLAS, ADDR32_SKY, ADDR32_RECORDS = 1, 2, 4  # chunky_addr32_word / chunky_scene_addr32 (csrc/addr32.h)

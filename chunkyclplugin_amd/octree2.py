@@ -402,6 +402,12 @@ def camera_settings_lens(cam: dict, origin=(0.0, 0.0, 0.0), world_width: float =
     return kind, settings, lens
 
 
+def biome_tint_option(js: dict) -> int:
+    """The value of native.OPT_BIOME_TINT for a scene JSON: Chunky's `biomeColors` flag (on unless the scene switches it off).  The
+    colours themselves are not read here: the host passes them to chunky_scene_set_biome_tints."""
+    return 1 if bool(js.get("biomeColors", True)) else 0
+
+
 def load_scene(octree2_path: str, json_path: str = None, width: int = 1920, height: int = 1080,
                emitters: bool = False) -> scenes.PackedScene:
     """`.octree2` (+ scene JSON for camera / sun) -> PackedScene through the procedural asset pack (`asset_pack`: model classes

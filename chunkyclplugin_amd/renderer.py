@@ -158,6 +158,7 @@ class HipSceneLoader:
         self._h = C.c_void_p()
         check(native.lib().chunky_scene_create(self.instance._h, C.byref(self._h)))
         self.packed = None
+        self._has_biome = False
 
     def load_packed(self, sc) -> bool:
         L = native.lib()
@@ -179,8 +180,26 @@ class HipSceneLoader:
         check(L.chunky_scene_set_sky(self._h, ptr(sky), sky.shape[1], sky.shape[0], float(sc.sky_intensity)))
         sun = i32(sc.sun)
         check(L.chunky_scene_set_sun(self._h, ptr(sun)))
+        biome = getattr(sc, "biome", None)
+        if biome is not None:
+            self.set_biome_tints(*biome)
+        elif self._has_biome:  # the scene loaded before had a map, this one has none
+            self.set_biome_tints(0, 0, None)
         self.packed = sc
         return True
+
+    def set_biome_tints(self, x0: int, z0: int, rgb) -> None:
+        """chunky_scene_set_biome_tints: rgb[size_z, size_x, 3] holds the foliage, grass and water colour (RGB in the low 24 bits) of
+        the octree cells x0 <= x < x0 + size_x, z0 <= z < z0 + size_z; rgb = None removes the map."""
+        if rgb is None:
+            check(native.lib().chunky_scene_set_biome_tints(self._h, None, 0, 0, 0, 0))
+            self._has_biome = False
+            return
+        a = np.ascontiguousarray(rgb, np.int32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"expected colours of shape (size_z, size_x, 3), got {a.shape}")
+        check(native.lib().chunky_scene_set_biome_tints(self._h, ptr(a), int(x0), int(z0), a.shape[1], a.shape[0]))
+        self._has_biome = True
 
     def emitters(self) -> np.ndarray:
         """The emitter list of the next-event-estimation extension: rows {x, y, z, level << 25 | block pointer}."""
@@ -315,7 +334,7 @@ class HipPathTracingRenderer:
         out = np.zeros(8, np.int32)
         check(native.lib().chunky_render_kernel_info(self._h, ptr(out)))
         return {"tree": int(out[0]), "group": int(out[1]), "bvh": bool(out[2]), "blocks": int(out[3]), "pool": int(out[4]),
-                "ext": bool(out[5]), "passes_per_launch": int(out[6]), "sorted": bool(out[7])}
+                "ext": int(out[5]) == 1, "biome": int(out[5]) == native.KERNEL_BIOME, "passes_per_launch": int(out[6]), "sorted": bool(out[7])}
 
     def phase_stats(self, reset: bool = True) -> dict:
         out = np.zeros(24, np.uint64)
@@ -378,7 +397,7 @@ class HipPathTracingRenderer:
         """The AOV instantiation the last AOV launch ran: tree form, entity-BVH walk, workgroups, launches of the last call."""
         out = np.zeros(4, np.int32)
         check(native.lib().chunky_render_aov_kernel_info(self._h, ptr(out)))
-        return {"tree": int(out[0]), "bvh": bool(out[1]), "blocks": int(out[2]), "launches": int(out[3])}
+        return {"tree": int(out[0]), "bvh": bool(out[1] & 1), "biome": bool(out[1] & native.KERNEL_BIOME), "blocks": int(out[2]), "launches": int(out[3])}
 
     # --- the first-hit images beside them (chunky_render_aov_passes_ex / _read_ex) -------------------
     def render_aov_ex(self, seeds, first_buffer_spp: int = 0, sync: bool = True) -> None:

@@ -415,6 +415,9 @@ class PackedScene:
     width: int = 64
     height: int = 64
     name: str = "scene"
+    # biome tints by block position (chunky_scene_set_biome_tints): (x0, z0, int32 [size_z, size_x, 3]) — the foliage, grass and water
+    # colour (RGB in the low 24 bits) of the octree cells x0 <= x < x0 + size_x, z0 <= z < z0 + size_z — or None: the reference's constants
+    biome: Optional[Tuple[int, int, np.ndarray]] = None
 
     def with_view(self, width: int, height: int, camera: Optional[np.ndarray] = None,
                   projector_type: Optional[int] = None) -> "PackedScene":
@@ -767,6 +770,7 @@ def save_scene(sc: PackedScene, path: str, compressed: bool = False) -> None:
     tmp = path + f".{os.getpid()}.tmp.npz"
     (np.savez_compressed if compressed else np.savez)(tmp, meta=np.array([sc.octree_depth, sc.projector_type, sc.width, sc.height], np.int64),
              sky_intensity=np.float64(sc.sky_intensity), name=np.array(sc.name),
+             **({} if sc.biome is None else {"biome_origin": np.array(sc.biome[:2], np.int64), "biome_rgb": np.ascontiguousarray(sc.biome[2], np.int32)}),
              **{f: getattr(sc, f) for f in _ARRAY_FIELDS})
     os.replace(tmp, path)
 
@@ -794,9 +798,19 @@ def save_raw(sc: PackedScene, path: str) -> None:
 def load_scene(path: str) -> PackedScene:
     z = np.load(path)
     depth, proj, w, h = (int(v) for v in z["meta"])
+    biome = (int(z["biome_origin"][0]), int(z["biome_origin"][1]), z["biome_rgb"]) if "biome_rgb" in z.files else None
     return PackedScene(octree_depth=depth, projector_type=proj, width=w, height=h,
-                       sky_intensity=float(z["sky_intensity"]), name=str(z["name"]),
+                       sky_intensity=float(z["sky_intensity"]), name=str(z["name"]), biome=biome,
                        **{f: z[f] for f in _ARRAY_FIELDS})
+
+
+def biome_patches(size_x: int, size_z: int, patch: int, seed: int = 0) -> np.ndarray:
+    """A biome colour map for PackedScene.biome: int32 [size_z, size_x, 3] in square patches of `patch` cells (the last row and column
+    of patches cut off at the map's edge), each with one random (foliage, grass, water) colour triple, RGB in the low 24 bits."""
+    rng = np.random.default_rng(seed)
+    nx, nz = -(-int(size_x) // int(patch)), -(-int(size_z) // int(patch))
+    triples = rng.integers(0, 1 << 24, size=(nz, nx, 3), dtype=np.int64).astype(np.int32)
+    return np.ascontiguousarray(np.repeat(np.repeat(triples, patch, axis=0), patch, axis=1)[:size_z, :size_x])
 
 
 def cached_outdoor_world(**kw) -> PackedScene:

@@ -155,6 +155,26 @@ int chunky_scene_set_sky(chunky_scene* scene, const uint8_t* rgba, int width, in
 int chunky_scene_emitters(chunky_scene* scene, int32_t* out4, int32_t cap, int32_t* count);
 /* getSun(): flags, textureSize, textureLocation, intensity, altitude, azimuth (PackedSun.java:32-41) */
 int chunky_scene_set_sun(chunky_scene* scene, const int32_t sun[6]);
+/* Biome tints by block position (no reference counterpart: the reference multiplies tint types 1, 2 and 3 — foliage, grass, water — by
+ * three fixed colours, K/material.h:61-72).  rgb3 holds size_x * size_z * 3 ints: the cell (x, z) of the octree's cell grid, x0 <= x <
+ * x0 + size_x, z0 <= z < z0 + size_z, has its foliage, grass and water colour at rgb3[((z - z0) * size_x + (x - x0)) * 3 + 0 / 1 / 2].
+ * Only the low 24 bits of a word are read: RGB as in a tint word.  The array is copied before the call returns.
+ * Rule (CHUNKY_OPT_BIOME_TINT at 1, its default): a material of tint type t in {1, 2, 3} evaluated for a block of the octree multiplies
+ * by colorFromArgb(0xFF000000 | rgb3[cell][t - 1]), where the cell is the integer cell (x, z) BlockPalette_intersectBlock receives (for a
+ * leaf larger than one cell: the march point's cell); outside the rectangle it multiplies by the reference's constant.  Entity triangles
+ * keep the constants, tint types 0 and 0xFF and everything else are unchanged, and record.material (the block-id image, the mattes,
+ * chunky_render_trace_records) reports the block pointer the octree holds.  The image is, bit for bit, the reference's image of a
+ * world in which every tinted block was replaced, cell by cell, by a copy whose material carries the constant tint 0xFF000000 | rgb.
+ * rgb3 == NULL with both sizes 0 removes the map.  CHUNKY_E_INVALID: a negative size, exactly one size 0, rgb3 == NULL with a size
+ * that is not 0, a non-NULL rgb3 with both sizes 0, or size_x * size_z above CHUNKY_BIOME_MAX_CELLS.  On a group the map reaches every member.
+ * As every setter it may be called again at any time: launches already queued finish on the old map.
+ * Served with a map: chunky_render_passes / _run (the pool kernel for pinhole and pre-generated cameras, render_lanes for the fallback
+ * kernels' scenes and options), chunky_render_preview, chunky_render_trace_records, chunky_render_aov_passes and _aov_passes_ex.  The
+ * matte and occlusion passes hold no colour and run as they are.  CHUNKY_E_STATE, before anything is allocated or launched, with
+ * the reason in the message: phase statistics (CHUNKY_OPT_KERNEL bit 2), the extended light-transport options, a projected camera
+ * on the pool kernel (CHUNKY_OPT_KERNEL bit 1 serves it), chunky_render_light_passes, chunky_render_adaptive*, chunky_selftest_render_list. */
+#define CHUNKY_BIOME_MAX_CELLS (1 << 26)
+int chunky_scene_set_biome_tints(chunky_scene* scene, const int32_t* rgb3, int x0, int z0, int size_x, int size_z);
 
 /* ---- render target (replaces the buffers and the launch of OpenClPathTracingRenderer.java:67-141) */
 int chunky_render_create(chunky_ctx* ctx, chunky_scene* scene, int width, int height, chunky_render** out);
@@ -281,7 +301,10 @@ typedef enum chunky_option {
      * few ulps of a box edge, the reference accepts a hit the culled walk never tests — 40 of 10^8 adversarial traces
      * (EXPERIMENTS.md 5.3, tests/test_bvh_cull.py).  Whole frames are usually identical to the reference's, single pixels
      * occasionally not: hence an option, and 0 the default.  Specification: oracle/port.c with port_set_bvh_cull(1). */
-    CHUNKY_OPT_BVH_CULL_BEHIND = 8  /* int: 0 (default) / 1 */
+    CHUNKY_OPT_BVH_CULL_BEHIND = 8, /* int: 0 (default) / 1 */
+    /* 1 (default): a scene's biome map (chunky_scene_set_biome_tints) tints this target's images by block position; 0: the target
+     * ignores the map and runs exactly the kernels it runs for a scene without one.  Without a map the option does nothing. */
+    CHUNKY_OPT_BIOME_TINT = 9       /* int: 1 (default) / 0 */
 } chunky_option;
 int chunky_render_set_option(chunky_render* r, int option, int32_t value);
 
@@ -334,7 +357,8 @@ int chunky_render_kernel_time(chunky_render* r, float* total_ms, int* launches);
  * workgroups launched; paths parked per wave (pool kernel; -1 = the grouped kernel); extended integrator; the most passes one
  * launch of this target carries (256, fewer when the staged samples of a launch would not fit: chunky_render_passes cuts longer
  * requests into launches of that many); 1 when the launch tested full cubes and model blocks in phases of their own}.  On a group:
- * member 0's launch. */
+ * member 0's launch.  The sixth word is 2 for a biome-tint instantiation (chunky_scene_set_biome_tints), before the target's first launch
+ * too: the first five words then name the instantiation its next launch will run (workgroups 0). */
 int chunky_render_kernel_info(chunky_render* r, int32_t out8[8]);
 
 /* Profile of the wave-scheduled kernel, filled only while CHUNKY_OPT_KERNEL has bit 2 set: for each of
@@ -398,7 +422,8 @@ int chunky_render_aov_reset(chunky_render* r);
 int chunky_render_aov_kernel_time(chunky_render* r, float* total_ms, int* launches);
 /* The AOV instantiation the most recent launch ran (as chunky_render_kernel_info): out4 = {tree form (0 reference octree layout,
  * -1 generic wide tree, 16 + n dense top node over n levels: the form render_pool runs for the scene), entity-BVH walk present,
- * workgroups launched, launches made by the most recent chunky_render_aov_passes}. */
+ * workgroups launched, launches made by the most recent chunky_render_aov_passes}.  Bit 1 of the second word: a biome-tint instantiation
+ * (chunky_scene_set_biome_tints). */
 int chunky_render_aov_kernel_info(chunky_render* r, int32_t out4[4]);
 
 /* ---- five more images of the same first hit, for compositing: coverage ("transparent sky"), depth, position, emittance and the
@@ -760,6 +785,12 @@ int chunky_render_adaptive_kernel_time(chunky_render* r, float* total_ms, int* r
  * framebuffer as it is.  pixels: n_pixels distinct indices y * width + x in any order.  Blocking.  Same state errors as
  * chunky_render_adaptive. */
 int chunky_selftest_render_list(chunky_render* r, const int32_t* pixels, int n_pixels, const int32_t* seeds, int n);
+/* ---- self test of the biome-tint launch plan (host only, needs no device): for n launch plans of 16 ints each — family (0 the pool
+ * kernel, 1 render_waves, 2 render_lanes), tree form, parked paths, words, lanes per pixel, stack entries, entity BVHs, extended
+ * integrator, statistics, sorted block tests, projected camera, LDS bytes, most passes, needs the pixel list, status (0 ok), the
+ * extended options' refusal — out16 receives the plan of the kernels that tint by position in the same layout and refusal[i] why
+ * there is none (0: there is one; 1 phase statistics, 2 the extended options, 3 a projected camera on the pool kernel). */
+int chunky_selftest_plan_biome(const int32_t* plans16, int64_t n, int32_t* out16, int32_t* refusal);
 
 /* ---- adaptive sampling that stops and continues: pause, a raised SPP target, a render dump reloaded after a restart ----
  * A run is described by its state after `passes` passes; every active pixel has seen exactly those passes.  Beside this header the
