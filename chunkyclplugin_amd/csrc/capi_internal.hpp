@@ -21,6 +21,7 @@
 #include "capi_error.hpp"
 #include "capi_host.hpp"
 #include "kernels.hpp"
+#include "lights_host.hpp"
 #include "rccl_dyn.hpp"
 #include "rt_device.hpp"
 #include "scene_records.hpp"
@@ -203,6 +204,11 @@ struct chunky_render {
     // are its own: no other call sees them
     DevBuf lights, light_mix;
     FirstHitPass light_pass{LaunchClock(&free_events)};
+    // chunky_render_light_set_emitter_groups: the table (n_groups == 0: no groups), and on the device the group images, the kernel's
+    // per-sample sums and touched words and the table's bytes (capi_lights.hip), allocated by the set call
+    LightGroupTable light_table;
+    DevBuf light_groups;
+    bool light_groups_rendered = false;  // a light pass has run since the groups were set: their images can be read
     // chunky_render_denoise: the filter's workspace (kept between calls) and its timing, apart from the render and AOV launches'
     DevBuf dn_work, dn_out;
     LaunchClock dn_clock{&free_events};  // (a bracket holds all launches of one call: their number is its weight)

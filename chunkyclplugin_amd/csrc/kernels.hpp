@@ -156,6 +156,24 @@ hipError_t launch_lights(int variant, const SceneView& S, const CameraView& C, c
                          float* const images[4], int* counter, hipStream_t stream, AovChoice* chosen);
 // out[i] = (w[0] * sky[i] + w[1] * sun[i]) + w[2] * emitters[i] for n floats on the device, without fma
 hipError_t launch_light_mix(const float* sky, const float* sun, const float* emitters, const float w[3], float* out, long long n, hipStream_t stream);
+// The emitter groups of a render target as the kernel reads them (lights_groups.hip; lights_device.hpp LightGroupOut), all device memory
+constexpr int kLightMaxGroups = 8;         // CHUNKY_LIGHT_MAX_EMITTER_GROUPS
+constexpr int kChoiceLightGroups = 4;      // bit 2 of AovChoice::bvh: the launch ran lights_groups.hip's kernel
+struct LightGroupImages {
+    int n_groups;                   // 1 .. kLightMaxGroups
+    float* images;                  // n_groups images of 3 * width * height floats
+    float* acc;                     // 3 * n_groups floats per pixel, all zero bits or whatever: read only where `touched` says so
+    int* touched;                   // a word per pixel, zero between launches
+    const unsigned char* of_block;  // n_blocks bytes: the group of block pointer p at [p >> 1]
+    int n_blocks;
+    int world_group, actor_group;
+};
+// launch_lights with one more image per emitter group folded from the same walk
+hipError_t launch_light_groups(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,
+                               float* const images[4], const LightGroupImages& G, int* counter, hipStream_t stream, AovChoice* chosen);
+// out[i] = ((w_sky * sky[i] + w_sun * sun[i]) + w_groups[0] * groups[i]) + w_groups[1] * groups[n + i] ... for n floats, without fma
+hipError_t launch_light_group_mix(const float* sky, const float* sun, const float* groups, int n_groups, float w_sky, float w_sun, const float* w_groups,
+                                  float* out, long long n, hipStream_t stream);
 // ID-matte passes (matte.hip; specification: matte_spec.h): P.n <= kMaxPassesPerLaunch; `planes` is 13 * width * height ints (six planes of
 // ids, six of counts, `other`), updated in place over the pixel slots of shard T; `counter` as launch_aov's.  The choice record is the AOV's.
 hipError_t launch_matte(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T, const PassSeeds& P,

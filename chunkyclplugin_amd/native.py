@@ -18,9 +18,9 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("CHUNKY_HIP_LIB") or os.path.join(PKG_DIR, "libchunky_hip.so")  # override: tuning builds (tools/variants.sh)
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
-SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_pool_biome.hip", "render_pool_biome_bvh.hip", "render_biome.hip", "aov_biome.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "lights.hip", "matte.hip", "denoise.hip", "adaptive.hip",
+SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_pool_biome.hip", "render_pool_biome_bvh.hip", "render_biome.hip", "aov_biome.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "lights.hip", "lights_groups.hip", "matte.hip", "denoise.hip", "adaptive.hip",
            "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_occlusion.hip", "capi_lights.hip", "capi_matte.hip", "capi_adaptive.hip", "capi_denoise.hip",
-           "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp",
+           "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp", "lights_host.cpp",
            "scene_records.cpp", "widetree.cpp", "launch_plan.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
 
@@ -41,6 +41,8 @@ AOV_ALPHA, AOV_DEPTH, AOV_POSITION, AOV_EMITTANCE, AOV_BLOCK = 2, 3, 4, 5, 6  # 
 AOV_WORDS = {AOV_ALBEDO: 3, AOV_NORMAL: 3, AOV_ALPHA: 1, AOV_DEPTH: 1, AOV_POSITION: 3, AOV_EMITTANCE: 1, AOV_BLOCK: 1}  # words per pixel
 AOV_AO, AOV_SUN = 7, 8  # chunky_render_occlusion_read (a float per pixel each)
 LIGHT_SKY, LIGHT_SUN, LIGHT_EMITTERS, LIGHT_ALL = range(4)  # chunky_render_light_read (3 floats per pixel each)
+LIGHT_MAX_EMITTER_GROUPS = 8  # CHUNKY_LIGHT_MAX_EMITTER_GROUPS
+KERNEL_LIGHT_GROUPS = 4  # bit 2 of word 1 of chunky_render_light_kernel_info: the kernel that carries the emitter groups ran
 MATTE_SLOTS = 6  # CHUNKY_MATTE_*: slots per pixel, the ids of a miss and of the two entity BVHs, the id an empty rank reports
 MATTE_SKY, MATTE_WORLD_ENTITY, MATTE_ACTOR_ENTITY, MATTE_EMPTY = -1, -2, -3, -2 ** 31
 DENOISE_DEMODULATE = 1  # chunky_denoise_params.flags
@@ -245,6 +247,9 @@ def lib() -> C.CDLL:
             "chunky_render_light_read": [vp, C.c_int, vp, i64],
             "chunky_render_light_mix": [vp, vp, vp, i64],
             "chunky_render_light_reset": [vp],
+            "chunky_render_light_set_emitter_groups": [vp, C.c_int, vp, vp, C.c_int],
+            "chunky_render_light_read_group": [vp, C.c_int, vp, i64],
+            "chunky_render_light_mix_groups": [vp, f32, f32, vp, C.c_int, vp, i64],
             "chunky_render_light_kernel_time": [vp, C.POINTER(f32), C.POINTER(C.c_int)],
             "chunky_render_light_kernel_info": [vp, vp],
             "chunky_render_matte_passes": [vp, vp, C.c_int],

@@ -480,10 +480,40 @@ class HipPathTracingRenderer:
         return ms.value, n.value
 
     def lights_info(self) -> dict:
-        """The instantiation the last light-group launch ran: tree form, entity-BVH walk, workgroups, launches of the last call."""
+        """The instantiation the last light-group launch ran: tree form, entity-BVH walk, whether it carried the emitter groups, workgroups,
+        launches of the last call."""
         out = np.zeros(4, np.int32)
         check(native.lib().chunky_render_light_kernel_info(self._h, ptr(out)))
-        return {"tree": int(out[0]), "bvh": bool(out[1]), "blocks": int(out[2]), "launches": int(out[3])}
+        return {"tree": int(out[0]), "bvh": bool(out[1] & 1), "groups": bool(out[1] & native.KERNEL_LIGHT_GROUPS), "blocks": int(out[2]),
+                "launches": int(out[3])}
+
+    def set_emitter_groups(self, mapping, n_groups: Optional[int] = None) -> int:
+        """Split the emitters' share by what emits: `mapping` is {id: group} over block pointers (scenes.emitter_ids),
+        native.MATTE_WORLD_ENTITY and native.MATTE_ACTOR_ENTITY; every other id is group 0.  n_groups defaults to the highest group
+        named + 1; an empty mapping with n_groups None (or 0) drops the groups.  The group images start at zero and the four images
+        are not touched: call reset_lights() too unless they are empty.  Returns the number of groups."""
+        ids = np.array(list(mapping.keys()), np.int32)
+        groups = np.array([int(mapping[k]) for k in mapping], np.int64)
+        if len(groups) and (groups.min() < 0 or groups.max() > 255):
+            raise ValueError("a group is a number from 0 to 255")
+        n = int(groups.max()) + 1 if n_groups is None and len(groups) else int(n_groups or 0)
+        g8 = groups.astype(np.uint8)
+        check(native.lib().chunky_render_light_set_emitter_groups(self._h, n, ptr(ids) if len(ids) else None, ptr(g8) if len(ids) else None, len(ids)))
+        return n
+
+    def read_light_group(self, group: int) -> np.ndarray:
+        """The image of one emitter group as a (height, width, 3) float32 array."""
+        out = np.empty((self.height, self.width, 3), np.float32)
+        check(native.lib().chunky_render_light_read_group(self._h, int(group), ptr(out), out.size))
+        return out
+
+    def mix_light_groups(self, w_sky: float, w_sun: float, w_groups) -> np.ndarray:
+        """((w_sky * SKY + w_sun * SUN) + w_groups[0] * G0) + w_groups[1] * G1 ..., mixed on the device, as a (height, width, 3)
+        float32 array; one weight per group of the target."""
+        w = np.ascontiguousarray(w_groups, np.float32).reshape(-1)
+        out = np.empty((self.height, self.width, 3), np.float32)
+        check(native.lib().chunky_render_light_mix_groups(self._h, float(w_sky), float(w_sun), ptr(w) if w.size else None, w.size, ptr(out), out.size))
+        return out
 
     # --- antialiased ID mattes (chunky_render_matte_*) ------------------------------------------------
     def render_matte(self, seeds, sync: bool = True) -> None:

@@ -689,6 +689,51 @@ def add_entities(scene: PackedScene, n_tris: int, seed: int = 11, actor_tris: in
                                name=scene.name + f"+{n_tris}tri")
 
 
+def bvh_triangles(bvh: np.ndarray, trigs: np.ndarray) -> np.ndarray:
+    """Offsets into `trigs` of every triangle (20 ints each; word 19 is its material pointer) in the leaves of `bvh`, ascending;
+    none for the empty BVH."""
+    nodes = np.asarray(bvh, np.int32).reshape(-1, 7)
+    trigs = np.asarray(trigs, np.int32)
+    if len(nodes) == 1 and np.isnan(nodes[0, 1:2].view(np.float32)[0]):
+        return np.zeros(0, np.int64)
+    out = []
+    for head in nodes[nodes[:, 0] <= 0, 0]:
+        at = -int(head)
+        out += [at + 1 + 20 * i for i in range(int(trigs[at]))]
+    return np.array(sorted(out), np.int64)
+
+
+def material_is_emissive(materials: np.ndarray, m: int) -> bool:
+    """A material record emits: an emittance texture (flag bit 1 of word 0) or a non-zero emittance byte (word 4) — `material.h:76-79`."""
+    return 0 <= m and m + 5 < len(materials) and bool((int(materials[m]) & 2) or (int(materials[m + 4]) & 0xFF))
+
+
+def block_materials(sc: "PackedScene", ptr: int) -> List[int]:
+    """Material pointers of the block at block-palette pointer `ptr` ([] for a block that cannot be hit)."""
+    blocks, aabbs, quads = (np.asarray(a, np.int32) for a in (sc.block_palette, sc.aabb_models, sc.quad_models))
+    if ptr < 0 or ptr + 1 >= len(blocks):
+        return []
+    kind, p = int(blocks[ptr]), int(blocks[ptr + 1])
+    if kind == 1:
+        return [p]
+    if kind == 2:
+        return [int(aabbs[p + 1 + 13 * i + k]) for i in range(int(aabbs[p])) for k in range(7, 13)]
+    if kind == 3:
+        return [int(quads[p + 1 + 15 * i + 13]) for i in range(int(quads[p]))]
+    return []
+
+
+def emitter_ids(sc: "PackedScene") -> Tuple[np.ndarray, bool, bool]:
+    """What there is to group for chunky_render_light_set_emitter_groups: (the block pointers with an emissive material, ascending
+    int32; whether the world BVH holds an emissive triangle; whether the actor BVH does)."""
+    mats = np.asarray(sc.material_palette, np.int32)
+    n = len(np.asarray(sc.block_palette))
+    ptrs = [p for p in range(0, n - 1, 2) if any(material_is_emissive(mats, m) for m in block_materials(sc, p))]
+    trigs = np.asarray(sc.bvh_trigs, np.int32)
+    ent = [any(material_is_emissive(mats, int(trigs[t + 19])) for t in bvh_triangles(b, trigs)) for b in (sc.world_bvh, sc.actor_bvh)]
+    return np.array(ptrs, np.int32), ent[0], ent[1]
+
+
 def embed_offset(depth: int, slots: Sequence[int]) -> np.ndarray:
     """(x, y, z) of the corner of the cube reached from the root of a depth-`depth` octree through child slots `slots`
     (slot = (x << 2) | (y << 1) | z of one address bit, top level first)."""

@@ -566,6 +566,44 @@ int chunky_render_light_kernel_time(chunky_render* r, float* total_ms, int* laun
 /* The instantiation the most recent light-group launch ran: the four words of chunky_render_aov_kernel_info. */
 int chunky_render_light_kernel_info(chunky_render* r, int32_t out4[4]);
 
+/* ---- emitter light groups: CHUNKY_LIGHT_EMITTERS split by what emits, so that a compositor turns the torches down while the lava
+ * stays.  Ids are the ids of the ID mattes below: a block pointer (rec.material of an octree hit: even, >= 0, inside the block
+ * palette), CHUNKY_MATTE_WORLD_ENTITY or CHUNKY_MATTE_ACTOR_ENTITY; the id of a hit names the last part of closestIntersect that
+ * won, at every vertex of the path, not only the first.  Every id belongs to one of n_groups groups; an id that is not listed
+ * belongs to group 0, "the rest".
+ *
+ * Specification.  For group g take the scene in which every block and entity triangle whose id is NOT in g keeps its place but
+ * points to copies of its materials with bit 1 of word 0 cleared and word 4 zero (the emittance becomes exactly 0).  Group g's image
+ * IS the reference's image of that scene with sky intensity 0, sun intensity 0 and the target's emitter scale, bit for bit.  Per
+ * sample the group's sum receives, in vertex order, the (c * (emittance * scale)) * throughput that CHUNKY_LIGHT_EMITTERS receives at
+ * the hits whose id maps to g, and at every miss or unshadowed sun ray the same literally evaluated (dark * throughput) * e term
+ * (a NaN direction makes every group NaN, as it does the reference).  A hit of another group adds (c * (0 * scale)) * throughput,
+ * which is +-0 for a finite scale and changes no sum: a sum that starts at +0 is never -0.  Each group image folds with
+ * (img * spp + v) / (spp + 1) every pass, also where v is +0.  The groups sum to CHUNKY_LIGHT_EMITTERS to rounding (at one pass
+ * within the bound above).
+ *
+ * With groups set, chunky_render_light_passes folds the four images exactly as before, bit for bit, and one image per group from
+ * the same walk; shards, group targets, chunky_render_light_reset (which zeroes the group images too), _kernel_time and _kernel_info
+ * (bit 2 of word 1: the kernel that carries the groups ran) behave as for the four images, and so do the refusals (the experimental
+ * light-transport options, a biome-tinted target).  A scene update that shortens the block palette afterwards is legal: a pointer
+ * beyond the stored table is group 0.  The Java binding does not reach these calls. */
+#define CHUNKY_LIGHT_MAX_EMITTER_GROUPS 8
+/* Set (n_groups 1 .. 8) or drop (n_groups 0, which frees the group images: every light call then behaves exactly as without this
+ * call) the groups of a target: ids[i] belongs to group_of[i] < n_groups.  The group images, allocated here, start at zero; the four
+ * images are NOT touched, so the group images lag behind them unless the host calls chunky_render_light_reset too.  Waits for the
+ * target's enqueued work.  CHUNKY_E_INVALID (nothing changes): n_groups outside 0 .. 8, n_ids < 0, NULL with n_ids > 0, ids with
+ * n_groups 0, an odd pointer or one beyond the palette, any other negative id, an id listed twice, a group >= n_groups.  While groups
+ * are set chunky_render_light_passes answers CHUNKY_E_STATE to a non-finite CHUNKY_OPT_EMITTER_SCALE (0 * inf would make the
+ * specification NaN wherever another group is hit). */
+int chunky_render_light_set_emitter_groups(chunky_render* r, int n_groups, const int32_t* ids, const uint8_t* group_of, int n_ids);
+/* Blocking read-back of one group image, 3*width*height floats.  CHUNKY_E_STATE with no groups set or before the first
+ * chunky_render_light_passes since they were set; CHUNKY_E_INVALID for a group outside 0 .. n_groups - 1 or a wrong count. */
+int chunky_render_light_read_group(chunky_render* r, int group, float* out, int64_t n_floats);
+/* A rebalanced image on the device, read back: out = ((w_sky * SKY + w_sun * SUN) + w_groups[0] * G0) + w_groups[1] * G1 ... per
+ * float, in that order, each operation rounded to float (no fma).  n_groups must be the target's.  CHUNKY_E_INVALID for NULL or
+ * non-finite weights, another n_groups, a NULL buffer or a wrong count; CHUNKY_E_STATE as chunky_render_light_read_group. */
+int chunky_render_light_mix_groups(chunky_render* r, float w_sky, float w_sun, const float* w_groups, int n_groups, float* out, int64_t n_floats);
+
 /* ---- antialiased ID mattes (no reference counterpart; the idea of Cryptomatte): per pixel a short list of (id, the number of passes
  * that saw it), counted over the same camera rays the beauty passes use, so that a mask for any set of ids is a sum of shares and
  * lines up with the antialiased image.  The exact arithmetic is chunkyclplugin_amd/csrc/matte_spec.h, which the kernels and the

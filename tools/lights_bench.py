@@ -8,7 +8,15 @@ with the scene's sun flag off); kernel time from the library's HIP-event accesso
 chunky_render_light_kernel_time).  The three group images cost three beauty renders without this pass, so the figure is light-group
 time / beauty time against 3.  With the sun flag off a path has no sun traces: (sun on - sun off) is what they cost.
 
-    python tools/lights_bench.py [out.json]     (default profiles/lights_bench.json)"""
+    python tools/lights_bench.py [out.json]     (default profiles/lights_bench.json)
+
+--groups: the emitter groups (chunky_render_light_set_emitter_groups).  On ONE target, for N = 16 and 64: one warm-up of each kind, then
+three alternating repeats of the beauty passes, the ungrouped light passes and the light passes with G = 1, 4 and 8 groups (the view's
+emissive block pointers dealt round-robin into the groups; the groups are set between the timed calls).  Before anything is timed the
+grouped call's four images are compared with the ungrouped call's.  One grouped walk delivers sky, sun and G group images, which cost
+G + 2 beauty renders with darkened scenes: the walk wins where grouped time / beauty time < G + 2.
+
+    python tools/lights_bench.py --groups [out.json]     (default profiles/lights_groups_bench.json)"""
 import dataclasses
 import json
 import os
@@ -83,5 +91,101 @@ def main(path):
     print(json.dumps(res))
 
 
+GROUPS = (1, 4, 8)
+
+
+def deal(ids, g):
+    """the ids dealt round-robin into g groups"""
+    return {int(i): k % g for k, i in enumerate(ids)}
+
+
+def bench_groups(r, ids, n):
+    seeds = native.java_random_ints(n)
+
+    def grouped(g):
+        def call(spp):
+            r.set_emitter_groups(deal(ids, g), g)
+            r.render_lights(seeds, first_buffer_spp=spp)
+        return call
+
+    def ungrouped(spp):
+        r.set_emitter_groups({})
+        r.render_lights(seeds, first_buffer_spp=spp)
+    kinds = {"beauty": (lambda spp: r.render_passes(seeds, first_buffer_spp=spp), r.kernel_time), "lights": (ungrouped, r.lights_time)}
+    kinds.update({f"lights_g{g}": (grouped(g), r.lights_time) for g in GROUPS})
+    for call, timer in kinds.values():  # warm-up
+        call(0)
+        timer()
+    ms = {k: [] for k in kinds}
+    carried = {}
+    for rep in range(REPEATS):
+        for k, (call, timer) in kinds.items():
+            call(n * (rep + 1))
+            ms[k].append(timer()[0])
+            if k != "beauty":
+                carried[k] = r.lights_info()["groups"]
+    assert carried == {"lights": False, **{f"lights_g{g}": True for g in GROUPS}}, carried
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    over_beauty = {g: med[f"lights_g{g}"] / med["beauty"] for g in GROUPS}
+    wins = [g for g in GROUPS if over_beauty[g] < g + 2]
+    # grouped time / beauty time as a line through G = 1 and G = 8, against G + 2
+    slope = (over_beauty[GROUPS[-1]] - over_beauty[GROUPS[0]]) / (GROUPS[-1] - GROUPS[0])
+    at0 = over_beauty[GROUPS[0]] - slope * GROUPS[0]
+    return {"passes": n, "ms": {k: round(v, 3) for k, v in med.items()}, "ms_runs": {k: [round(x, 3) for x in v] for k, v in ms.items()},
+            "grouped_over_ungrouped": {str(g): med[f"lights_g{g}"] / med["lights"] for g in GROUPS},
+            "grouped_over_beauty": {str(g): over_beauty[g] for g in GROUPS}, "lights_over_beauty": med["lights"] / med["beauty"],
+            "renders_replaced": {str(g): g + 2 for g in GROUPS}, "smallest_measured_G_that_wins": wins[0] if wins else None,
+            "break_even_G_on_the_line_through_G1_and_G8": (at0 - 2) / (1 - slope) if slope < 1 else None}
+
+
+def view_groups(inst, name, sc):
+    """`name`: "outdoor", bench.py's headline view, which holds no emitter (every block pointer is dealt into the groups: what the walk
+    pays there is the fold of G more images), or "outdoor_emitters", the same world with 2 % of its surface cells glowing (one
+    emissive block pointer: the hit term, the table read and the per-sample sums run too)."""
+    ids = [int(p) for p in scenes.emitter_ids(sc)[0]]
+    emissive = len(ids)
+    if not ids:
+        ids = list(range(0, len(np.asarray(sc.block_palette)) - 1, 2))
+    loader, r = target(inst, sc)
+    # the grouped kernel folds the four images the ungrouped kernel folds, bit for bit, before anything is timed
+    check = native.java_random_ints(2)
+    r.render_lights(check)
+    plain = [r.read_light(w).tobytes() for w in range(4)]
+    same = True
+    for g in GROUPS:
+        r.set_emitter_groups(deal(ids, g), g)
+        r.reset_lights()
+        r.render_lights(check)
+        assert r.lights_info()["groups"]
+        same = same and [r.read_light(w).tobytes() for w in range(4)] == plain
+    lit = [bool(r.read_light_group(g).any()) for g in range(GROUPS[-1])]
+    r.set_emitter_groups({})
+    r.reset()
+    r.reset_lights()
+    r.kernel_time(), r.lights_time()
+    res = {"view": name, "width": sc.width, "height": sc.height, "four_images_equal_ungrouped": same, "emissive_block_pointers": emissive,
+           "groups_lit_at_G8": lit, "runs": [bench_groups(r, ids, n) for n in PASSES]}
+    for x in (r, loader):
+        x.close()
+    assert same, "the grouped call's four images differ from the ungrouped call's"
+    return res
+
+
+def main_groups(path):
+    inst = RendererInstance.get(0)
+    views = [view_groups(inst, "outdoor", scenes.cached_outdoor_world(chunks=32, height=256)),
+             view_groups(inst, "outdoor_emitters", scenes.cached_outdoor_world(chunks=32, height=256, emitters=0.02))]
+    res = {"device": inst.device_name(), "views": views,
+           "note": "measured once on one GPU; kernel time from HIP events; median of three alternating repeats on one target; "
+                   "G + 2 is what sky, sun and G group images cost as beauty renders"}
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "lights_bench.json"))
+    args = [a for a in sys.argv[1:] if a != "--groups"]
+    if "--groups" in sys.argv[1:]:
+        main_groups(args[0] if args else os.path.join(ROOT, "profiles", "lights_groups_bench.json"))
+    else:
+        main(args[0] if args else os.path.join(ROOT, "profiles", "lights_bench.json"))
