@@ -253,7 +253,7 @@ hipError_t launch_preview(int variant, const SceneView& S, const CameraView& C, 
 __global__ void __launch_bounds__(256) camera_rays_kernel(CameraView C, unsigned seed, float* __restrict__ out) {
     const int gid = (int)(blockIdx.x * 256 + threadIdx.x);
     if (gid >= C.width * C.height) return;
-    const RayOD r = projected_ray(C, seed, gid, gid % C.width, gid / C.width);
+    const RayOD r = projected_ray(C, seed, canvas_pixel(C, gid));
     float* o = out + 6 * (size_t)gid;
     o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z;
     o[3] = r.d.x; o[4] = r.d.y; o[5] = r.d.z;

@@ -32,7 +32,9 @@ RT_FN float rt_rad(float v) { return v * 0.0174532924f; }
 /* The ray of pixel (px, py) = (gid % width, gid / width) in the pass of seed `seed`, in world space.  s13 / s14 are settings[13] /
  * settings[14] of chunky_render_set_camera; pos and m as the pinhole camera's (ClCamera.java:42-52, m row-major); height is the
  * image's (the stacked ODS image changes eye at height / 2); aperture / focus are chunky_render_set_lens', aperture 0 = no lens:
- * nothing more is drawn and nothing below the projection runs. */
+ * nothing more is drawn and nothing below the projection runs.
+ * The image is the CANVAS (chunky_render_set_canvas, canvas_window.h): for a target that is a window of one, px, py and gid are the
+ * pixel's column, row and index on the canvas, and half_width, inv_height and height the canvas's. */
 RT_FN RtRay rt_projected_ray(int type, const float* pos, const float* m, float s13, float s14, float half_width, float inv_height,
                              int height, float aperture, float focus, int px, int py, unsigned seed, int gid) {
     unsigned j = (seed ^ RT_PROJ_JITTER_KEY) + (unsigned)gid;

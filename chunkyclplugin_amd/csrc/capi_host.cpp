@@ -8,6 +8,8 @@
 
 #include "../../include/chunky_hip.h"
 #include "camera_proj.h"
+#include "canvas_host.hpp"
+#include "canvas_window.h"
 #include "capi_error.hpp"
 #include "filter_alpha.h"
 #include "rt_math.h"
@@ -78,6 +80,28 @@ extern "C" int chunky_camera_rays_lens(int projector_type, const float* settings
         const RtRay r = rt_projected_ray(projector_type, settings, settings + 3, settings[13], settings[14], half_width, inv_height,
                                          height, aperture, focus, gid % width, gid / width, (unsigned)seed, gid);
         float* o = out + 6 * (size_t)gid;
+        o[0] = r.ox; o[1] = r.oy; o[2] = r.oz;
+        o[3] = r.dx; o[4] = r.dy; o[5] = r.dz;
+    }
+    return CHUNKY_OK;
+}
+
+// the same table for a window of a canvas (chunky_render_set_canvas): window pixel g is the canvas's pixel G — its jitter stream, its
+// column and row, the canvas's half_width, inv_height and height — stored at g
+extern "C" int chunky_camera_rays_window(int projector_type, const float* settings, int64_t n_floats, int width, int height, int canvas_width,
+                                         int canvas_height, int x0, int y0, int32_t seed, float aperture, float focus, float* out) {
+    if (int rc = check_canvas("camera_rays_window", width, height, canvas_width, canvas_height, x0, y0, projector_type)) return rc;
+    if (int rc = check_projected("camera_rays_window", projector_type, settings, n_floats, canvas_height)) return rc;
+    if (int rc = check_lens("camera_rays_window", aperture, focus)) return rc;
+    if ((int64_t)width * height > INT32_MAX / 6) return fail(CHUNKY_E_INVALID, "camera_rays_window: bad size %dx%d", width, height);
+    if (!out) return fail(CHUNKY_E_INVALID, "camera_rays_window: NULL output");
+    const float half_width = (float)(canvas_width / (2.0 * canvas_height)), inv_height = (float)(1.0 / canvas_height);  // as set_camera
+    const RtWindow w = rt_make_window(width, canvas_width, canvas_height, x0, y0);
+    for (int g = 0; g < width * height; g++) {
+        const RtCanvasPixel p = rt_canvas_pixel(g, g % width, g / width, w.x0, w.y0, w.row_skip, w.gid0);
+        const RtRay r = rt_projected_ray(projector_type, settings, settings + 3, settings[13], settings[14], half_width, inv_height,
+                                         w.canvas_height, aperture, focus, p.X, p.Y, (unsigned)seed, p.G);
+        float* o = out + 6 * (size_t)g;
         o[0] = r.ox; o[1] = r.oy; o[2] = r.oz;
         o[3] = r.dx; o[4] = r.dy; o[5] = r.dz;
     }

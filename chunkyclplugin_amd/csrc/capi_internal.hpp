@@ -19,6 +19,7 @@
 
 #include "../../include/chunky_hip.h"
 #include "capi_error.hpp"
+#include "canvas_host.hpp"
 #include "capi_host.hpp"
 #include "kernels.hpp"
 #include "lights_host.hpp"
@@ -151,6 +152,8 @@ struct chunky_render {
     chunky_ctx* ctx = nullptr;
     chunky_scene* scene = nullptr;
     int width = 0, height = 0;
+    // chunky_render_set_canvas: the canvas this target is a window of (0 x 0: none, the target is its own canvas) and the window's corner
+    int canvas_width = 0, canvas_height = 0, canvas_x0 = 0, canvas_y0 = 0;
     CameraView cam{};
     bool have_camera = false;
     DevBuf rays;

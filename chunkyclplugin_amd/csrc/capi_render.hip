@@ -96,15 +96,56 @@ extern "C" int chunky_render_destroy(chunky_render* r) {
     return CHUNKY_OK;
 }
 
+// the frame-dependent words of r's camera, from r's window (the identity while none is set): the target's own size, the CANVAS's
+// two floats (the expressions of K/rayTracer.cl:66-67 on the canvas's dimensions) and the window's fields (canvas_window.h)
+static void apply_canvas(chunky_render* r) {
+    CameraView& c = r->cam;
+    const int cw = r->canvas_width ? r->canvas_width : r->width, ch = r->canvas_height ? r->canvas_height : r->height;
+    c.width = r->width;
+    c.height = r->height;
+    c.half_width = (float)(cw / (2.0 * ch));  // K/rayTracer.cl:66
+    c.inv_height = (float)(1.0 / ch);         // K/rayTracer.cl:67
+    const RtWindow w = rt_make_window(r->width, cw, ch, r->canvas_x0, r->canvas_y0);
+    c.x0 = w.x0, c.y0 = w.y0, c.row_skip = w.row_skip, c.gid0 = w.gid0, c.canvas_height = w.canvas_height;
+}
+
+extern "C" int chunky_render_set_canvas(chunky_render* r, int canvas_width, int canvas_height, int x0, int y0) {
+    if (r && !r->parts.empty()) {
+        // every member or none: the checks are the same on each (one size, one camera), so the group's own copy is checked first
+        std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
+        if (int rc = check_canvas("set_canvas", r->width, r->height, canvas_width, canvas_height, x0, y0, r->parts[0]->have_camera ? r->parts[0]->cam.projector_type : 0))
+            return rc;
+        return each_part(r, [&](chunky_render* m_) { return chunky_render_set_canvas(m_, canvas_width, canvas_height, x0, y0); });
+    }
+    LOCK_RENDER(r);
+    if (int rc = check_canvas("set_canvas", r->width, r->height, canvas_width, canvas_height, x0, y0, r->have_camera ? r->cam.projector_type : 0)) return rc;
+    const bool identity = canvas_width == r->width && canvas_height == r->height;  // (inside the canvas: the offsets are 0)
+    r->canvas_width = identity ? 0 : canvas_width;
+    r->canvas_height = identity ? 0 : canvas_height;
+    r->canvas_x0 = x0, r->canvas_y0 = y0;
+    apply_canvas(r);  // (the camera travels by value in the kernel arguments: launches already queued keep the window they had)
+    r->ad_resumable = false;  // what a pass renders changes: an adaptive run cannot continue across it
+    return CHUNKY_OK;
+}
+
+extern "C" int chunky_render_canvas(chunky_render* r, int32_t out4[4]) {
+    if (r && !r->parts.empty()) {
+        std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
+        return chunky_render_canvas(r->parts[0], out4);
+    }
+    LOCK_RENDER(r);
+    if (!out4) return fail(CHUNKY_E_INVALID, "render_canvas: NULL output");
+    out4[0] = r->canvas_width ? r->canvas_width : r->width;
+    out4[1] = r->canvas_height ? r->canvas_height : r->height;
+    out4[2] = r->canvas_x0, out4[3] = r->canvas_y0;
+    return CHUNKY_OK;
+}
+
 extern "C" int chunky_render_set_camera(chunky_render* r, int projector_type, const float* settings, int64_t n) {
     FAN_RENDER(r, chunky_render_set_camera(m_, projector_type, settings, n));
     LOCK_RENDER(r);
     if (!settings) return fail(CHUNKY_E_INVALID, "set_camera: NULL settings");
     CameraView& c = r->cam;
-    c.width = r->width;
-    c.height = r->height;
-    c.half_width = (float)(r->width / (2.0 * r->height));  // K/rayTracer.cl:66
-    c.inv_height = (float)(1.0 / r->height);               // K/rayTracer.cl:67
     if (projector_type == 0) {
         if (n != 15) return fail(CHUNKY_E_INVALID, "set_camera: pinhole needs 15 floats, got %lld", (long long)n);
         memcpy(c.pos, settings, 12);
@@ -121,7 +162,7 @@ extern "C" int chunky_render_set_camera(chunky_render* r, int projector_type, co
         HIP_TRY(r->rays.upload(settings, (size_t)n * 4, r->ctx->stream));
         c.rays = (const float*)r->rays.p;
     } else if (is_projected_type(projector_type)) {
-        if (int rc = check_projected("set_camera", projector_type, settings, n, r->height)) return rc;
+        if (int rc = check_projected("set_camera", projector_type, settings, n, r->canvas_height ? r->canvas_height : r->height)) return rc;
         memcpy(c.pos, settings, 12);
         memcpy(c.m, settings + 3, 36);
         c.aperture = 0.0f;  // no lens until chunky_render_set_lens
@@ -131,6 +172,7 @@ extern "C" int chunky_render_set_camera(chunky_render* r, int projector_type, co
     } else {
         return fail(CHUNKY_E_INVALID, "set_camera: projector type %d is not supported (-1 to 5, 7, 8)", projector_type);
     }
+    apply_canvas(r);  // (behind every check: a refused call leaves the camera as it was)
     c.lens_focus = 0.0f;
     c.projector_type = projector_type;
     r->have_camera = true;

@@ -94,9 +94,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Fold::
             for (int k = 0; k < n_passes; k++) {
                 auto b = first_hit_args<typename Fold::Out>();
                 const unsigned seed = (unsigned)b->P.seed[k];
-                unsigned rng = seed + (unsigned)gid;  // K/rayTracer.cl:54-56
+                const CameraView C = arg_copy(&b->C);
+                const CanvasPixel cp = canvas_pixel(C, gid, px, py);
+                unsigned rng = seed + (unsigned)cp.G;  // K/rayTracer.cl:54-56
                 rt_pcg_next(&rng);
-                const RayOD r = primary_ray<PROJ>(arg_copy(&b->C), seed, gid, rng, false, px, py);
+                const RayOD r = primary_ray<PROJ>(C, seed, gid, cp, rng, false);
                 Hit h;
                 h.distance = rt_inf();
                 h.material = 0;

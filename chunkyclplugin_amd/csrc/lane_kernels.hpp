@@ -58,14 +58,17 @@ __global__ void __launch_bounds__(256) preview_lanes(CHUNKY_KERNEL_ARGS_HEAD Sce
     int gid = blockIdx.x * blockDim.x + threadIdx.x;
     int W = C.width, H = C.height;
     if (gid >= W * H) return;
-    int px = gid % W, py = gid / W;
+    // the crosshair is the canvas's (K/rayTracer.cl:146-150 on the canvas pixel and the canvas's size; a target that is no window: its own)
+    const CanvasPixel cp = canvas_pixel(C, gid);
+    const int px = cp.X, py = cp.Y;
+    W += C.row_skip, H = C.canvas_height;
     if ((px == W / 2 && (py >= H / 2 - 5 && py <= H / 2 + 5)) || (py == H / 2 && (px >= W / 2 - 5 && px <= W / 2 + 5))) {
         argb[gid] = (int)0xFFFFFFFFu;
         return;
     }
     unsigned rng = 0;
     rt_pcg_next(&rng);
-    const RayOD pr = primary_ray_any(C, 0u, gid, rng, true);  // a projected camera: the rays of seed 0
+    const RayOD pr = primary_ray_any(C, 0u, gid, cp, rng, true);  // a projected camera: the rays of seed 0
     const f3 o = pr.o, d = pr.d;
     Hit h;
     h.distance = rt_inf();

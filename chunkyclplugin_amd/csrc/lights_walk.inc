@@ -34,9 +34,11 @@
             if (start) {  // K/rayTracer.cl:54-91
                 auto b = first_hit_args<LightOut>();
                 const unsigned seed = (unsigned)b->P.seed[k];
-                rng = seed + (unsigned)gid;
+                const CameraView C = arg_copy(&b->C);
+                const CanvasPixel cp = canvas_pixel(C, gid, px, py);
+                rng = seed + (unsigned)cp.G;
                 rt_pcg_next(&rng);
-                const RayOD r = primary_ray<PROJ>(arg_copy(&b->C), seed, gid, rng, false, px, py);
+                const RayOD r = primary_ray<PROJ>(C, seed, gid, cp, rng, false);
                 o = r.o, d = r.d;
                 reach = rt_inf();
                 step = 0, tn = mk3(0, 0, 0);

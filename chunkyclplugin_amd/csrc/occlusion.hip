@@ -100,9 +100,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(occlus
             if (start) {  // K/rayTracer.cl:54-91
                 auto b = first_hit_args<OcclusionOut>();
                 const unsigned seed = (unsigned)b->P.seed[k];
-                rng = seed + (unsigned)gid;
+                const CameraView C = arg_copy(&b->C);
+                const CanvasPixel cp = canvas_pixel(C, gid, px, py);
+                rng = seed + (unsigned)cp.G;
                 rt_pcg_next(&rng);
-                const RayOD r = primary_ray<PROJ>(arg_copy(&b->C), seed, gid, rng, false, px, py);
+                const RayOD r = primary_ray<PROJ>(C, seed, gid, cp, rng, false);
                 o = r.o, d = r.d;
                 reach = rt_inf();
             }

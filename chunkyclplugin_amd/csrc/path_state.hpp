@@ -163,9 +163,10 @@ DEV void put_record(HitRecord* out, int& n, bool hit, const Hit& h, f3 point) {
 template <bool RECORD, int TREE>
 DEV f3 sample_path(const SceneView& S, const CameraView& C, const RenderOpts& O, int seed, int gid, LdsStack& stack,
                    HitRecord* rec_out, int* rec_n) {
-    unsigned rng = (unsigned)seed + (unsigned)gid;
+    const CanvasPixel cp = canvas_pixel(C, gid);
+    unsigned rng = (unsigned)seed + (unsigned)cp.G;
     rt_pcg_next(&rng);
-    const RayOD pr = primary_ray_any(C, (unsigned)seed, gid, rng, false);
+    const RayOD pr = primary_ray_any(C, (unsigned)seed, gid, cp, rng, false);
     f3 o = pr.o, d = pr.d;
     f3 radiance = mk3(0, 0, 0), throughput = mk3(1, 1, 1);
     Hit h;
@@ -612,6 +613,8 @@ DEV SampleArgs sample_args(WaveArgPtr A) {
     for (int k = 0; k < 9; k++) pin_scalar(N.C.m[k]);
     pin_scalar(N.C.subject_distance), pin_scalar(N.C.fov_tan), pin_scalar(N.C.width), pin_scalar(N.C.height);
     pin_scalar(N.C.half_width), pin_scalar(N.C.inv_height);
+    pin_scalar(N.C.x0), pin_scalar(N.C.y0), pin_scalar(N.C.row_skip), pin_scalar(N.C.gid0);  // the window (canvas_pixel)
+    if (PROJ) pin_scalar(N.C.canvas_height);
     pin_scalar(N.T.rank), pin_scalar(N.T.world), pin_scalar(N.T.tile), pin_scalar(N.T.n_local), N.T.list = pin_pointer(N.T.list);
     N.next = pin_pointer(N.next), N.staging = pin_pointer(N.staging), pin_scalar(N.n_samples), pin_scalar(N.xcd_stripe);
     pin_scalar(N.div_sub.m), pin_scalar(N.div_sub.s), pin_scalar(N.div_bw.m), pin_scalar(N.div_bw.s);

@@ -317,9 +317,10 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
                     const SlotPixel px = pool_slot_pixel(N.T, N.C.width, N.C.height, slot, N.div_bw);
                     const int gid = px.gid;
                     if (gid < N.C.width * N.C.height) {  // else: a padding slot, nothing to render (the lane claims again)
-                        unsigned rng = seed + (unsigned)gid;
+                        const CanvasPixel cp = canvas_pixel(N.C, gid, px.x, px.y);  // (the identity unless the target is a window)
+                        unsigned rng = seed + (unsigned)cp.G;
                         rt_pcg_next(&rng);
-                        const RayOD pr = primary_ray<CHUNKY_POOL_PROJ>(N.C, seed, gid, rng, false, px.x, px.y);
+                        const RayOD pr = primary_ray<CHUNKY_POOL_PROJ>(N.C, seed, gid, cp, rng, false);
                         L.sidx = (int)sidx;
                         L.rng = rng;
                         L.o = pr.o;

@@ -208,9 +208,10 @@ DEV int next_sample_single(const SceneView& S, const CameraView& C, const ShardV
     {
         // locals, not struct members, as out-parameters: keeps LaneState promotable to registers
         const unsigned seed = (unsigned)A->P.seed[L.pass];  // per-lane index: a vector load from the argument segment
-        unsigned rng = seed + (unsigned)L.gid;
+        const CanvasPixel cp = canvas_pixel(C, L.gid);
+        unsigned rng = seed + (unsigned)cp.G;
         rt_pcg_next(&rng);
-        const RayOD pr = primary_ray_any(C, seed, L.gid, rng, false);
+        const RayOD pr = primary_ray_any(C, seed, L.gid, cp, rng, false);
         L.rng = rng;
         L.o = pr.o;
         L.d = pr.d;
@@ -346,9 +347,10 @@ DEV int next_sample(const SceneView& S, const CameraView& C, const ShardView& T,
     {
         // locals, not struct members, as out-parameters: keeps LaneState promotable to registers
         const unsigned seed = (unsigned)A->P.seed[L.pass];  // per-lane index: a vector load from the argument segment
-        unsigned rng = seed + (unsigned)gid;
+        const CanvasPixel cp = canvas_pixel(C, gid);
+        unsigned rng = seed + (unsigned)cp.G;
         rt_pcg_next(&rng);
-        const RayOD pr = primary_ray_any(C, seed, gid, rng, false);
+        const RayOD pr = primary_ray_any(C, seed, gid, cp, rng, false);
         L.rng = rng;
         L.o = pr.o;
         L.d = pr.d;

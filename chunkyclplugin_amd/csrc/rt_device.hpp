@@ -14,6 +14,7 @@
 
 #include "rt_math.h"
 #include "camera_proj.h"
+#include "canvas_window.h"
 #include "addr32.h"
 #include "launch_plan.hpp"  // RenderOpts, SceneFacts
 
@@ -130,7 +131,20 @@ struct CameraView {
     int width, height;
     float half_width, inv_height;    // K/rayTracer.cl:66-67 (double sites, rounded once on the host)
     float lens_focus;                // projected types: the lens's focus distance (chunky_render_set_lens); nothing else reads it
+    // The target as a window of a larger canvas (chunky_render_set_canvas, canvas_window.h): width and height
+    // above stay the target's own, half_width and inv_height are the canvas's, and these five words carry a window pixel to its
+    // canvas pixel (canvas_pixel below).  The identity — the default — is x0 = y0 = row_skip = gid0 = 0, canvas_height = height.
+    int x0, y0;         // the window's corner
+    int row_skip;       // canvas_width - width
+    int gid0;           // y0 * canvas_width + x0
+    int canvas_height;  // projected types: the stacked ODS image changes eye at canvas_height / 2
 };
+
+// Where the sample stored at local index g = py * C.width + px lies on the canvas: G seeds its RNG streams, (X, Y) go through the
+// camera.  Everything else about a pixel (its slot, its place in a table of pre-generated rays, its images) stays g.
+typedef RtCanvasPixel CanvasPixel;
+DEV CanvasPixel canvas_pixel(const CameraView& C, int g, int px, int py) { return rt_canvas_pixel(g, px, py, C.x0, C.y0, C.row_skip, C.gid0); }
+DEV CanvasPixel canvas_pixel(const CameraView& C, int g) { return canvas_pixel(C, g, g % C.width, g / C.width); }
 
 // (RenderOpts, the other kernel argument, lives in launch_plan.hpp: the launch planner reads it too)
 
@@ -829,7 +843,7 @@ struct RayOD {
 };
 // Returned by value through scalars (ox..dz each assigned once per branch): out-parameters written
 // in both branches end up as a select between two addresses, which keeps them in scratch memory.
-// (px, py) = (gid % width, gid / width): callers that know the pixel's column and row pass them and save the two divisions
+// gid: the pixel's local index (its place in a table of pre-generated rays); (px, py): its column and row ON THE CANVAS (canvas_pixel)
 DEV RayOD primary_ray(const CameraView& C, int gid, unsigned& rng, bool unit_dir, int px, int py) {
     float ox, oy, oz, dx, dy, dz;
     if (C.projector_type != -1) {
@@ -871,23 +885,23 @@ DEV RayOD primary_ray(const CameraView& C, int gid, unsigned& rng, bool unit_dir
 // It draws nothing from the path's state and does not take the preview's extra normalize (the projection normalises already,
 // and the reference preview does not normalise pre-generated rays).  settings[13] / [14] travel in subject_distance / fov_tan, the
 // lens (a uniform branch on aperture > 0) in aperture / lens_focus.
-DEV RayOD projected_ray(const CameraView& C, unsigned seed, int gid, int px, int py) {
-    const RtRay r = rt_projected_ray(C.projector_type, C.pos, C.m, C.subject_distance, C.fov_tan, C.half_width, C.inv_height, C.height,
-                                     C.aperture, C.lens_focus, px, py, seed, gid);
+// P: the sample's canvas pixel (its index keys the jitter stream).
+DEV RayOD projected_ray(const CameraView& C, unsigned seed, CanvasPixel P) {
+    const RtRay r = rt_projected_ray(C.projector_type, C.pos, C.m, C.subject_distance, C.fov_tan, C.half_width, C.inv_height, C.canvas_height,
+                                     C.aperture, C.lens_focus, P.X, P.Y, seed, P.G);
     return RayOD{mk3(r.ox, r.oy, r.oz), mk3(r.dx, r.dy, r.dz)};
 }
 // PROJ: a compile-time choice of the kernels whose registers are budgeted (render_pool, first_hit_kernel): their pinhole / pre-generated
 // instantiations compile exactly the code above
 template <bool PROJ>
-DEV RayOD primary_ray(const CameraView& C, unsigned seed, int gid, unsigned& rng, bool unit_dir, int px, int py) {
-    if (PROJ) return projected_ray(C, seed, gid, px, py);
-    return primary_ray(C, gid, rng, unit_dir, px, py);
+DEV RayOD primary_ray(const CameraView& C, unsigned seed, int gid, CanvasPixel P, unsigned& rng, bool unit_dir) {
+    if (PROJ) return projected_ray(C, seed, P);
+    return primary_ray(C, gid, rng, unit_dir, P.X, P.Y);
 }
 // the other kernels (fallbacks, preview, trace records): a uniform branch on the projector type
-DEV RayOD primary_ray_any(const CameraView& C, unsigned seed, int gid, unsigned& rng, bool unit_dir) {
-    const int px = gid % C.width, py = gid / C.width;
-    if (C.projector_type > 0) return projected_ray(C, seed, gid, px, py);
-    return primary_ray(C, gid, rng, unit_dir, px, py);
+DEV RayOD primary_ray_any(const CameraView& C, unsigned seed, int gid, CanvasPixel P, unsigned& rng, bool unit_dir) {
+    if (C.projector_type > 0) return projected_ray(C, seed, P);
+    return primary_ray(C, gid, rng, unit_dir, P.X, P.Y);
 }
 
 }  // namespace chunky

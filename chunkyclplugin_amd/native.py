@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("CHUNKY_HIP_LIB") or os.path.join(PKG_DIR, "libchunky_
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
 SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_pool_biome.hip", "render_pool_biome_bvh.hip", "render_biome.hip", "aov_biome.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "lights.hip", "lights_groups.hip", "matte.hip", "denoise.hip", "adaptive.hip",
            "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_occlusion.hip", "capi_lights.hip", "capi_matte.hip", "capi_adaptive.hip", "capi_denoise.hip",
-           "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp", "lights_host.cpp",
+           "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "canvas_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp", "lights_host.cpp",
            "scene_records.cpp", "widetree.cpp", "launch_plan.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
 
@@ -295,6 +295,11 @@ def lib() -> C.CDLL:
             "chunky_selftest_shard_map": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp],
             "chunky_camera_rays": [C.c_int, vp, i64, C.c_int, C.c_int, i32, vp],
             "chunky_camera_rays_lens": [C.c_int, vp, i64, C.c_int, C.c_int, i32, f32, f32, vp],
+            "chunky_camera_rays_window": [C.c_int, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32, f32, f32, vp],
+            "chunky_render_set_canvas": [vp, C.c_int, C.c_int, C.c_int, C.c_int],
+            "chunky_render_canvas": [vp, vp],
+            "chunky_canvas_check": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+            "chunky_selftest_canvas_pixel": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32, vp],
             "chunky_filter_frame": [vp, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int],
             "chunky_filter_frame_alpha": [vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, C.c_int],
             "chunky_filter_alpha_bytes": [vp, i64, vp],
@@ -309,7 +314,7 @@ def lib() -> C.CDLL:
         }
         for name, args in sig.items():
             if not hasattr(L, name) and os.environ.get("CHUNKY_HIP_LIB") and os.environ.get("CHUNKY_HIP_LIB_EARLIER") == "1":
-                continue  # only tools/adaptive_bench.py --resume-legs sets this, for the child that times an earlier commit's build: what that lacks stays unbound
+                continue  # only tools/adaptive_bench.py --resume-legs and tools/headline_ab.py set this, for the child that times an earlier commit's build: what that lacks stays unbound
             fn = getattr(L, name)
             fn.argtypes = args
             fn.restype = C.c_int
@@ -344,6 +349,31 @@ def camera_rays(projector_type: int, settings, width: int, height: int, seed: in
     else:
         check(lib().chunky_camera_rays_lens(int(projector_type), ptr(s), s.size, int(width), int(height), seed32, float(lens[0]), float(lens[1]), ptr(out)))
     return out
+
+
+def camera_rays_window(projector_type: int, settings, width: int, height: int, canvas_width: int, canvas_height: int, x0: int, y0: int,
+                       seed: int, lens=None) -> np.ndarray:
+    """chunky_camera_rays_window: the width*height*6-float table of the WINDOW at (x0, y0) of a canvas_width x canvas_height canvas
+    (chunky_render_set_canvas) — the crop of camera_rays on the canvas, computed for the window's pixels alone.  Host only."""
+    s = np.ascontiguousarray(settings, np.float32)
+    out = np.zeros(max(int(width), 0) * max(int(height), 0) * 6, np.float32)
+    seed32 = int(np.int32(np.uint32(seed & 0xFFFFFFFF)))
+    a, f = (0.0, 0.0) if lens is None else (float(lens[0]), float(lens[1]))
+    check(lib().chunky_camera_rays_window(int(projector_type), ptr(s), s.size, int(width), int(height), int(canvas_width), int(canvas_height),
+                                          int(x0), int(y0), seed32, a, f, ptr(out)))
+    return out
+
+
+def canvas_check(width: int, height: int, canvas_width: int, canvas_height: int, x0: int, y0: int, projector_type: int = 0) -> int:
+    """chunky_canvas_check: chunky_render_set_canvas' own test of a window, without a target or a device; the status code (0 = accepted)."""
+    return int(lib().chunky_canvas_check(int(width), int(height), int(canvas_width), int(canvas_height), int(x0), int(y0), int(projector_type)))
+
+
+def canvas_pixel(width: int, height: int, canvas_width: int, canvas_height: int, x0: int, y0: int, g: int):
+    """chunky_selftest_canvas_pixel: (G, X, Y) of the window's local index g, by the helper the kernels use."""
+    out = np.zeros(3, np.int32)
+    check(lib().chunky_selftest_canvas_pixel(int(width), int(height), int(canvas_width), int(canvas_height), int(x0), int(y0), int(g), ptr(out)))
+    return tuple(int(v) for v in out)
 
 
 def filter_alpha_bytes(alpha) -> np.ndarray:

@@ -276,6 +276,18 @@ class HipPathTracingRenderer:
         `aperture` in focus at distance `focus`; aperture 0 switches it off.  set_camera clears the lens."""
         check(native.lib().chunky_render_set_lens(self._h, float(aperture), float(focus)))
 
+    def set_canvas(self, canvas_width: int, canvas_height: int, x0: int = 0, y0: int = 0) -> None:
+        """chunky_render_set_canvas: this target is the window at (x0, y0) of a canvas_width x canvas_height canvas — it stores, per
+        pixel, exactly what a target of the canvas's size stores at that canvas pixel.  canvas == target at (0, 0) switches the
+        window off.  It touches no image: reset() (and the other passes' resets) before rendering another window."""
+        check(native.lib().chunky_render_set_canvas(self._h, int(canvas_width), int(canvas_height), int(x0), int(y0)))
+
+    def canvas(self):
+        """chunky_render_canvas: (canvas_width, canvas_height, x0, y0)."""
+        out = np.zeros(4, np.int32)
+        check(native.lib().chunky_render_canvas(self._h, ptr(out)))
+        return tuple(int(v) for v in out)
+
     def camera_rays(self, seed: int) -> np.ndarray:
         """Self test of a projected camera (types 1-5, 7, 8, with its lens if one is set): the rays the render kernels compute for the pass of `seed`, every pixel,
         width*height*6 floats as camera_rays() lays them out."""
@@ -705,6 +717,53 @@ class HipPathTracingRenderer:
         if self._h:
             check(native.lib().chunky_render_destroy(self._h))
             self._h = C.c_void_p()
+
+
+def render_tiled(scene_loader: HipSceneLoader, canvas_w: int, canvas_h: int, tile_w: int, tile_h: int, seeds, projector_type: int, settings,
+                 lens=None, options=None, x_cuts=None, y_cuts=None) -> np.ndarray:
+    """A canvas_w x canvas_h frame rendered window by window (chunky_render_set_canvas) and assembled: bit for bit the image one
+    target of the canvas's size renders from the same seeds.  The canvas is cut into a grid of tile_w x tile_h windows (the last
+    column and row smaller), or, with x_cuts / y_cuts, at those columns / rows; one render target per window size is created and
+    reused, reset between windows.  `lens` = (aperture, focus) for a projected camera, `options` = {option: value}.  A camera of
+    pre-generated rays (type -1) is not served: its table is per window.  Returns the canvas_h x canvas_w x 3 float32 image."""
+    if projector_type == native.PROJ_PREGENERATED:
+        raise ValueError("render_tiled: a table of pre-generated rays is per window; crop it and call set_canvas yourself")
+
+    def edges(total, step, cuts):
+        if cuts is None:
+            if step <= 0:
+                raise ValueError("render_tiled: tile size must be positive")
+            cuts = range(step, total, step)
+        e = [0] + sorted(set(int(c) for c in cuts)) + [total]
+        if any(b <= a for a, b in zip(e, e[1:])):
+            raise ValueError("render_tiled: cuts must lie strictly inside the canvas")
+        return e
+
+    xs, ys = edges(canvas_w, tile_w, x_cuts), edges(canvas_h, tile_h, y_cuts)
+    frame = np.zeros((canvas_h, canvas_w, 3), np.float32)
+    targets = {}
+    try:
+        for y0, y1 in zip(ys, ys[1:]):
+            for x0, x1 in zip(xs, xs[1:]):
+                w, h = x1 - x0, y1 - y0
+                r = targets.get((w, h))
+                if r is None:
+                    r = targets[(w, h)] = HipPathTracingRenderer(scene_loader, w, h)
+                    for k, v in (options or {}).items():
+                        r.set_option(k, v)
+                    r.set_canvas(canvas_w, canvas_h, x0, y0)  # (ahead of the camera: a stacked ODS camera is checked on the canvas's height)
+                    r.set_camera(projector_type, settings)
+                    if lens is not None:
+                        r.set_lens(*lens)
+                else:
+                    r.set_canvas(canvas_w, canvas_h, x0, y0)
+                    r.reset()
+                r.render_passes(seeds)
+                frame[y0:y1, x0:x1] = r.read().reshape(h, w, 3)
+    finally:
+        for r in targets.values():
+            r.close()
+    return frame
 
 
 class HipPostProcessingFilter:

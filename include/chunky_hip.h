@@ -269,6 +269,48 @@ int chunky_render_set_lens(chunky_render* r, float aperture, float focus);
 int chunky_camera_rays_lens(int projector_type, const float* settings, int64_t n_floats, int width, int height, int32_t seed,
                             float aperture, float focus, float* out);
 
+/* Canvas windows: a render target of width x height pixels may be declared the window at (x0, y0) of a canvas
+ * of canvas_width x canvas_height.  Window pixel (x, y), local index g = y * width + x, is canvas pixel (X, Y) = (x0 + x, y0 + y),
+ * canvas index G = Y * canvas_width + X.
+ *
+ * THE RULE.  The window target stores, at g, exactly what a canvas_width x canvas_height target with the same scene, camera, lens,
+ * options and seeds stores at G — in every image any call produces, bit for bit.  Per sample: the RNG state is seed + (unsigned)G,
+ * advanced once; the pinhole camera and the preview use half_width = (float)(canvas_width / (2.0 * canvas_height)), inv_height =
+ * (float)(1.0 / canvas_height) and (float)X, (float)Y (the offset is added to the integer, before the conversion); the projected
+ * cameras and their lens draw from ((uint)seed ^ 0x9E3779B9u) + (uint)G and read X, Y and the canvas's size (ODS_STACKED changes
+ * eye at canvas_height / 2 and needs an even canvas height); the preview's crosshair is the canvas's.  A table of pre-generated rays
+ * (type -1) stays window-sized, width * height * 6 floats read at g — the caller crops its table — while the RNG state still uses G.
+ * Everything else stays the target's own: buffer sizes and read-back counts, the 16 x 16 block map and chunky_render_set_shard, a
+ * group's split among its members, chunky_render_set_device_buffer, the gids of chunky_render_trace_records (local), matte planes.
+ * No call answers CHUNKY_E_STATE because a window is set.
+ *
+ * Two calls look at neighbouring pixels and so cannot equal a crop near the window's edge; they run as they are:
+ *   chunky_render_denoise / chunky_denoise_frame  the filter reaches as far as its A-Trous levels (2^iterations pixels): render the
+ *                                                 window with an apron that wide and crop after filtering
+ *   chunky_render_adaptive*                       the 3 x 3 activity neighbourhood is clipped to the window, so a pixel may stop at
+ *                                                 another pass count than on the canvas; every pixel's result is still
+ *                                                 chunky_render_passes(seeds[0 .. n_p)) of its canvas pixel
+ *
+ * chunky_render_set_canvas may be called before or after chunky_render_set_camera, and again at any time; canvas == target with
+ * offsets 0 is the default and switches the window off.  Launches already queued keep the window they were enqueued with (the
+ * camera travels by value).  It touches no image: a host that moves the window calls chunky_render_reset (and the other passes'
+ * reset functions) itself.  Like set_camera it reaches every member of a group and ends an adaptive run that could have been resumed.
+ *   CHUNKY_E_INVALID, nothing changed: a negative offset; a window that does not lie inside the canvas; canvas_width *
+ *   canvas_height > INT32_MAX (G is an int); an odd canvas_height while the camera is CHUNKY_PROJ_ODS_STACKED (set_camera checks the
+ *   same on the canvas's height, not the target's)
+ * chunky_render_canvas reports canvas_width, canvas_height, x0, y0.  chunky_canvas_check is set_canvas' test without a target or a
+ * device (projector_type: the camera's, 0 if none); chunky_selftest_canvas_pixel (a self test, like the other chunky_selftest_* entries) gives {G, X, Y} of local index g by the kernels' own helper.
+ * chunky_camera_rays_window is the host twin of a projected camera on a window: the width * height * 6 table of the WINDOW's pixels;
+ * with canvas == window and aperture 0 it returns chunky_camera_rays' bytes, with a lens chunky_camera_rays_lens'.
+ * The Java binding does not reach these calls. */
+int chunky_render_set_canvas(chunky_render* r, int canvas_width, int canvas_height, int x0, int y0);
+int chunky_render_canvas(chunky_render* r, int32_t out4[4]);
+int chunky_canvas_check(int width, int height, int canvas_width, int canvas_height, int x0, int y0, int projector_type);
+int chunky_selftest_canvas_pixel(int width, int height, int canvas_width, int canvas_height, int x0, int y0, int32_t g, int32_t out3[3]);
+int chunky_camera_rays_window(int projector_type, const float* settings, int64_t n_floats, int width, int height,
+                              int canvas_width, int canvas_height, int x0, int y0, int32_t seed,
+                              float aperture, float focus, float* out);
+
 typedef enum chunky_option {
     CHUNKY_OPT_DRAW_DEPTH = 0,      /* int, default 256  (K/rayTracer.cl:94) */
     CHUNKY_OPT_MAX_DEPTH = 1,       /* int >= 1, default 5 (K/rayTracer.cl:107); above 254 the fallback kernels run (render_pool marks a
