@@ -56,8 +56,11 @@ static int adaptive_launch(chunky_render* r, const SceneView& S, const ShardView
         ps.n = (n - done) < cap ? (n - done) : cap;
         ps.first_spp = first_spp + done;
         memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
-        HIP_TRY(launch_render_stats(r->kernel_variant, S, r->cam, r->opts, T, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream, &r->last_choice,
-                                    (float*)r->staging.p, nullptr, (float*)r->ad_stat.p));
+        StagedFold fold;
+        fold.kind = StagedFold::stats;
+        fold.stat_image = (float*)r->ad_stat.p;
+        HIP_TRY(launch_render_fold(r->kernel_variant, S, r->cam, r->opts, T, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream, &r->last_choice,
+                                   (float*)r->staging.p, nullptr, fold));
         done += ps.n;
     }
     return CHUNKY_OK;

@@ -28,8 +28,9 @@ extern "C" int chunky_denoise_frame(chunky_ctx* ctx, int width, int height, cons
     return CHUNKY_OK;
 }
 
-// on one device: r's framebuffer holds the whole image (a single-device target, or member 0 of a group after the exchange)
-static int render_denoise(chunky_render* r, const DnCoeffs& K, int form, float* out) {
+// on one device: `color` holds the whole image — r's framebuffer (a single-device target, or member 0 of a group after the exchange),
+// or the resolved image of chunky_render_robust_denoise
+int render_denoise(chunky_render* r, const DnCoeffs& K, int form, const float* color, float* out) {
     LOCK_RENDER(r);
     if (!r->aov.p) return fail(CHUNKY_E_STATE, "render_denoise before any AOV pass");
     const size_t bytes = aov_image_bytes(r), need = denoise_work_bytes(r->width, r->height);
@@ -43,7 +44,7 @@ static int render_denoise(chunky_render* r, const DnCoeffs& K, int form, float* 
     const float* normal = (const float*)((const char*)r->aov.p + bytes);
     int launches = 0;
     if (int rc = r->dn_clock.open(r->ctx->stream)) return rc;
-    HIP_TRY(launch_denoise(form, r->width, r->height, r->fb, albedo, normal, K, (float*)r->dn_out.p, r->dn_work.p, r->dn_work.bytes, r->ctx->stream, &launches));
+    HIP_TRY(launch_denoise(form, r->width, r->height, color, albedo, normal, K, (float*)r->dn_out.p, r->dn_work.p, r->dn_work.bytes, r->ctx->stream, &launches));
     if (int rc = r->dn_clock.close(r->ctx->stream, launches)) return rc;
     const int64_t n = (int64_t)(bytes / 4);  // (checked against the caller's count by chunky_render_denoise)
     return read_floats("render_denoise", r, r->dn_out.p, out, n, n);
@@ -60,10 +61,10 @@ extern "C" int chunky_render_denoise(chunky_render* r, const chunky_denoise_para
     std::lock_guard<std::recursive_mutex> g(r->ctx->mu);
     const ShardView& share = r->parts.empty() ? r->shard : r->outer;
     if (share.world > 1) return fail(CHUNKY_E_STATE, "render_denoise: this target holds rank %d of %d of the image, not all of it", share.rank, share.world);
-    if (r->parts.empty()) return render_denoise(r, K, form, out);
+    if (r->parts.empty()) return render_denoise(r, K, form, r->fb, out);
     if (!r->parts[0]->aov.p) return fail(CHUNKY_E_STATE, "render_denoise before any AOV pass");
     if (int rc = group_gather(r)) return rc;  // member 0's buffer then holds the whole image (chunky_render_read's exchange)
-    return render_denoise(r->parts[0], K, form, out);
+    return render_denoise(r->parts[0], K, form, r->parts[0]->fb, out);
 }
 
 extern "C" int chunky_render_denoise_kernel_time(chunky_render* r, float* total_ms, int* launches) {

@@ -228,6 +228,13 @@ struct chunky_render {
     chunky_adaptive_state ad_state{};
     bool ad_resumable = false;
     LaunchClock ad_clock{&free_events};  // one bracket per round
+    // chunky_render_robust_*: rb_m bucket images [bucket][pixel][3] (0: no state) and the robust samples folded into them since
+    // chunky_render_robust_begin; the resolved image and the trim bytes on their way to the host or to the denoiser, allocated by the
+    // first resolve.  Its timing is kept apart from the other launches': one clock for the passes, one for the resolves
+    DevBuf rb_buckets, rb_out, rb_trim;
+    int rb_m = 0;
+    int32_t rb_count = 0;
+    LaunchClock rb_clock{&free_events}, rb_resolve_clock{&free_events};
     ~chunky_render() {
         if (ad_total_host) (void)hipHostFree(ad_total_host);
         for (auto e : free_events) (void)hipEventDestroy(e);
@@ -323,4 +330,6 @@ int read_floats(const char* who, chunky_render* r, const void* src, void* out, i
 int first_hit_kernel_time(chunky_render* r, FirstHitPass chunky_render::*pass, float* total_ms, int* launches);  // capi_aov.hip
 int first_hit_kernel_info(const char* who, chunky_render* r, FirstHitPass chunky_render::*pass, int32_t out4[4]);
 int device_gamma_table(chunky_ctx* ctx, const float** out);                             // capi_filter.hip
+// the denoiser on r's device with r's own AOV images: `color` (3 * width * height floats on that device) filtered into `out` on the host
+int render_denoise(chunky_render* r, const DnCoeffs& K, int form, const float* color, float* out);  // capi_denoise.hip
 #pragma GCC visibility pop

@@ -90,12 +90,24 @@ inline hipError_t persistent_grid(Kernel k, int block, size_t lds, long long wan
 hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                          const PassSeeds& P, float* res, int* work_counter, hipStream_t stream,
                          KernelChoice* chosen = nullptr, float* staging = nullptr, const int* seeds_dev = nullptr);
-// launch_render with the launch's samples folded by fold_stats_kernel (adaptive.hip) in place of fold_kernel: fold_stats holds two
-// floats per pixel of the image, the luminance statistic that kernel updates beside the running mean.  render_pool only
-// (hipErrorNotSupported under the other kernels, which stage no samples); fold_stats == nullptr is launch_render.
-hipError_t launch_render_stats(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
-                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
-                               float* staging, const int* seeds_dev, float* fold_stats);
+// What folds the staged samples of a render_pool launch into the target's images, besides fold_kernel's running mean into `res`
+// (which every kind keeps, operation for operation):
+//   none     fold_kernel alone: launch_render
+//   stats    fold_stats_kernel (adaptive.hip): stat_image holds two floats per pixel of the image, the luminance statistic
+//   buckets  fold_buckets_kernel<n_buckets> (robust.hip): bucket_images holds n_buckets images [bucket][pixel][3]; the launch's first
+//            sample is robust sample `first_index` (robust_spec.h)
+struct StagedFold {
+    enum Kind : int { none = 0, stats = 1, buckets = 2 } kind = none;
+    float* stat_image = nullptr;
+    float* bucket_images = nullptr;
+    int n_buckets = 0;
+    int first_index = 0;
+};
+// launch_render with the launch's samples folded as `fold` says.  A fold other than `none` is render_pool's only
+// (hipErrorNotSupported under the other kernels, which stage no samples); kind == none is launch_render.
+hipError_t launch_render_fold(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
+                              const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
+                              float* staging, const int* seeds_dev, const StagedFold& fold);
 // the kernels behind render_pool (render_fallback.hip): render_waves, render_lanes, as `plan` names them
 hipError_t launch_fallback(const RenderPlan& plan, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                            const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen);
@@ -206,6 +218,16 @@ hipError_t launch_adaptive_rebuild(int width, int height, unsigned char* active,
                                    hipStream_t stream);
 // pixels still active record n
 hipError_t launch_adaptive_finish(int n_pixels, const unsigned char* active, int* count, int n, hipStream_t stream);
+// Firefly-robust accumulation (robust.hip; specification: robust_spec.h).
+// fold_kernel's running mean over the staged samples of n_tiles tiles of shard T, and the update of the n_buckets bucket means
+// (buckets: [bucket][pixel][3]) for robust samples first_index ..; hipErrorInvalidValue for a bucket count the specification does not take
+hipError_t launch_fold_buckets(const float* staging, float* res, float* buckets, int n_buckets, int first_index, const ShardView& T, int width,
+                               int height, long long n_tiles, int n_passes, int first_spp, hipStream_t stream);
+// the resolve of every pixel: out 3 * n_pixels floats, trim n_pixels bytes or null; mode RB_MODE_*
+hipError_t launch_robust_resolve(const float* buckets, int n_buckets, long long n_pixels, int mode, float gain, float* out, unsigned char* trim,
+                                 hipStream_t stream);
+// self test: samples [pass][pixel][3] into the staging layout of the whole image (staging zeroed by the caller: padding slots stay 0)
+hipError_t launch_robust_stage(const float* samples, float* staging, int width, int height, long long n_tiles, int n_passes, hipStream_t stream);
 // thresholds: 256 floats on the device (capi_host.cpp gamma_thresholds) or null = evaluate pow per channel
 hipError_t launch_filter(long long n_pixels, float exposure, const double* in, unsigned* out, int type, hipStream_t stream,
                          const float* thresholds = nullptr);

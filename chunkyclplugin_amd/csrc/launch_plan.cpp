@@ -149,7 +149,7 @@ static void plan_fallback(RenderPlan& p, int variant, const SceneFacts& F, int n
 }
 
 RenderPlan plan_render(int variant, const SceneFacts& F, const RenderOpts& O, int projector_type, const ShardView& T, int n_passes,
-                       bool have_queue_and_staging, bool have_seeds_dev, bool want_fold_stats) {
+                       bool have_queue_and_staging, bool have_seeds_dev, bool want_staged_fold) {
     RenderPlan p{};
     p.why = why_not_pool(variant, F, O, have_queue_and_staging);
     p.ext_refusal = ext_refusal(variant, F, O, p.why);
@@ -163,7 +163,7 @@ RenderPlan plan_render(int variant, const SceneFacts& F, const RenderOpts& O, in
     p.status = PlanStatus::ok;
     if (pool) {
         if (n_passes > kMaxPoolPasses || (n_passes > kMaxPassesPerLaunch && !have_seeds_dev)) p.status = PlanStatus::invalid_value;
-    } else if (want_fold_stats) {
+    } else if (want_staged_fold) {
         p.status = PlanStatus::not_supported;  // only render_pool stages samples
     } else if (n_passes > kMaxPassesPerLaunch) {
         p.status = PlanStatus::invalid_value;

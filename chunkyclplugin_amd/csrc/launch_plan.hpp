@@ -133,12 +133,12 @@ struct RenderPlan {
     NotPool why;
     ExtRefusal ext_refusal;
 };
-// projector_type: CameraView::projector_type; n_passes: of this launch; want_fold_stats: launch_render_stats' fold
+// projector_type: CameraView::projector_type; n_passes: of this launch; want_staged_fold: the launch's samples are folded by more than fold_kernel (kernels.hpp StagedFold)
 // have_queue_and_staging: the work counter AND the staging array exist.  The two are deliberately one fact: every caller has both or
 // neither (the C API allocates them together before any launch), and without either render_lanes runs — render_waves, which needs
 // the counter alone, is not chosen for a caller that has the counter but could not stage.
 RenderPlan plan_render(int variant, const SceneFacts& F, const RenderOpts& O, int projector_type, const ShardView& T, int n_passes,
-                       bool have_queue_and_staging, bool have_seeds_dev, bool want_fold_stats);
+                       bool have_queue_and_staging, bool have_seeds_dev, bool want_staged_fold);
 // the message of check_extended_opts for a refusal, with `who` in front
 const char* ext_refusal_text(ExtRefusal r);
 

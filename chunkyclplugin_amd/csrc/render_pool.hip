@@ -624,7 +624,7 @@ __global__ void __launch_bounds__(256) clear_foreign_kernel(ShardView T, int wid
 // render_pool + fold_kernel, as planned: look the kernel up, size the persistent grid, fill the arguments, launch, fold.
 static hipError_t launch_pool(const RenderPlan& plan, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
-                              float* staging, const int* seeds_dev, float* fold_stats = nullptr, const BiomeMap* biome = nullptr) {
+                              float* staging, const int* seeds_dev, const StagedFold& fold = StagedFold{}, const BiomeMap* biome = nullptr) {
     // (biome: a plan of plan_biome's, run by the instantiation that takes the map ahead of the same arguments)
     const PoolKernel k = biome ? nullptr : pool_kernel(plan);
     const PoolBiomeKernel kb = biome ? pool_kernel_biome(plan) : nullptr;
@@ -651,8 +651,11 @@ static hipError_t launch_pool(const RenderPlan& plan, const SceneView& S, const 
         hipLaunchKernelGGL(k, dim3(grid), dim3(block), plan.lds, stream, A);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (fold_stats) {  // adaptive sampling: the same running mean, and the pixels' luminance statistic from the same read
-        return launch_fold_stats(staging, res, fold_stats, T, C.width, C.height, n_tiles, P.n, P.first_spp, stream);
+    if (fold.kind == StagedFold::stats) {  // adaptive sampling: the same running mean, and the pixels' luminance statistic from the same read
+        return launch_fold_stats(staging, res, fold.stat_image, T, C.width, C.height, n_tiles, P.n, P.first_spp, stream);
+    }
+    if (fold.kind == StagedFold::buckets) {  // robust accumulation: the same running mean, and the pixels' bucket means from the same read
+        return launch_fold_buckets(staging, res, fold.bucket_images, fold.n_buckets, fold.first_index, T, C.width, C.height, n_tiles, P.n, P.first_spp, stream);
     }
     const long long threads = 3ll * n_tiles * kSampleTile;
     hipLaunchKernelGGL(fold_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, (const float*)staging, res, T,
@@ -662,19 +665,19 @@ static hipError_t launch_pool(const RenderPlan& plan, const SceneView& S, const 
 hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                          const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
                          float* staging, const int* seeds_dev) {
-    return launch_render_stats(variant, S, C, O, T, P, res, work_counter, stream, chosen, staging, seeds_dev, nullptr);
+    return launch_render_fold(variant, S, C, O, T, P, res, work_counter, stream, chosen, staging, seeds_dev, StagedFold{});
 }
-hipError_t launch_render_stats(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
-                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
-                               float* staging, const int* seeds_dev, float* fold_stats) {
-    const RenderPlan plan = plan_render(variant, scene_facts(S), O, C.projector_type, T, P.n, work_counter && staging, seeds_dev != nullptr, fold_stats != nullptr);
+hipError_t launch_render_fold(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
+                              const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
+                              float* staging, const int* seeds_dev, const StagedFold& fold) {
+    const RenderPlan plan = plan_render(variant, scene_facts(S), O, C.projector_type, T, P.n, work_counter && staging, seeds_dev != nullptr, fold.kind != StagedFold::none);
     switch (plan.status) {
         case PlanStatus::invalid_value: return hipErrorInvalidValue;
         case PlanStatus::not_supported: return hipErrorNotSupported;
         default: break;
     }
     if (plan.family == KernelFamily::pool)
-        return launch_pool(plan, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr, fold_stats);
+        return launch_pool(plan, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr, fold);
     if (plan.needs_list) {  // a shard of 16 x 16 blocks: the fallback kernels take the rank's pixels as a list
         ShardView F = T;
         F.n_local = T.n_list;
@@ -695,9 +698,9 @@ hipError_t launch_render_biome(int variant, const SceneView& S, const BiomeMap& 
     }
     if (b.refusal != BiomeRefusal::none) return hipErrorNotSupported;  // (the C API has refused it with the reason before it came here)
     if (b.plan.family == KernelFamily::pool)
-        return launch_pool(b.plan, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr, nullptr, &B);
+        return launch_pool(b.plan, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr, StagedFold{}, &B);
     ShardView F = T;
-    if (b.plan.needs_list) F.n_local = T.n_list;  // a shard of 16 x 16 blocks: the rank's pixels as a list (launch_render_stats)
+    if (b.plan.needs_list) F.n_local = T.n_list;  // a shard of 16 x 16 blocks: the rank's pixels as a list (launch_render_fold)
     return launch_lanes_biome(b.plan, S, B, C, O, F, P, res, stream, chosen);
 }
 

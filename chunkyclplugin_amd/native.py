@@ -18,9 +18,9 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("CHUNKY_HIP_LIB") or os.path.join(PKG_DIR, "libchunky_hip.so")  # override: tuning builds (tools/variants.sh)
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
-SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_pool_biome.hip", "render_pool_biome_bvh.hip", "render_biome.hip", "aov_biome.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "lights.hip", "lights_groups.hip", "matte.hip", "denoise.hip", "adaptive.hip",
-           "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_occlusion.hip", "capi_lights.hip", "capi_matte.hip", "capi_adaptive.hip", "capi_denoise.hip",
-           "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "canvas_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp", "lights_host.cpp",
+SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_pool_biome.hip", "render_pool_biome_bvh.hip", "render_biome.hip", "aov_biome.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "lights.hip", "lights_groups.hip", "matte.hip", "denoise.hip", "adaptive.hip", "robust.hip",
+           "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_occlusion.hip", "capi_lights.hip", "capi_matte.hip", "capi_adaptive.hip", "capi_denoise.hip", "capi_robust.hip",
+           "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "canvas_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp", "lights_host.cpp", "robust_host.cpp",
            "scene_records.cpp", "widetree.cpp", "launch_plan.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
 
@@ -175,6 +175,14 @@ class AdaptiveState(C.Structure):
 
 ROUND_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32)
 
+ROBUST_MEAN, ROBUST_MEDIAN, ROBUST_GINI = 0, 1, 2  # chunky_robust_params.mode
+ROBUST_BUCKETS = (3, 5, 7, 9, 11, 13, 15)  # the bucket counts chunky_render_robust_begin takes
+
+
+class RobustParams(C.Structure):
+    """chunky_robust_params (include/chunky_hip.h)."""
+    _fields_ = [("size", C.c_int32), ("mode", C.c_int32), ("gain", C.c_float)]
+
 
 class AdaptiveCallbacks(C.Structure):
     """chunky_adaptive_callbacks (include/chunky_hip.h)."""
@@ -285,6 +293,16 @@ def lib() -> C.CDLL:
             "chunky_render_adaptive_resume": [vp, vp, C.c_int, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveCallbacks), C.POINTER(AdaptiveSummary)],
             "chunky_render_adaptive_state": [vp, C.POINTER(AdaptiveState), vp, i64],
             "chunky_render_adaptive_restore": [vp, C.POINTER(AdaptiveState), vp, vp, vp, vp],
+            "chunky_robust_default_params": [C.POINTER(RobustParams)],
+            "chunky_robust_host": [C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp],
+            "chunky_robust_host_resolve": [C.c_int, i64, vp, C.POINTER(RobustParams), vp, vp],
+            "chunky_render_robust_begin": [vp, C.c_int],
+            "chunky_render_robust_passes": [vp, vp, C.c_int, C.c_int],
+            "chunky_render_robust_read_bucket": [vp, C.c_int, vp, i64, C.POINTER(i32)],
+            "chunky_render_robust_resolve": [vp, C.POINTER(RobustParams), vp, i64, vp, i64],
+            "chunky_render_robust_denoise": [vp, C.POINTER(RobustParams), C.POINTER(DenoiseParams), vp, i64],
+            "chunky_render_robust_kernel_time": [vp, C.POINTER(f32), C.POINTER(C.c_int), C.POINTER(f32)],
+            "chunky_selftest_robust": [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(RobustParams), vp, vp, vp],
             "chunky_render_run": [vp, vp, C.POINTER(i32), i32, i32, POST_RENDER_FN, vp],
             "chunky_render_run_ex": [vp, vp, C.POINTER(i32), i32, i32, C.POINTER(RunCallbacks)],
             "chunky_java_random_ints": [i64, vp, C.c_int],
@@ -611,3 +629,38 @@ def adaptive_host_resume(run: AdaptiveRun, samples) -> AdaptiveRun:
 def adaptive_state_check(run: AdaptiveRun) -> None:
     """chunky_adaptive_state_check: raises ChunkyHipError (E_INVALID) for a state no run can have left."""
     check(lib().chunky_adaptive_state_check(C.byref(run.state), ptr(run.count), ptr(run.active)))
+
+
+def robust_params(mode: Optional[int] = None, gain: Optional[float] = None) -> RobustParams:
+    """chunky_robust_default_params (ROBUST_GINI, gain 1) with the given members replaced."""
+    p = RobustParams()
+    check(lib().chunky_robust_default_params(C.byref(p)))
+    if mode is not None:
+        p.mode = int(mode)
+    if gain is not None:
+        p.gain = float(gain)
+    return p
+
+
+def robust_host(samples, n_buckets: int, first_index: int = 0, buckets=None) -> np.ndarray:
+    """chunky_robust_host: the bucket means (n_buckets, h, w, 3) after the per-pass samples (n, h, w, 3) float32, taken as robust
+    samples first_index .. and folded into a copy of `buckets` (default: zero).  No device needed."""
+    s = np.ascontiguousarray(samples, np.float32)
+    if s.ndim != 4 or s.shape[3] != 3:
+        raise ValueError(f"expected samples of shape (n, height, width, 3), got {s.shape}")
+    n, h, w, _ = s.shape
+    b = np.zeros((int(n_buckets), h, w, 3), np.float32) if buckets is None else np.array(buckets, np.float32, order="C").reshape(int(n_buckets), h, w, 3)
+    check(lib().chunky_robust_host(w, h, ptr(s), n, int(n_buckets), int(first_index), ptr(b)))
+    return b
+
+
+def robust_host_resolve(buckets, params: Optional[RobustParams] = None):
+    """chunky_robust_host_resolve: (image (..., 3) float32, trim (...) uint8) of bucket means (n_buckets, ..., 3).  No device needed."""
+    b = np.ascontiguousarray(buckets, np.float32)
+    if b.ndim < 3 or b.shape[-1] != 3:
+        raise ValueError(f"expected buckets of shape (n_buckets, ..., 3), got {b.shape}")
+    p = params if params is not None else robust_params()
+    out = np.empty(b.shape[1:], np.float32)
+    trim = np.empty(b.shape[1:-1], np.uint8)
+    check(lib().chunky_robust_host_resolve(b.shape[0], trim.size, ptr(b), C.byref(p), ptr(out), ptr(trim)))
+    return out, trim

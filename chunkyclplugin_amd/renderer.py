@@ -675,6 +675,59 @@ class HipPathTracingRenderer:
         check(native.lib().chunky_render_adaptive_kernel_time(self._h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    # --- firefly-robust accumulation (chunky_render_robust_*) -----------------------------------------
+    def robust_begin(self, n_buckets: int) -> None:
+        """chunky_render_robust_begin: n_buckets zeroed bucket images and a sample count of 0 (0 releases the state)."""
+        check(native.lib().chunky_render_robust_begin(self._h, int(n_buckets)))
+
+    def robust_passes(self, seeds, first_buffer_spp: int = 0, sync: bool = True) -> None:
+        """chunky_render_robust_passes: render_passes plus the bucket fold of the same samples."""
+        s = np.ascontiguousarray(seeds, np.int32)
+        check(native.lib().chunky_render_robust_passes(self._h, ptr(s) if s.size else None, s.size, int(first_buffer_spp)))
+        if sync:
+            self.sync()
+
+    def robust_bucket(self, b: int):
+        """(bucket image (h, w, 3), robust sample count)"""
+        out = np.empty((self.height, self.width, 3), np.float32)
+        n = C.c_int32()
+        check(native.lib().chunky_render_robust_read_bucket(self._h, int(b), ptr(out), out.size, C.byref(n)))
+        return out, n.value
+
+    def robust_buckets(self, n_buckets: int) -> np.ndarray:
+        """All bucket images, (n_buckets, h, w, 3)."""
+        return np.stack([self.robust_bucket(b)[0] for b in range(n_buckets)])
+
+    def robust_resolve(self, params=None, trim: bool = True):
+        """chunky_render_robust_resolve: (image (h, w, 3), trim (h, w) uint8 or None), resolved on the device."""
+        p = params if params is not None else native.robust_params()
+        out = np.empty((self.height, self.width, 3), np.float32)
+        t = np.empty((self.height, self.width), np.uint8) if trim else None
+        check(native.lib().chunky_render_robust_resolve(self._h, C.byref(p), ptr(out), out.size, ptr(t) if trim else None, t.size if trim else 0))
+        return out, t
+
+    def robust_denoise(self, params=None, denoise_params=None) -> np.ndarray:
+        """chunky_render_robust_denoise: the resolved image filtered with this target's AOV images, all on the device."""
+        p = params if params is not None else native.robust_params()
+        d = denoise_params if denoise_params is not None else native.denoise_params()
+        out = np.empty((self.height, self.width, 3), np.float32)
+        check(native.lib().chunky_render_robust_denoise(self._h, C.byref(p), C.byref(d), ptr(out), out.size))
+        return out
+
+    def robust_kernel_time(self):
+        """(milliseconds of the robust_passes launches, their number, milliseconds of the resolve kernels) since the last call."""
+        ms, n, rs = C.c_float(), C.c_int(), C.c_float()
+        check(native.lib().chunky_render_robust_kernel_time(self._h, C.byref(ms), C.byref(n), C.byref(rs)))
+        return ms.value, n.value, rs.value
+
+    def render_robust(self, seeds, n_buckets: int = 9, params=None, first_buffer_spp: int = 0):
+        """Begins a robust state of n_buckets buckets, renders len(seeds) passes into it and the framebuffer, and resolves.  Returns
+        (resolved image (h, w, 3), trim (h, w) uint8).  The resolved image is a biased estimator (it darkens rare bright paths with
+        the fireflies); read() still returns the unbiased running mean of the same passes."""
+        self.robust_begin(n_buckets)
+        self.robust_passes(seeds, first_buffer_spp)
+        return self.robust_resolve(params)
+
     def render_list(self, pixels, seeds) -> None:
         """chunky_selftest_render_list: len(seeds) passes on the listed pixel indices only, through the list route of the adaptive rounds."""
         px = np.ascontiguousarray(pixels, np.int32)

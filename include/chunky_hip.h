@@ -959,6 +959,100 @@ int chunky_render_adaptive_state(chunky_render* r, chunky_adaptive_state* out, u
 int chunky_render_adaptive_restore(chunky_render* r, const chunky_adaptive_state* st, const float* mean, const int32_t* count,
                                    const float* stat, const uint8_t* active);
 
+/* ---- firefly-robust accumulation: bucket means and a Gini-trimmed resolve ----
+ * No counterpart in the reference (its image is the plain running mean, in which one sample thousands of times brighter than its
+ * neighbours stays visible for thousands of passes).  The method is a median of means with an adaptive trim, after the idea of
+ * Buisine, Delepoulle and Renaud, "Firefly removal in Monte Carlo rendering with adaptive Median of meaNs" (2021); the formulas are
+ * this project's own specification and do not claim to reproduce that paper.  The arithmetic is chunkyclplugin_amd/csrc/robust_spec.h,
+ * compiled by the kernels and the host alike; every operation is ONE exactly rounded float operation, no multiply-add is fused.
+ *
+ * Buckets.  M is odd, 3 <= M <= 15, h = (M - 1) / 2.  The target counts robust samples from 0 since chunky_render_robust_begin; sample
+ * j goes to bucket j % M, whose mean is updated per channel as the framebuffer's is (K/rayTracer.cl:109-112) with k = j / M:
+ *     mean_b = (mean_b * (float)k + c) / (float)(k + 1)
+ * first_buffer_spp weights only the beauty mean (the framebuffer), exactly as in chunky_render_passes.
+ *
+ * Resolve, per pixel and per channel, over the M bucket means x:
+ *   1. sort ascending with the fixed odd-even transposition network: rounds r = 0 .. M - 1, round r compares the pairs (i, i + 1) for
+ *      i = r & 1, (r & 1) + 2, ... and swaps iff x[i + 1] < x[i].  A NaN never swaps; the order is then defined but arbitrary.
+ *   2. S = x0; S = S + x_i for i = 1 .. M - 1.   W = (float)(1 - M) * x0; W = W + (float)(2 i - M + 1) * x_i for i = 1 .. M - 1.
+ *   3. G = (S > 0 && S < inf) ? W / ((float)M * S) : 0 (the Gini coefficient of the bucket means; a NaN in S gives 0).
+ *   4. p = (G * (float)(h + 1)) * gain;  t = !(p > 0) ? 0 : (p >= (float)h ? h : (int)p).  CHUNKY_ROBUST_MEAN forces t = 0,
+ *      CHUNKY_ROBUST_MEDIAN forces t = h, CHUNKY_ROBUST_GINI uses the formula.
+ *   5. out = (x_t + x_{t+1} + ... + x_{M-1-t}) / (float)(M - 2 t), added left to right.
+ * The trim byte of a pixel is the largest t of its three channels.
+ *
+ * The resolved image is a BIASED estimator: it darkens legitimately rare bright paths (a small light seen through a long diffuse
+ * chain) as it darkens fireflies.  It is not the reference's image.  The beauty image — chunky_render_read — is unchanged by all of
+ * this: chunky_render_robust_passes folds it bit for bit as chunky_render_passes does. */
+#define CHUNKY_ROBUST_MEAN 0
+#define CHUNKY_ROBUST_MEDIAN 1
+#define CHUNKY_ROBUST_GINI 2
+#define CHUNKY_ROBUST_MIN_BUCKETS 3
+#define CHUNKY_ROBUST_MAX_BUCKETS 15
+typedef struct chunky_robust_params {
+    int32_t size; /* sizeof(chunky_robust_params) as the caller was compiled (members may be appended) */
+    int32_t mode; /* CHUNKY_ROBUST_MEAN, _MEDIAN or _GINI */
+    float gain;   /* finite, >= 0: scales the trim of CHUNKY_ROBUST_GINI (0 trims nothing); checked in every mode */
+} chunky_robust_params;
+/* Fills the defaults: CHUNKY_ROBUST_GINI with gain 1. */
+int chunky_robust_default_params(chunky_robust_params* p);
+
+/* The bucket fold on the host: needs no context and no device.  samples = n images [n][height][width][3], the robust samples
+ * first_index .. first_index + n - 1 of every pixel; buckets = n_buckets images [bucket][height][width][3], the state before (all
+ * zero at the start) and after.  n == 0 is legal.  CHUNKY_E_INVALID: a NULL array, width or height <= 0, an even n_buckets or one
+ * outside 3 .. 15, n < 0, first_index < 0 or first_index + n beyond INT32_MAX. */
+int chunky_robust_host(int width, int height, const float* samples, int n, int n_buckets, int first_index, float* buckets);
+/* The resolve on the host, the specification the device is held to: buckets [n_buckets][n_pixels][3] to out (3 * n_pixels floats)
+ * and, where trim is not NULL, the trim bytes (n_pixels).  Whether a bucket holds a sample is the caller's affair here.
+ * CHUNKY_E_INVALID: a NULL array, n_pixels <= 0, a bad n_buckets, params NULL or with a size below this struct's first version
+ * (through `gain`), an unknown mode, a gain that is not finite or < 0. */
+int chunky_robust_host_resolve(int n_buckets, int64_t n_pixels, const float* buckets, const chunky_robust_params* params, float* out,
+                               uint8_t* trim);
+
+/* Allocates and zeroes the target's n_buckets bucket images, laid out [bucket][pixel][3], and sets the robust sample count to 0; a
+ * second call resets the state (to another n_buckets where asked); n_buckets == 0 releases it.  Waits for the target's queued work.
+ * The framebuffer is not touched.  CHUNKY_E_INVALID for an even n_buckets or one outside 3 .. 15; CHUNKY_E_STATE for a group's
+ * target.  No other call sees or touches the robust state (chunky_render_reset included), and the robust calls touch no other
+ * image than the framebuffer, which chunky_render_robust_passes folds as chunky_render_passes does. */
+int chunky_render_robust_begin(chunky_render* r, int n_buckets);
+/* chunky_render_passes plus the bucket fold: n passes (seeds[k], bufferSpp first_buffer_spp + k) folded into the framebuffer bit
+ * for bit as chunky_render_passes folds them, and as robust samples count .. count + n - 1 into the buckets, from one read of the
+ * staged samples.  Asynchronous, in launches of at most 256 passes (fewer where the staging array would pass its cap); n == 0 is
+ * legal.  A chunky_render_passes between two of these calls adds to the framebuffer only.  A shard set with chunky_render_set_shard
+ * is honoured: a rank folds its own pixels and leaves the others' buckets zero.
+ * CHUNKY_E_INVALID: n < 0, NULL seeds with n > 0, first_buffer_spp < 0, a count that would pass INT32_MAX.  CHUNKY_E_STATE, never a
+ * fallback and before anything is launched: before chunky_render_robust_begin or chunky_render_set_camera; a group's target; a scene
+ * or options that send the target to the fallback kernels, which stage no samples; a biome map on the scene while the target tints
+ * by position; the extended light-transport options where chunky_render_passes refuses them. */
+int chunky_render_robust_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp);
+/* Blocking read-back of bucket b (0 .. n_buckets - 1), 3 * width * height floats; *count (may be NULL) receives the robust sample
+ * count.  CHUNKY_E_STATE before chunky_render_robust_begin; CHUNKY_E_INVALID for a bucket outside the range, a NULL buffer or a
+ * wrong n_floats. */
+int chunky_render_robust_read_bucket(chunky_render* r, int b, float* out, int64_t n_floats, int32_t* count);
+/* The resolve on the device, blocking: out receives the image (n_floats = 3 * width * height) and trim, where not NULL, the trim
+ * bytes (n_pixels = width * height; ignored with trim == NULL).  The buckets and the framebuffer are read, never written.
+ * Parameter errors as chunky_robust_host_resolve.  CHUNKY_E_STATE before chunky_render_robust_begin, and while fewer than n_buckets
+ * samples have been folded (a bucket would be empty). */
+int chunky_render_robust_resolve(chunky_render* r, const chunky_robust_params* params, float* out, int64_t n_floats, uint8_t* trim,
+                                 int64_t n_pixels);
+/* chunky_render_denoise with the resolved image in the place of the framebuffer: resolved and filtered on the device with the
+ * target's own AOV images, only the result crosses to the host.  Errors as chunky_render_robust_resolve and chunky_render_denoise
+ * (CHUNKY_E_STATE before any AOV pass and on a shard of world > 1); its launches are timed with the denoiser's
+ * (chunky_render_denoise_kernel_time). */
+int chunky_render_robust_denoise(chunky_render* r, const chunky_robust_params* robust_params, const chunky_denoise_params* denoise_params,
+                                 float* out, int64_t n_floats);
+/* Device time of the chunky_render_robust_passes launches (render kernel and fold) and of the resolve kernels since the last call,
+ * from HIP events on the stream they run on, and the number of render launches; apart from chunky_render_kernel_time, which does
+ * not see them.  resolve_ms (may be NULL, as the others) receives the resolves' share on its own; it is not in total_ms. */
+int chunky_render_robust_kernel_time(chunky_render* r, float* total_ms, int* launches, float* resolve_ms);
+/* ---- self test of the two robust kernels on caller-supplied samples (how non-finite values reach the device): samples = n images
+ * [n][height][width][3] are arranged on the device in the staging layout of one launch of the whole image, folded from zero buckets
+ * as robust samples first_index .. by the fold kernel, and resolved.  buckets_out (3 * n_buckets * width * height floats), image_out
+ * (3 * width * height) and trim_out (width * height bytes) may each be NULL.  1 <= n <= 256, width * height <= 2^20; parameter errors
+ * as chunky_robust_host and chunky_robust_host_resolve.  Blocking. */
+int chunky_selftest_robust(chunky_ctx* ctx, int width, int height, const float* samples, int n, int n_buckets, int first_index,
+                           const chunky_robust_params* params, float* buckets_out, float* image_out, uint8_t* trim_out);
+
 /* ---- host pass loop (replaces OpenClPathTracingRenderer.render, J/opencl/OpenClPathTracingRenderer.java:54-191):
  * seeds from java.util.Random(0).nextInt(), bufferSpp restarting at 0 after each read-back, merge
  * sample = (sample*sampSpp + pass*passSpp) / (sampSpp+passSpp) in double (:167-173).

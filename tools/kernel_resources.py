@@ -2,7 +2,7 @@
 """tools/kernel_resources.py [out.json] — registers, spills and occupancy of every render_pool / fold_kernel instantiation, of the
 denoise kernels, of the adaptive-sampling kernels, of the first-hit pass kernels (first_hit_kernel with the AOV, AOV-ex and ID-matte folds) and of the matte read-outs as hipcc reports them for gfx950
 (-Rpass-analysis=kernel-resource-usage on csrc/render_pool.hip, csrc/render_pool_bvh.hip (the entity-BVH instantiations),
-csrc/denoise.hip, csrc/adaptive.hip, csrc/aov.hip, csrc/matte.hip, csrc/occlusion.hip (occlusion_kernel), csrc/lights.hip (light_kernel, light_mix_kernel) and csrc/lights_groups.hip (light_group_kernel, light_group_mix_kernel) with the library's flags),
+csrc/denoise.hip, csrc/adaptive.hip, csrc/robust.hip (fold_buckets_kernel<M>, robust_resolve_kernel<M>), csrc/aov.hip, csrc/matte.hip, csrc/occlusion.hip (occlusion_kernel), csrc/lights.hip (light_kernel, light_mix_kernel) and csrc/lights_groups.hip (light_group_kernel, light_group_mix_kernel) with the library's flags),
 and of the biome-tint units csrc/render_pool_biome.hip, csrc/render_pool_biome_bvh.hip, csrc/render_biome.hip and csrc/aov_biome.hip, whose kernels are listed as "biome <name>" (they
 have the names of the kernels they are instantiated from and the biome map as one more argument).  CPU only."""
 import json
@@ -17,7 +17,7 @@ from chunkyclplugin_amd import native  # noqa: E402
 
 flags = [f for f in native.HIPCC_FLAGS if f not in ("-shared",)]
 err = ""
-for src in ("render_pool.hip", "render_pool_bvh.hip", "denoise.hip", "adaptive.hip", "aov.hip", "matte.hip", "occlusion.hip", "lights.hip", "lights_groups.hip",
+for src in ("render_pool.hip", "render_pool_bvh.hip", "denoise.hip", "adaptive.hip", "robust.hip", "aov.hip", "matte.hip", "occlusion.hip", "lights.hip", "lights_groups.hip",
             "render_pool_biome.hip", "render_pool_biome_bvh.hip", "render_biome.hip", "aov_biome.hip"):
     cmd = ["hipcc", *flags, "-x", "hip", "-c", os.path.join(native.CSRC, src), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
     err += "Unit: " + src + "\n" + subprocess.run(cmd, capture_output=True, text=True).stderr
