@@ -20,49 +20,16 @@ static int adaptive_ensure(chunky_render* r) {
 // what an adaptive call needs of the target: one device, the whole image, and render_pool for the scene and options as they are
 static int adaptive_state(const char* who, chunky_render* r, SceneView* S) {
     if (r->shard.world > 1) return fail(CHUNKY_E_STATE, "%s: this target holds rank %d of %d of the image, not all of it", who, r->shard.rank, r->shard.world);
-    if (!r->have_camera) return fail(CHUNKY_E_STATE, "%s before set_camera", who);
-    if (int rc = refuse_biome(who, r)) return rc;  // the statistics fold runs on the kernels that do not tint by position
-    if (int rc = scene_view(r->scene, S, r->opts.nee != 0)) return rc;
-    S->bvh_cull = r->opts.bvh_cull;
-    const RenderPlan plan = render_plan(r, *S);
-    if (int rc = check_extended_opts(who, plan)) return rc;
-    if (plan.family != KernelFamily::pool)
-        return fail(CHUNKY_E_STATE, "%s: the scene or the options send this target to the fallback kernels, which stage no samples", who);
-    return CHUNKY_OK;
+    return needs_render_pool(who, r, S);
 }
 
-// The most passes one launch over the pixel slots of T carries (launch_pass_cap of T, not of r->shard; at most kMaxPassesPerLaunch:
-// the seeds travel in the kernel-argument segment), and the staging array grown to hold a launch of min(n, cap) passes — before
-// the round's timing bracket opens, so that no allocation is timed.  It grows only: chunky_render_passes reuses it, and
-// r->launch_cap is not touched.
-static int adaptive_stage(chunky_render* r, const ShardView& T, int n, int* cap_out) {
-    const int cap = launch_pass_cap(T, r->width, r->height, kStagingBytes, kMaxPassesPerLaunch);
-    if (cap < 1) return fail(CHUNKY_E_INVALID, "adaptive: the image is too large to stage one pass");
-    *cap_out = cap;
-    const size_t need = staging_floats(T, r->width, r->height, n < cap ? n : cap) * sizeof(float);
-    if (r->staging.bytes < need) {
-        HIP_TRY(hipStreamSynchronize(r->ctx->stream));
-        HIP_TRY(r->staging.alloc(need));
-    }
-    return CHUNKY_OK;
-}
-
-// n passes (bufferSpp first_spp ..) over the pixel slots of T — the target's own shard, or a list of pixels — folded with the
-// luminance statistic, in launches of at most `cap` passes (adaptive_stage)
-static int adaptive_launch(chunky_render* r, const SceneView& S, const ShardView& T, const int32_t* seeds, int n, int first_spp, int cap) {
-    if (T.n_local <= 0) return CHUNKY_OK;
-    for (int done = 0; done < n;) {
-        PassSeeds ps;
-        ps.n = (n - done) < cap ? (n - done) : cap;
-        ps.first_spp = first_spp + done;
-        memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
-        StagedFold fold;
-        fold.kind = StagedFold::stats;
-        fold.stat_image = (float*)r->ad_stat.p;
-        HIP_TRY(launch_render_fold(r->kernel_variant, S, r->cam, r->opts, T, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream, &r->last_choice,
-                                   (float*)r->staging.p, nullptr, fold));
-        done += ps.n;
-    }
+// one launch over the pixel slots of T — the target's own shard, or a list of pixels — folded with the luminance statistic
+static int adaptive_fold(chunky_render* r, const SceneView& S, const ShardView& T, const PassSeeds& ps) {
+    StagedFold fold;
+    fold.kind = StagedFold::stats;
+    fold.stat_image = (float*)r->ad_stat.p;
+    HIP_TRY(launch_render_fold(r->kernel_variant, S, r->cam, r->opts, T, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream, &r->last_choice,
+                               (float*)r->staging.p, nullptr, fold));
     return CHUNKY_OK;
 }
 
@@ -92,21 +59,24 @@ static int adaptive_run(chunky_render* r, const char* who, const SceneView& S, c
         int launched = 0;
         bool opened = false;
         if (!step.check_first) {
+            // the staging array before the round's timing bracket opens, so that no allocation is timed (T's cap, not r->launch_cap's)
             int cap = 0;
-            if (int rc = adaptive_stage(r, T, step.round, &cap)) return rc;
-            while (launched < step.round) {  // a round longer than the launch cap is several launches, with a poll before each
+            if (int rc = stage_fold_launches("adaptive", r, T, step.round, &cap)) return rc;
+            // a round longer than the launch cap is several launches, with a poll before each
+            const int cut = for_each_launch(seeds + s.passes, step.round, s.passes, cap, [&](const PassSeeds& ps, const int32_t*) {
                 if (cb.post_render && cb.post_render(cb.user)) {
                     stop = true;
-                    break;
+                    return (int)CHUNKY_E_ABORTED;
                 }
                 if (!opened) {
                     if (int rc = r->ad_clock.open(st)) return rc;
                     opened = true;
                 }
-                const int n = step.round - launched < cap ? step.round - launched : cap;
-                if (int rc = adaptive_launch(r, S, T, seeds + s.passes + launched, n, s.passes + launched, cap)) return rc;
-                launched += n;
-            }
+                if (int rc = adaptive_fold(r, S, T, ps)) return rc;
+                launched += ps.n;
+                return (int)CHUNKY_OK;
+            });
+            if (cut && !stop) return cut;
             s.summary.samples += (int64_t)s.active * launched;
             s.passes += launched;
             if (launched > 0) s.summary.rounds += 1;
@@ -299,9 +269,9 @@ extern "C" int chunky_selftest_render_list(chunky_render* r, const int32_t* pixe
     HIP_TRY(hipStreamSynchronize(st));  // the caller may reuse its array on return
     const ShardView T{0, 2, 1, n_pixels, (const int*)r->ad_list.p, n_pixels};
     int cap = 0;
-    if (int rc = adaptive_stage(r, T, n, &cap)) return rc;
+    if (int rc = stage_fold_launches("adaptive", r, T, n, &cap)) return rc;
     if (int rc = r->ad_clock.open(st)) return rc;
-    if (int rc = adaptive_launch(r, S, T, seeds, n, 0, cap)) return rc;
+    if (int rc = for_each_launch(seeds, n, 0, cap, [&](const PassSeeds& ps, const int32_t*) { return adaptive_fold(r, S, T, ps); })) return rc;
     if (int rc = r->ad_clock.close(st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return r->ad_clock.collect();

@@ -7,13 +7,6 @@ static const int kAovExOffset[7] = {0, 0, 0, 1, 2, 5, 6};  // alpha, depth, posi
 constexpr int kAovExWords = 7;
 static size_t aov_ex_bytes(const chunky_render* r) { return (size_t)r->width * r->height * kAovExWords * 4; }
 
-static int aov_ensure(chunky_render* r) {
-    if (r->aov.p) return CHUNKY_OK;
-    const size_t bytes = aov_image_bytes(r) * 2 + 256;  // albedo, normal, the claim counter
-    HIP_TRY(r->aov.alloc(bytes));
-    HIP_TRY(hipMemsetAsync(r->aov.p, 0, bytes, r->ctx->stream));
-    return CHUNKY_OK;
-}
 // the five first-hit images: allocated, zeroed, by the first chunky_render_aov_passes_ex
 static int aov_ex_ensure(chunky_render* r) {
     if (r->aov_ex.p) return CHUNKY_OK;
@@ -27,17 +20,17 @@ static int aov_ex_ensure(chunky_render* r) {
 static int aov_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n, int first_buffer_spp, bool ex) {
     LOCK_RENDER(r);
     if (!r->have_camera) return fail(CHUNKY_E_STATE, "aov_passes before set_camera");
-    if (int rc = aov_ensure(r)) return rc;
+    if (int rc = r->aov_pass.ensure(2 * aov_image_bytes(r), r->ctx->stream)) return rc;  // albedo, normal
     if (ex)
         if (int rc = aov_ex_ensure(r)) return rc;
     r->aov_pass.last_launches = 0;
     if (n == 0 || T.n_local <= 0) return CHUNKY_OK;
     SceneView S;
-    if (int rc = scene_view(r->scene, &S)) return rc;
-    S.bvh_cull = r->opts.bvh_cull;
-    int* counter = (int*)((char*)r->aov.p + 2 * aov_image_bytes(r));
+    if (int rc = target_scene_view(r, &S)) return rc;
+    int* counter = r->aov_pass.counter();
+    char* aov = (char*)r->aov_pass.images.p;
     const size_t plane = (size_t)r->width * r->height;  // words of a one-word image
-    AovExImages images{(float*)r->aov.p, (float*)((char*)r->aov.p + aov_image_bytes(r)), nullptr, nullptr, nullptr, nullptr, nullptr};  // albedo, normal
+    AovExImages images{(float*)aov, (float*)(aov + aov_image_bytes(r)), nullptr, nullptr, nullptr, nullptr, nullptr};  // albedo, normal
     if (ex) {
         float* exf = (float*)r->aov_ex.p;
         images.alpha = exf + kAovExOffset[CHUNKY_AOV_ALPHA] * plane;
@@ -74,7 +67,8 @@ extern "C" int chunky_render_aov_read(chunky_render* r, int which, float* out, i
     if (r && !r->parts.empty()) return chunky_render_aov_read(r->parts[0], which, out, n);
     LOCK_RENDER(r);
     if (which != CHUNKY_AOV_ALBEDO && which != CHUNKY_AOV_NORMAL) return fail(CHUNKY_E_INVALID, "aov_read: unknown image %d", which);
-    const char* src = r->aov.p ? (const char*)r->aov.p + (which == CHUNKY_AOV_NORMAL ? aov_image_bytes(r) : 0) : nullptr;  // null before any AOV pass
+    const char* aov = (const char*)r->aov_pass.images.p;
+    const char* src = aov ? aov + (which == CHUNKY_AOV_NORMAL ? aov_image_bytes(r) : 0) : nullptr;  // null before any AOV pass
     return read_floats("aov_read", r, src, out, n, (int64_t)r->width * r->height * 3);
 }
 
@@ -83,8 +77,9 @@ extern "C" int chunky_render_aov_read_ex(chunky_render* r, int which, void* out,
     LOCK_RENDER(r);
     if (which < CHUNKY_AOV_ALBEDO || which > CHUNKY_AOV_BLOCK) return fail(CHUNKY_E_INVALID, "aov_read_ex: unknown image %d", which);
     const int64_t need = (int64_t)r->width * r->height * kAovWords[which];
+    const char* aov = (const char*)r->aov_pass.images.p;
     const char* src;  // null before any pass that writes the image
-    if (which <= CHUNKY_AOV_NORMAL) src = r->aov.p ? (const char*)r->aov.p + (which == CHUNKY_AOV_NORMAL ? aov_image_bytes(r) : 0) : nullptr;
+    if (which <= CHUNKY_AOV_NORMAL) src = aov ? aov + (which == CHUNKY_AOV_NORMAL ? aov_image_bytes(r) : 0) : nullptr;
     else src = r->aov_ex.p ? (const char*)r->aov_ex.p + (size_t)kAovExOffset[which] * r->width * r->height * 4 : nullptr;
     return read_floats("aov_read_ex", r, src, out, n, need);
 }
@@ -92,7 +87,7 @@ extern "C" int chunky_render_aov_read_ex(chunky_render* r, int which, void* out,
 extern "C" int chunky_render_aov_reset(chunky_render* r) {
     if (r && !r->parts.empty()) return chunky_render_aov_reset(r->parts[0]);
     LOCK_RENDER(r);
-    if (r->aov.p) HIP_TRY(hipMemsetAsync(r->aov.p, 0, 2 * aov_image_bytes(r), r->ctx->stream));
+    if (r->aov_pass.images.p) HIP_TRY(hipMemsetAsync(r->aov_pass.images.p, 0, 2 * aov_image_bytes(r), r->ctx->stream));
     if (r->aov_ex.p) HIP_TRY(hipMemsetAsync(r->aov_ex.p, 0, aov_ex_bytes(r), r->ctx->stream));
     return CHUNKY_OK;
 }

@@ -32,7 +32,7 @@ extern "C" int chunky_denoise_frame(chunky_ctx* ctx, int width, int height, cons
 // or the resolved image of chunky_render_robust_denoise
 int render_denoise(chunky_render* r, const DnCoeffs& K, int form, const float* color, float* out) {
     LOCK_RENDER(r);
-    if (!r->aov.p) return fail(CHUNKY_E_STATE, "render_denoise before any AOV pass");
+    if (!r->aov_pass.images.p) return fail(CHUNKY_E_STATE, "render_denoise before any AOV pass");
     const size_t bytes = aov_image_bytes(r), need = denoise_work_bytes(r->width, r->height);
     if (!r->dn_work.p) {
         HIP_TRY(r->dn_work.alloc(need));
@@ -40,8 +40,8 @@ int render_denoise(chunky_render* r, const DnCoeffs& K, int form, const float* c
     }
     if (r->dn_clock.full())
         if (int rc = r->dn_clock.collect()) return rc;
-    const float* albedo = (const float*)r->aov.p;
-    const float* normal = (const float*)((const char*)r->aov.p + bytes);
+    const float* albedo = (const float*)r->aov_pass.images.p;
+    const float* normal = (const float*)((const char*)r->aov_pass.images.p + bytes);
     int launches = 0;
     if (int rc = r->dn_clock.open(r->ctx->stream)) return rc;
     HIP_TRY(launch_denoise(form, r->width, r->height, color, albedo, normal, K, (float*)r->dn_out.p, r->dn_work.p, r->dn_work.bytes, r->ctx->stream, &launches));
@@ -62,7 +62,7 @@ extern "C" int chunky_render_denoise(chunky_render* r, const chunky_denoise_para
     const ShardView& share = r->parts.empty() ? r->shard : r->outer;
     if (share.world > 1) return fail(CHUNKY_E_STATE, "render_denoise: this target holds rank %d of %d of the image, not all of it", share.rank, share.world);
     if (r->parts.empty()) return render_denoise(r, K, form, r->fb, out);
-    if (!r->parts[0]->aov.p) return fail(CHUNKY_E_STATE, "render_denoise before any AOV pass");
+    if (!r->parts[0]->aov_pass.images.p) return fail(CHUNKY_E_STATE, "render_denoise before any AOV pass");
     if (int rc = group_gather(r)) return rc;  // member 0's buffer then holds the whole image (chunky_render_read's exchange)
     return render_denoise(r->parts[0], K, form, r->parts[0]->fb, out);
 }

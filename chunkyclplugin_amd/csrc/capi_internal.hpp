@@ -141,11 +141,22 @@ struct LaunchClock {
     int take(float* ms_out, int* count_out);  // collect, report the totals since the last take, zero them
 };
 
-// What the launches of one first-hit pass (first_hit_pass.hpp: the AOV's, the mattes') leave on a render target
+// What one first-hit pass (first_hit_pass.hpp: the AOV's, the mattes', the occlusion and light passes') keeps on a render target
 struct FirstHitPass {
-    LaunchClock clock;           // their device time (chunky_render_*_kernel_time)
+    LaunchClock clock;           // the launches' device time (chunky_render_*_kernel_time)
     AovChoice choice{0, 0, 0};   // what the most recent one ran
     int last_launches = 0;       // launches of the most recent *_passes call
+    DevBuf images;               // the pass's images, then the kernels' claim counter; null before the first call
+    size_t image_bytes = 0;      // bytes of the images, in front of the counter
+    // allocated, zeroed, by the first call that needs them
+    int ensure(size_t bytes, hipStream_t stream) {
+        if (images.p) return CHUNKY_OK;
+        HIP_TRY(images.alloc(bytes + 256));
+        HIP_TRY(hipMemsetAsync(images.p, 0, bytes + 256, stream));
+        image_bytes = bytes;
+        return CHUNKY_OK;
+    }
+    int* counter() const { return (int*)((char*)images.p + image_bytes); }
 };
 
 struct chunky_render {
@@ -184,28 +195,25 @@ struct chunky_render {
     std::vector<chunky_render*> parts;
     ShardView outer{0, 1, 0, 0};
     std::vector<DevBuf> gather_send, gather_recv;
-    // the denoiser's auxiliary images (chunky_render_aov_passes): albedo then normal, 3 * width * height floats each, then the
-    // kernel's claim counter; allocated (and zeroed) by the first AOV call.  Timing and the last instantiation are kept apart from
-    // the render kernels' (chunky_render_kernel_time / _kernel_info do not see AOV launches)
-    DevBuf aov;
+    // the denoiser's auxiliary images (chunky_render_aov_passes): aov_pass.images holds albedo then normal, 3 * width * height floats
+    // each.  Timing and the last instantiation are kept apart from the render kernels' (chunky_render_kernel_time / _kernel_info do
+    // not see AOV launches)
     // chunky_render_aov_passes_ex: alpha, depth (a word per pixel each), position (3), emittance, block id (1 each), allocated (and
     // zeroed) by the first _ex call; its launches share the AOV's counter and record
     DevBuf aov_ex;
     FirstHitPass aov_pass{LaunchClock(&free_events)};
-    // chunky_render_matte_passes: 13 planes of width * height int32 (six of ids, six of counts, `other`), then the kernel's claim
-    // counter; allocated (and zeroed) by the first matte call.  matte_work holds a read-out on its way to the host (ranks: 12 planes;
-    // extract: one) and matte_set the sorted ids of an extract.  Record and counter are its own: the AOV calls do not see them
-    DevBuf matte, matte_work, matte_set;
+    // chunky_render_matte_passes: matte_pass.images holds 13 planes of width * height int32 (six of ids, six of counts, `other`).
+    // matte_work holds a read-out on its way to the host (ranks: 12 planes; extract: one) and matte_set the sorted ids of an extract.
+    // Record and counter are its own: the AOV calls do not see them
+    DevBuf matte_work, matte_set;
     FirstHitPass matte_pass{LaunchClock(&free_events)};
     int32_t matte_passes = 0;     // passes folded since the last reset
-    // chunky_render_occlusion_passes: the AO image, the SUN image (width * height floats each), then the kernel's claim counter;
-    // allocated (and zeroed) by the first occlusion call.  Record and counter are its own: no other call sees them
-    DevBuf occlusion;
+    // chunky_render_occlusion_passes: occlusion_pass.images holds the AO image, then the SUN image (width * height floats each).
+    // Record and counter are its own: no other call sees them
     FirstHitPass occlusion_pass{LaunchClock(&free_events)};
-    // chunky_render_light_passes: the SKY, SUN, EMITTERS and ALL images (3 * width * height floats each), then the kernel's claim
-    // counter; allocated (and zeroed) by the first light call.  light_mix holds a mix on its way to the host.  Record and counter
-    // are its own: no other call sees them
-    DevBuf lights, light_mix;
+    // chunky_render_light_passes: light_pass.images holds the SKY, SUN, EMITTERS and ALL images (3 * width * height floats each).
+    // light_mix holds a mix on its way to the host.  Record and counter are its own: no other call sees them
+    DevBuf light_mix;
     FirstHitPass light_pass{LaunchClock(&free_events)};
     // chunky_render_light_set_emitter_groups: the table (n_groups == 0: no groups), and on the device the group images, the kernel's
     // per-sample sums and touched words and the table's bytes (capi_lights.hip), allocated by the set call
@@ -289,17 +297,13 @@ template <class Launch>
 static int first_hit_launches(chunky_render* r, FirstHitPass& fp, const int32_t* seeds, int n, int first_buffer_spp, Launch launch) {
     if (fp.clock.full())
         if (int rc = fp.clock.collect()) return rc;
-    for (int done = 0; done < n; done += kMaxPassesPerLaunch) {
-        PassSeeds ps;
-        ps.n = std::min(n - done, kMaxPassesPerLaunch);
-        ps.first_spp = first_buffer_spp + done;
-        memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
+    return for_each_launch(seeds, n, first_buffer_spp, kMaxPassesPerLaunch, [&](const PassSeeds& ps, const int32_t*) {
         if (int rc = fp.clock.open(r->ctx->stream)) return rc;
         if (int rc = launch(ps)) return rc;
         if (int rc = fp.clock.close(r->ctx->stream)) return rc;
         fp.last_launches += 1;
-    }
-    return CHUNKY_OK;
+        return (int)CHUNKY_OK;
+    });
 }
 
 // A first-hit pass on a group's render target: member 0 renders the caller's whole share (as chunky_render_preview does), so the
@@ -321,7 +325,15 @@ void group_close_rccl(chunky_ctx* g, bool abort);                               
 int group_gather(chunky_render* r);
 void scene_unref(chunky_scene* s);                                                      // capi_scene.hip
 int scene_view(chunky_scene* s, SceneView* v, bool want_emitters = false);
-int launch_pass_cap(const ShardView& T, int width, int height, size_t budget, int most);  // capi_render.hip
+// the scene as r's launches read it: scene_view with r's CHUNKY_OPT_BVH_CULL_BEHIND                  // capi_render.hip
+int target_scene_view(const chunky_render* r, SceneView* S, bool want_emitters = false);
+// what a call that folds staged samples needs of r from the camera on: render_pool for the scene and options as they are (*S: the scene)
+int needs_render_pool(const char* who, const chunky_render* r, SceneView* S);
+// r's staging array grown to hold the first launch of n passes over T at *cap passes per launch (pass_schedule.hpp stage_passes);
+// *cap comes back lower when memory was short.  The one place staging is allocated
+int stage_launches(const char* who, chunky_render* r, const ShardView& T, int n, int reserve, int* cap);
+// ... for the calls that fold (the seeds travel in the kernel arguments, no reserve hint, r->launch_cap is not touched): *cap is made here
+int stage_fold_launches(const char* who, chunky_render* r, const ShardView& T, int n, int* cap);
 RenderPlan render_plan(const chunky_render* r, const SceneView& S);                      // what plan_render decides for r's passes over S
 int check_extended_opts(const char* who, const RenderPlan& plan);
 bool biome_map(const chunky_render* r, BiomeMap* B);  // r tints by position: its scene has a biome map and CHUNKY_OPT_BIOME_TINT is 1 (then *B is the map)

@@ -4,16 +4,7 @@
 constexpr int kLightImages = 4;  // CHUNKY_LIGHT_SKY, _SUN, _EMITTERS, _ALL
 static_assert(CHUNKY_LIGHT_SKY == 0 && CHUNKY_LIGHT_SUN == 1 && CHUNKY_LIGHT_EMITTERS == 2 && CHUNKY_LIGHT_ALL == 3, "the images lie in this order");
 
-static float* light_image(const chunky_render* r, int which) { return (float*)((char*)r->lights.p + (size_t)which * aov_image_bytes(r)); }
-
-// the four images, allocated, zeroed, by the first chunky_render_light_passes
-static int lights_ensure(chunky_render* r) {
-    if (r->lights.p) return CHUNKY_OK;
-    const size_t bytes = kLightImages * aov_image_bytes(r) + 256;  // the images, the claim counter
-    HIP_TRY(r->lights.alloc(bytes));
-    HIP_TRY(hipMemsetAsync(r->lights.p, 0, bytes, r->ctx->stream));
-    return CHUNKY_OK;
-}
+static float* light_image(const chunky_render* r, int which) { return (float*)((char*)r->light_pass.images.p + (size_t)which * aov_image_bytes(r)); }
 
 // ---- emitter groups (chunky_render_light_set_emitter_groups): r->light_groups holds, in this order, the group images, the per-sample
 // sums (3 * groups floats per pixel), the touched words (one per pixel) and the table's bytes
@@ -46,16 +37,15 @@ static int light_passes(chunky_render* r, ShardView T, const int32_t* seeds, int
     const bool groups = r->light_table.n_groups > 0;
     if (groups && !std::isfinite(r->opts.emitter_scale))  // 0 * inf: the specification of a group would be NaN wherever another group is hit
         return fail(CHUNKY_E_STATE, "light_passes: emitter groups are set and CHUNKY_OPT_EMITTER_SCALE is not finite");
-    if (int rc = lights_ensure(r)) return rc;
+    if (int rc = r->light_pass.ensure(kLightImages * aov_image_bytes(r), r->ctx->stream)) return rc;
     if (groups) r->light_groups_rendered = true;
     r->light_pass.last_launches = 0;
     if (n == 0 || T.n_local <= 0) return CHUNKY_OK;
     SceneView S;
-    if (int rc = scene_view(r->scene, &S)) return rc;
-    S.bvh_cull = r->opts.bvh_cull;
+    if (int rc = target_scene_view(r, &S)) return rc;
     float* images[kLightImages];
     for (int g = 0; g < kLightImages; g++) images[g] = light_image(r, g);
-    int* counter = (int*)light_image(r, kLightImages);
+    int* counter = r->light_pass.counter();
     return first_hit_launches(r, r->light_pass, seeds, n, first_buffer_spp, [&](const PassSeeds& ps) {  // (each continues the running means)
         if (groups)
             HIP_TRY(launch_light_groups(r->kernel_variant, S, r->cam, r->opts, T, ps, images, light_group_images(r), counter, r->ctx->stream, &r->light_pass.choice));
@@ -74,7 +64,7 @@ extern "C" int chunky_render_light_read(chunky_render* r, int which, float* out,
     if (r && !r->parts.empty()) return chunky_render_light_read(r->parts[0], which, out, n);
     LOCK_RENDER(r);
     if (which < CHUNKY_LIGHT_SKY || which > CHUNKY_LIGHT_ALL) return fail(CHUNKY_E_INVALID, "light_read: unknown image %d", which);
-    const float* src = r->lights.p ? light_image(r, which) : nullptr;  // null before any pass
+    const float* src = r->light_pass.images.p ? light_image(r, which) : nullptr;  // null before any pass
     return read_floats("light_read", r, src, out, n, (int64_t)r->width * r->height * 3);
 }
 
@@ -84,7 +74,7 @@ extern "C" int chunky_render_light_mix(chunky_render* r, const float w[3], float
     if (!w || !std::isfinite(w[0]) || !std::isfinite(w[1]) || !std::isfinite(w[2])) return fail(CHUNKY_E_INVALID, "light_mix: three finite weights are needed");
     const int64_t need = (int64_t)r->width * r->height * 3;
     if (!out || n != need) return fail(CHUNKY_E_INVALID, "light_mix: need %lld floats, got %lld", (long long)need, (long long)n);
-    if (!r->lights.p) return fail(CHUNKY_E_STATE, "light_mix before any light pass");
+    if (!r->light_pass.images.p) return fail(CHUNKY_E_STATE, "light_mix before any light pass");
     if (!r->light_mix.p) HIP_TRY(r->light_mix.alloc(aov_image_bytes(r)));
     HIP_TRY(launch_light_mix(light_image(r, CHUNKY_LIGHT_SKY), light_image(r, CHUNKY_LIGHT_SUN), light_image(r, CHUNKY_LIGHT_EMITTERS), w, (float*)r->light_mix.p, need,
                              r->ctx->stream));
@@ -94,7 +84,7 @@ extern "C" int chunky_render_light_mix(chunky_render* r, const float w[3], float
 extern "C" int chunky_render_light_reset(chunky_render* r) {
     if (r && !r->parts.empty()) return chunky_render_light_reset(r->parts[0]);
     LOCK_RENDER(r);
-    if (r->lights.p) HIP_TRY(hipMemsetAsync(r->lights.p, 0, kLightImages * aov_image_bytes(r), r->ctx->stream));
+    if (r->light_pass.images.p) HIP_TRY(hipMemsetAsync(r->light_pass.images.p, 0, kLightImages * aov_image_bytes(r), r->ctx->stream));
     if (r->light_groups.p) HIP_TRY(hipMemsetAsync(r->light_groups.p, 0, (size_t)r->light_table.n_groups * aov_image_bytes(r), r->ctx->stream));
     return CHUNKY_OK;
 }
@@ -122,7 +112,7 @@ extern "C" int chunky_render_light_set_emitter_groups(chunky_render* r, int n_gr
 // CHUNKY_E_STATE unless groups are set and a pass has run with them
 static int light_groups_ready(const char* who, const chunky_render* r) {
     if (r->light_table.n_groups == 0) return fail(CHUNKY_E_STATE, "%s: no emitter groups are set", who);
-    if (!r->light_groups_rendered || !r->lights.p) return fail(CHUNKY_E_STATE, "%s before a light pass with the groups set", who);
+    if (!r->light_groups_rendered || !r->light_pass.images.p) return fail(CHUNKY_E_STATE, "%s before a light pass with the groups set", who);
     return CHUNKY_OK;
 }
 

@@ -3,28 +3,18 @@
 
 static size_t occlusion_plane_bytes(const chunky_render* r) { return (size_t)r->width * r->height * sizeof(float); }
 
-// AO then SUN, allocated, zeroed, by the first chunky_render_occlusion_passes
-static int occlusion_ensure(chunky_render* r) {
-    if (r->occlusion.p) return CHUNKY_OK;
-    const size_t bytes = 2 * occlusion_plane_bytes(r) + 256;  // the two images, the claim counter
-    HIP_TRY(r->occlusion.alloc(bytes));
-    HIP_TRY(hipMemsetAsync(r->occlusion.p, 0, bytes, r->ctx->stream));
-    return CHUNKY_OK;
-}
-
 // n passes over the pixel slots of shard T (a single-device target: its own share; member 0 of a group: the caller's share)
 static int occlusion_passes(chunky_render* r, ShardView T, const int32_t* seeds, int n, int first_buffer_spp, float ao_distance) {
     LOCK_RENDER(r);
     if (!r->have_camera) return fail(CHUNKY_E_STATE, "occlusion_passes before set_camera");
-    if (int rc = occlusion_ensure(r)) return rc;
+    if (int rc = r->occlusion_pass.ensure(2 * occlusion_plane_bytes(r), r->ctx->stream)) return rc;  // AO then SUN
     r->occlusion_pass.last_launches = 0;
     if (n == 0 || T.n_local <= 0) return CHUNKY_OK;
     SceneView S;
-    if (int rc = scene_view(r->scene, &S)) return rc;
-    S.bvh_cull = r->opts.bvh_cull;
-    float* ao = (float*)r->occlusion.p;
-    float* sun = (float*)((char*)r->occlusion.p + occlusion_plane_bytes(r));
-    int* counter = (int*)((char*)r->occlusion.p + 2 * occlusion_plane_bytes(r));
+    if (int rc = target_scene_view(r, &S)) return rc;
+    float* ao = (float*)r->occlusion_pass.images.p;
+    float* sun = (float*)((char*)r->occlusion_pass.images.p + occlusion_plane_bytes(r));
+    int* counter = r->occlusion_pass.counter();
     return first_hit_launches(r, r->occlusion_pass, seeds, n, first_buffer_spp, [&](const PassSeeds& ps) {  // (each continues the running means)
         HIP_TRY(launch_occlusion(r->kernel_variant, S, r->cam, r->opts, T, ps, ao, sun, ao_distance, counter, r->ctx->stream, &r->occlusion_pass.choice));
         return (int)CHUNKY_OK;
@@ -41,14 +31,15 @@ extern "C" int chunky_render_occlusion_read(chunky_render* r, int which, float* 
     if (r && !r->parts.empty()) return chunky_render_occlusion_read(r->parts[0], which, out, n);
     LOCK_RENDER(r);
     if (which != CHUNKY_AOV_AO && which != CHUNKY_AOV_SUN) return fail(CHUNKY_E_INVALID, "occlusion_read: unknown image %d", which);
-    const char* src = r->occlusion.p ? (const char*)r->occlusion.p + (which == CHUNKY_AOV_SUN ? occlusion_plane_bytes(r) : 0) : nullptr;  // null before any pass
+    const char* images = (const char*)r->occlusion_pass.images.p;
+    const char* src = images ? images + (which == CHUNKY_AOV_SUN ? occlusion_plane_bytes(r) : 0) : nullptr;  // null before any pass
     return read_floats("occlusion_read", r, src, out, n, (int64_t)r->width * r->height);
 }
 
 extern "C" int chunky_render_occlusion_reset(chunky_render* r) {
     if (r && !r->parts.empty()) return chunky_render_occlusion_reset(r->parts[0]);
     LOCK_RENDER(r);
-    if (r->occlusion.p) HIP_TRY(hipMemsetAsync(r->occlusion.p, 0, 2 * occlusion_plane_bytes(r), r->ctx->stream));
+    if (r->occlusion_pass.images.p) HIP_TRY(hipMemsetAsync(r->occlusion_pass.images.p, 0, 2 * occlusion_plane_bytes(r), r->ctx->stream));
     return CHUNKY_OK;
 }
 

@@ -337,19 +337,6 @@ int LaunchClock::take(float* ms_out, int* count_out) {
     return CHUNKY_OK;
 }
 
-// The most passes one launch over the pixel slots of T carries: render_pool stages every sample of a launch (12 bytes each) — at
-// most `budget` bytes of it, fewer than 2^31 samples, at most `most` passes (kMaxPassesPerLaunch: the seeds fit the kernel-argument
-// segment; kMaxPoolPasses for render_pool, which reads longer launches' seeds from device memory — a share of the image on several
-// GPUs then pays the end-of-launch tail once per 1024 passes instead of four times).  Below 1 when not even one pass fits.
-int launch_pass_cap(const ShardView& T, int width, int height, size_t budget, int most) {
-    const int64_t n_slots = (int64_t)(staging_floats(T, width, height, 1) / 3);  // padded tiles
-    if (n_slots <= 0) return most;
-    int64_t cap = (int64_t)(budget / 12) / n_slots;
-    const int64_t cap31 = ((int64_t)1 << 31) / n_slots - 1;
-    if (cap > cap31) cap = cap31;
-    return (int)(cap > most ? most : cap);
-}
-
 // What launch_render is going to run for r's passes over S (launch_plan.hpp), as far as it is known before a launch's pass count is:
 // the kernel family, whether a block shard needs the pixel list, the most passes per launch, the answer to the extended options
 RenderPlan render_plan(const chunky_render* r, const SceneView& S) {
@@ -361,6 +348,23 @@ RenderPlan render_plan(const chunky_render* r, const SceneView& S) {
 int check_extended_opts(const char* who, const RenderPlan& plan) {
     if (plan.ext_refusal == ExtRefusal::none) return CHUNKY_OK;
     return fail(CHUNKY_E_STATE, "%s: %s", who, ext_refusal_text(plan.ext_refusal));
+}
+
+int target_scene_view(const chunky_render* r, SceneView* S, bool want_emitters) {
+    if (int rc = scene_view(r->scene, S, want_emitters)) return rc;
+    S->bvh_cull = r->opts.bvh_cull;
+    return CHUNKY_OK;
+}
+
+int needs_render_pool(const char* who, const chunky_render* r, SceneView* S) {
+    if (!r->have_camera) return fail(CHUNKY_E_STATE, "%s before set_camera", who);
+    if (int rc = refuse_biome(who, r)) return rc;  // the folds run on the kernels that do not tint by position
+    if (int rc = target_scene_view(r, S, r->opts.nee != 0)) return rc;
+    const RenderPlan plan = render_plan(r, *S);
+    if (int rc = check_extended_opts(who, plan)) return rc;
+    if (plan.family != KernelFamily::pool)
+        return fail(CHUNKY_E_STATE, "%s: the scene or the options send this target to the fallback kernels, which stage no samples", who);
+    return CHUNKY_OK;
 }
 
 // Biome tints (chunky_scene_set_biome_tints): does r tint by position, and with which map
@@ -385,14 +389,45 @@ int read_floats(const char* who, chunky_render* r, const void* src, void* out, i
     return CHUNKY_OK;
 }
 
+// The staging array is sized once, before the cut, by the call's first launch: it is the longest, so this equals sizing before every
+// launch; and after a halving the cap is the launch that fitted, so every later launch fits as well.  It grows only (launches on the
+// stream are ordered, so one array serves them all, whichever call they come from).
+int stage_launches(const char* who, chunky_render* r, const ShardView& T, int n, int reserve, int* cap) {
+    const int launch = n < *cap ? n : *cap;
+    if (r->staging.bytes >= staging_floats(T, r->width, r->height, launch) * sizeof(float)) return CHUNKY_OK;
+    HIP_TRY(hipStreamSynchronize(r->ctx->stream));  // queued launches may still write the old array
+    r->staging.release();
+    size_t free_b = SIZE_MAX, total_b = 0;  // (a reserve is never more than half of what the device has left, stage_passes; unknown: tried)
+    if (reserve > launch) {
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = SIZE_MAX;
+        (void)hipGetLastError();
+    }
+    const StagedLaunch got = stage_passes(0, T, r->width, r->height, launch, *cap, reserve, free_b, [&](size_t bytes) {
+        if (hipMalloc(&r->staging.p, bytes) == hipSuccess) return true;
+        (void)hipGetLastError();
+        r->staging.p = nullptr;
+        return false;
+    });
+    r->staging.bytes = got.bytes;
+    if (got.passes < launch && launch > 1) *cap = std::max(1, got.passes);  // memory is short: shorter launches instead of a failed render
+    if (got.passes < 1)
+        return fail(CHUNKY_E_HIP, "%s: cannot allocate %zu bytes for one pass of staged samples", who, staging_floats(T, r->width, r->height, 1) * sizeof(float));
+    return CHUNKY_OK;
+}
+
+int stage_fold_launches(const char* who, chunky_render* r, const ShardView& T, int n, int* cap) {
+    *cap = launch_pass_cap(T, r->width, r->height, kStagingBytes, kMaxPassesPerLaunch);
+    if (*cap < 1) return fail(CHUNKY_E_INVALID, "%s: the image is too large to stage one pass", who);
+    return stage_launches(who, r, T, n, 0, cap);
+}
+
 extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp) {
     FAN_RENDER(r, chunky_render_passes(m_, seeds, n, first_buffer_spp));  // asynchronous on every member: the shares run side by side
     LOCK_RENDER(r);
     if (n < 0 || (n > 0 && !seeds) || first_buffer_spp < 0) return fail(CHUNKY_E_INVALID, "render_passes: bad arguments");
     if (!r->have_camera) return fail(CHUNKY_E_STATE, "render_passes before set_camera");
     SceneView S;
-    if (int rc = scene_view(r->scene, &S, r->opts.nee != 0)) return rc;
-    S.bvh_cull = r->opts.bvh_cull;
+    if (int rc = target_scene_view(r, &S, r->opts.nee != 0)) return rc;
     RenderPlan plan = render_plan(r, S);
     if (int rc = check_extended_opts("render_passes", plan)) return rc;
     BiomeMap biome;
@@ -423,46 +458,10 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
         r->launch_cap = std::max(1, launch_pass_cap(r->shard, r->width, r->height, kStagingBytes, most));  // sized by the tiles THIS rank renders
         r->launch_cap_most = most;
     }
-    for (int done = 0; done < n;) {
-        PassSeeds ps;
-        ps.n = (n - done) < r->launch_cap ? (n - done) : r->launch_cap;
-        size_t need = staging_floats(r->shard, r->width, r->height, ps.n) * sizeof(float);
-        if (r->staging.bytes < need) {  // grows to the largest launch seen; launches on the stream are ordered, so it is reused
-            HIP_TRY(hipStreamSynchronize(r->ctx->stream));
-            r->staging.release();
-            // chunky_render_run_ex climbs 1, 8, 64 ... passes per launch: one allocation for where it is going, not four
-            int ahead = r->reserve_passes < r->launch_cap ? r->reserve_passes : r->launch_cap;
-            if (ahead > kMaxPassesPerLaunch) ahead = kMaxPassesPerLaunch;  // (the pass loop's own launches stop there)
-            if (ahead > ps.n) {
-                size_t want = staging_floats(r->shard, r->width, r->height, ahead) * sizeof(float);
-                size_t free_b = 0, total_b = 0;  // never more than half of what the device has left: other targets and members live there too
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b / 2) want = 0;
-                (void)hipGetLastError();
-                if (want >= need && hipMalloc(&r->staging.p, want) == hipSuccess) {
-                    r->staging.bytes = want;
-                } else {
-                    (void)hipGetLastError();
-                    r->staging.p = nullptr;
-                }
-            }
-        }
-        if (r->staging.bytes < need) {
-            // memory is short: shorter launches instead of a failed render (each halving halves the array)
-            while (hipMalloc(&r->staging.p, need) != hipSuccess) {
-                (void)hipGetLastError();
-                r->staging.p = nullptr;
-                if (ps.n == 1) return fail(CHUNKY_E_HIP, "render_passes: cannot allocate %zu bytes for one pass of staged samples", need);
-                ps.n = (ps.n + 1) / 2;
-                r->launch_cap = ps.n;
-                need = staging_floats(r->shard, r->width, r->height, ps.n) * sizeof(float);
-            }
-            r->staging.bytes = need;
-        }
-        ps.first_spp = first_buffer_spp + done;
+    if (int rc = stage_launches("render_passes", r, r->shard, n, r->reserve_passes, &r->launch_cap)) return rc;  // (the cache remembers a halving)
+    return for_each_launch(seeds, n, first_buffer_spp, r->launch_cap, [&](const PassSeeds& ps, const int32_t* launch_seeds) {
         const int* seeds_dev = nullptr;
-        if (ps.n <= kMaxPassesPerLaunch) {
-            memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
-        } else {  // a long launch: its seeds go to device memory, in stream order behind the launch that read the buffer last
+        if (ps.n > kMaxPassesPerLaunch) {  // a long launch: its seeds go to device memory, in stream order behind the launch that read the buffer last
             if (!r->seed_buf.p) {
                 HIP_TRY(r->seed_buf.alloc((size_t)kMaxPoolPasses * 4));
             }
@@ -475,22 +474,16 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
             } else {
                 HIP_TRY(hipEventSynchronize(slot.copied));  // the copy that read this slot last (kSeedSlots launches ago)
             }
-            memcpy(slot.host, seeds + done, (size_t)ps.n * 4);
+            memcpy(slot.host, launch_seeds, (size_t)ps.n * 4);
             HIP_TRY(hipMemcpyAsync(r->seed_buf.p, slot.host, (size_t)ps.n * 4, hipMemcpyHostToDevice, r->ctx->stream));
             HIP_TRY(hipEventRecord(slot.copied, r->ctx->stream));
             seeds_dev = (const int*)r->seed_buf.p;
         }
         if (int rc = r->clock.open(r->ctx->stream)) return rc;
-        if (tinted)
-            HIP_TRY(launch_render_biome(r->kernel_variant, S, biome, r->cam, r->opts, r->shard, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream,
-                                        &r->last_choice, (float*)r->staging.p, seeds_dev));
-        else
-            HIP_TRY(launch_render(r->kernel_variant, S, r->cam, r->opts, r->shard, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream,
-                                  &r->last_choice, (float*)r->staging.p, seeds_dev));
-        if (int rc = r->clock.close(r->ctx->stream)) return rc;
-        done += ps.n;
-    }
-    return CHUNKY_OK;
+        HIP_TRY(launch_render_fold(r->kernel_variant, S, r->cam, r->opts, r->shard, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream, &r->last_choice,
+                                   (float*)r->staging.p, seeds_dev, StagedFold{}, tinted ? &biome : nullptr));
+        return r->clock.close(r->ctx->stream);
+    });
 }
 
 extern "C" int chunky_render_sync(chunky_render* r) {
@@ -590,8 +583,7 @@ extern "C" int chunky_render_preview(chunky_render* r, int32_t* argb_out) {
     if (!argb_out) return fail(CHUNKY_E_INVALID, "preview: NULL output");
     if (!r->have_camera) return fail(CHUNKY_E_STATE, "preview before set_camera");
     SceneView S;
-    if (int rc = scene_view(r->scene, &S)) return rc;
-    S.bvh_cull = r->opts.bvh_cull;
+    if (int rc = target_scene_view(r, &S)) return rc;
     DevBuf out;
     size_t bytes = (size_t)r->width * r->height * 4;
     HIP_TRY(out.alloc(bytes));
@@ -616,8 +608,7 @@ extern "C" int chunky_render_trace_records(chunky_render* r, int32_t seed, const
     for (int i = 0; i < n; i++)
         if (gids[i] < 0 || gids[i] >= r->width * r->height) return fail(CHUNKY_E_INVALID, "trace_records: gid %d outside the image", gids[i]);
     SceneView S;
-    if (int rc = scene_view(r->scene, &S)) return rc;
-    S.bvh_cull = r->opts.bvh_cull;
+    if (int rc = target_scene_view(r, &S)) return rc;
     DevBuf dg, dr, dc, dq;
     hipStream_t st = r->ctx->stream;
     HIP_TRY(dg.upload(gids, (size_t)n * 4, st));

@@ -31,15 +31,7 @@ extern "C" int chunky_render_robust_begin(chunky_render* r, int n_buckets) {
 // what a robust pass needs of the target: the state, a camera, and render_pool for the scene and options as they are
 static int robust_state(const char* who, chunky_render* r, SceneView* S) {
     if (!r->rb_m) return fail(CHUNKY_E_STATE, "%s before render_robust_begin", who);
-    if (!r->have_camera) return fail(CHUNKY_E_STATE, "%s before set_camera", who);
-    if (int rc = refuse_biome(who, r)) return rc;  // the bucket fold runs on the kernels that do not tint by position
-    if (int rc = scene_view(r->scene, S, r->opts.nee != 0)) return rc;
-    S->bvh_cull = r->opts.bvh_cull;
-    const RenderPlan plan = render_plan(r, *S);
-    if (int rc = check_extended_opts(who, plan)) return rc;
-    if (plan.family != KernelFamily::pool)
-        return fail(CHUNKY_E_STATE, "%s: the scene or the options send this target to the fallback kernels, which stage no samples", who);
-    return CHUNKY_OK;
+    return needs_render_pool(who, r, S);
 }
 
 extern "C" int chunky_render_robust_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp) {
@@ -61,20 +53,9 @@ extern "C" int chunky_render_robust_passes(chunky_render* r, const int32_t* seed
         return CHUNKY_OK;
     }
     hipStream_t st = r->ctx->stream;
-    // the most passes one launch carries (the seeds travel in the kernel-argument segment) and the staging array grown to hold it;
-    // it grows only: chunky_render_passes reuses it, and r->launch_cap is not touched
-    const int cap = launch_pass_cap(T, r->width, r->height, kStagingBytes, kMaxPassesPerLaunch);
-    if (cap < 1) return fail(CHUNKY_E_INVALID, "render_robust_passes: the image is too large to stage one pass");
-    const size_t need = staging_floats(T, r->width, r->height, n < cap ? n : cap) * sizeof(float);
-    if (r->staging.bytes < need) {
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(r->staging.alloc(need));
-    }
-    for (int done = 0; done < n;) {
-        PassSeeds ps;
-        ps.n = (n - done) < cap ? (n - done) : cap;
-        ps.first_spp = first_buffer_spp + done;
-        memcpy(ps.seed, seeds + done, (size_t)ps.n * 4);
+    int cap = 0;
+    if (int rc = stage_fold_launches("render_robust_passes", r, T, n, &cap)) return rc;
+    return for_each_launch(seeds, n, first_buffer_spp, cap, [&](const PassSeeds& ps, const int32_t*) {
         StagedFold fold;
         fold.kind = StagedFold::buckets;
         fold.bucket_images = (float*)r->rb_buckets.p;
@@ -85,9 +66,8 @@ extern "C" int chunky_render_robust_passes(chunky_render* r, const int32_t* seed
                                    (float*)r->staging.p, nullptr, fold));
         if (int rc = r->rb_clock.close(st)) return rc;
         r->rb_count += ps.n;  // (per launch: a launch that failed leaves the count of those that ran)
-        done += ps.n;
-    }
-    return CHUNKY_OK;
+        return (int)CHUNKY_OK;
+    });
 }
 
 extern "C" int chunky_render_robust_read_bucket(chunky_render* r, int b, float* out, int64_t n_floats, int32_t* count) {
@@ -148,7 +128,7 @@ extern "C" int chunky_render_robust_denoise(chunky_render* r, const chunky_robus
     LOCK_RENDER(r);
     if (r->shard.world > 1)
         return fail(CHUNKY_E_STATE, "render_robust_denoise: this target holds rank %d of %d of the image, not all of it", r->shard.rank, r->shard.world);
-    if (!r->aov.p) return fail(CHUNKY_E_STATE, "render_robust_denoise before any AOV pass");
+    if (!r->aov_pass.images.p) return fail(CHUNKY_E_STATE, "render_robust_denoise before any AOV pass");
     if (int rc = robust_resolve("render_robust_denoise", r, p, false)) return rc;
     return render_denoise(r, K, form, (const float*)r->rb_out.p, out);
 }

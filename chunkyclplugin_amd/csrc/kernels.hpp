@@ -7,6 +7,7 @@
 #include <atomic>
 
 #include "launch_plan.hpp"  // RenderOpts, the launch limits, pool_tiles: what the launch planner shares with the launchers
+#include "pass_schedule.hpp"  // PassSeeds, staging_floats: how passes become launches
 #include "shard_map.hpp"  // ShardView, FastDiv: the host arithmetic of the shard-to-pixel map
 
 struct DnCoeffs;  // denoise_spec.h
@@ -30,15 +31,6 @@ struct HitRecord {
     float point[3];
 };
 
-// Seeds of the passes one launch runs, passed by value in the kernel-argument segment (wave-uniform
-// scalar loads, no per-launch host->device copy): pass k uses seed[k] and bufferSpp first_spp + k
-// (OpenClPathTracingRenderer.java:106-109).
-// (kMaxPassesPerLaunch, and render_pool's kMaxPoolPasses: launch_plan.hpp)
-struct PassSeeds {
-    int n, first_spp;
-    int seed[kMaxPassesPerLaunch];
-};
-
 // What launch_render picked for a launch (chunky_render_kernel_info): the tests assert that the instantiation they
 // mean to compare with the oracle is the one that ran.
 struct KernelChoice {
@@ -51,10 +43,6 @@ struct KernelChoice {
     int sorted;  // render_pool: full cubes and model blocks tested in phases of their own
 };
 constexpr int kChoiceBiome = 2;  // KernelChoice::ext, and bit 1 of AovChoice::bvh: the launch ran a kernel compiled with CHUNKY_BIOME_TINT
-// staging floats render_pool needs for a launch of n passes over this rank's tiles
-inline size_t staging_floats(const ShardView& T, int width, int height, int n_passes) {
-    return 3 * (size_t)pool_tiles(T, width, height) * kSampleTile * (size_t)n_passes;
-}
 
 // compute units of the CURRENT device (cached per device index: members of a group and threads of a host may sit on different GPUs)
 inline hipError_t current_device_cus(int* n_cu) {
@@ -105,18 +93,16 @@ struct StagedFold {
 };
 // launch_render with the launch's samples folded as `fold` says.  A fold other than `none` is render_pool's only
 // (hipErrorNotSupported under the other kernels, which stage no samples); kind == none is launch_render.
+// With a biome map (tints by block position) the launch runs what plan_biome (launch_plan.hpp) makes of
+// plan_render's plan, on the kernels compiled with CHUNKY_BIOME_TINT (render_pool_biome.hip, render_pool_biome_bvh.hip,
+// render_biome.hip); hipErrorNotSupported for what plan_biome refuses, and for a map with a fold other than `none`.
 hipError_t launch_render_fold(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
-                              float* staging, const int* seeds_dev, const StagedFold& fold);
+                              float* staging, const int* seeds_dev, const StagedFold& fold, const BiomeMap* biome = nullptr);
 // the kernels behind render_pool (render_fallback.hip): render_waves, render_lanes, as `plan` names them
 hipError_t launch_fallback(const RenderPlan& plan, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                            const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen);
-// Biome tints by block position: launch_render for a scene with a biome map — what plan_biome (launch_plan.hpp) makes of
-// plan_render's plan, on the kernels compiled with CHUNKY_BIOME_TINT (render_pool_biome.hip, render_pool_biome_bvh.hip, render_biome.hip);
-// hipErrorNotSupported for what plan_biome refuses.  The twins of launch_trace_records, launch_preview, launch_aov and launch_aov_ex follow.
-hipError_t launch_render_biome(int variant, const SceneView& S, const BiomeMap& B, const CameraView& C, const RenderOpts& O, const ShardView& T,
-                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen, float* staging,
-                               const int* seeds_dev);
+// The kernels that tint by position: render_lanes for launch_render_fold, and the twins of launch_trace_records, launch_preview, launch_aov and launch_aov_ex
 hipError_t launch_lanes_biome(const RenderPlan& plan, const SceneView& S, const BiomeMap& B, const CameraView& C, const RenderOpts& O,
                               const ShardView& T, const PassSeeds& P, float* res, hipStream_t stream, KernelChoice* chosen);
 hipError_t launch_trace_records_biome(int variant, const SceneView& S, const BiomeMap& B, const CameraView& C, const RenderOpts& O, int seed,

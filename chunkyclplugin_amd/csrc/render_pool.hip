@@ -669,39 +669,25 @@ hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, c
 }
 hipError_t launch_render_fold(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
-                              float* staging, const int* seeds_dev, const StagedFold& fold) {
-    const RenderPlan plan = plan_render(variant, scene_facts(S), O, C.projector_type, T, P.n, work_counter && staging, seeds_dev != nullptr, fold.kind != StagedFold::none);
+                              float* staging, const int* seeds_dev, const StagedFold& fold, const BiomeMap* biome) {
+    if (biome && fold.kind != StagedFold::none) return hipErrorNotSupported;  // the folds run on the kernels that do not tint by position
+    RenderPlan plan = plan_render(variant, scene_facts(S), O, C.projector_type, T, P.n, work_counter && staging, seeds_dev != nullptr, fold.kind != StagedFold::none);
     switch (plan.status) {
         case PlanStatus::invalid_value: return hipErrorInvalidValue;
         case PlanStatus::not_supported: return hipErrorNotSupported;
         default: break;
     }
+    if (biome) {  // a scene with a biome map: plan_render's plan as plan_biome maps it
+        const BiomePlan b = plan_biome(plan);
+        if (b.refusal != BiomeRefusal::none) return hipErrorNotSupported;  // (the C API has refused it with the reason before it came here)
+        plan = b.plan;
+    }
     if (plan.family == KernelFamily::pool)
-        return launch_pool(plan, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr, fold);
-    if (plan.needs_list) {  // a shard of 16 x 16 blocks: the fallback kernels take the rank's pixels as a list
-        ShardView F = T;
-        F.n_local = T.n_list;
-        return launch_fallback(plan, S, C, O, F, P, res, work_counter, stream, chosen);
-    }
-    return launch_fallback(plan, S, C, O, T, P, res, work_counter, stream, chosen);
-}
-
-// launch_render for a scene with a biome map (kernels.hpp): plan_render's plan as plan_biome maps it
-hipError_t launch_render_biome(int variant, const SceneView& S, const BiomeMap& B, const CameraView& C, const RenderOpts& O, const ShardView& T,
-                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen, float* staging,
-                               const int* seeds_dev) {
-    const BiomePlan b = plan_biome(plan_render(variant, scene_facts(S), O, C.projector_type, T, P.n, work_counter && staging, seeds_dev != nullptr, false));
-    switch (b.plan.status) {
-        case PlanStatus::invalid_value: return hipErrorInvalidValue;
-        case PlanStatus::not_supported: return hipErrorNotSupported;
-        default: break;
-    }
-    if (b.refusal != BiomeRefusal::none) return hipErrorNotSupported;  // (the C API has refused it with the reason before it came here)
-    if (b.plan.family == KernelFamily::pool)
-        return launch_pool(b.plan, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr, StagedFold{}, &B);
+        return launch_pool(plan, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr, fold, biome);
     ShardView F = T;
-    if (b.plan.needs_list) F.n_local = T.n_list;  // a shard of 16 x 16 blocks: the rank's pixels as a list (launch_render_fold)
-    return launch_lanes_biome(b.plan, S, B, C, O, F, P, res, stream, chosen);
+    if (plan.needs_list) F.n_local = T.n_list;  // a shard of 16 x 16 blocks: the fallback kernels take the rank's pixels as a list
+    if (biome) return launch_lanes_biome(plan, S, *biome, C, O, F, P, res, stream, chosen);
+    return launch_fallback(plan, S, C, O, F, P, res, work_counter, stream, chosen);
 }
 
 hipError_t launch_gather(bool pack, const ShardView& T, int width, int height, float* fb, float* packed, hipStream_t stream) {

@@ -108,7 +108,7 @@ def test_every_list_a_pregenerated_camera_renders_is_a_derangement():
 
 
 # ---- launch splitting -------------------------------------------------------------------------------------------------------------
-# adaptive_launch (csrc/capi_adaptive.hip) cuts a round into launches of at most launch_pass_cap(T, ..., kStagingBytes, kMaxPassesPerLaunch)
+# for_each_launch (csrc/pass_schedule.hpp) cuts an adaptive round into launches of at most launch_pass_cap(T, ..., kStagingBytes, kMaxPassesPerLaunch)
 # passes: min(256, 8 GiB / 12 bytes / padded slots, 2^31 / padded slots - 1).  A list of 5 pixels pads to one tile of 256 slots, so
 # the cap is kMaxPassesPerLaunch = 256 (the seeds of a launch travel in the kernel arguments) and 257 passes make two launches, of
 # 256 and of 1 pass; the staging budget never binds at a size a test could afford (8 GiB / 12 / 256 passes = 2.8 million slots).
