@@ -21,6 +21,7 @@
 #include "capi_error.hpp"
 #include "canvas_host.hpp"
 #include "capi_host.hpp"
+#include "fog_host.hpp"
 #include "kernels.hpp"
 #include "lights_host.hpp"
 #include "rccl_dyn.hpp"
@@ -171,6 +172,7 @@ struct chunky_render {
     RenderOpts opts{256, 5, 13.0f, -1, 1, 0, 0};
     int kernel_variant = 0;
     int biome_tint = 1;  // CHUNKY_OPT_BIOME_TINT: 0 = this target ignores the scene's biome map
+    FogSettings fog;     // chunky_render_set_fog: the ground-fog layer of chunky_render_passes; density 0 (default) = none
     ShardView shard{0, 1, 256, 0};
     DevBuf own_fb, work_counter;
     DevBuf staging;  // render_pool: one launch's samples, [tile of 256 slots][pass][slot][3] floats
@@ -338,6 +340,10 @@ RenderPlan render_plan(const chunky_render* r, const SceneView& S);             
 int check_extended_opts(const char* who, const RenderPlan& plan);
 bool biome_map(const chunky_render* r, BiomeMap* B);  // r tints by position: its scene has a biome map and CHUNKY_OPT_BIOME_TINT is 1 (then *B is the map)
 int refuse_biome(const char* who, const chunky_render* r);  // CHUNKY_E_STATE for a call that does not tint by position while r does
+bool fog_params_of(const chunky_render* r, FogParams* F);  // r has a fog layer (then *F holds it as the fog kernels take it)      // capi_fog.hip
+int refuse_fog(const char* who, const chunky_render* r);  // CHUNKY_E_STATE for a call that has no fog kernels while r has a layer
+// what plan_fog decides for r's passes over S, as render_plan does for a target without fog
+FogPlan fog_plan(const chunky_render* r, const SceneView& S);
 int read_floats(const char* who, chunky_render* r, const void* src, void* out, int64_t n, int64_t need);
 int first_hit_kernel_time(chunky_render* r, FirstHitPass chunky_render::*pass, float* total_ms, int* launches);  // capi_aov.hip
 int first_hit_kernel_info(const char* who, chunky_render* r, FirstHitPass chunky_render::*pass, int32_t out4[4]);

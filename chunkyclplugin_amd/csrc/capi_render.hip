@@ -359,6 +359,7 @@ int target_scene_view(const chunky_render* r, SceneView* S, bool want_emitters) 
 int needs_render_pool(const char* who, const chunky_render* r, SceneView* S) {
     if (!r->have_camera) return fail(CHUNKY_E_STATE, "%s before set_camera", who);
     if (int rc = refuse_biome(who, r)) return rc;  // the folds run on the kernels that do not tint by position
+    if (int rc = refuse_fog(who, r)) return rc;    // ... and that have no medium
     if (int rc = target_scene_view(r, S, r->opts.nee != 0)) return rc;
     const RenderPlan plan = render_plan(r, *S);
     if (int rc = check_extended_opts(who, plan)) return rc;
@@ -429,9 +430,16 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
     SceneView S;
     if (int rc = target_scene_view(r, &S, r->opts.nee != 0)) return rc;
     RenderPlan plan = render_plan(r, S);
+    FogParams fog;
+    const bool foggy = fog_params_of(r, &fog);
+    if (foggy) {  // the fog kernels (launch_plan.hpp plan_fog), or a refusal that says why: never an image of clear air
+        const FogPlan f = fog_plan(r, S);
+        if (f.refusal != FogRefusal::none) return fail(CHUNKY_E_STATE, "render_passes: %s", fog_refusal_text(f.refusal));
+        plan = f.plan;  // (render_pool: no pixel list, launches of up to kMaxPoolPasses)
+    }
     if (int rc = check_extended_opts("render_passes", plan)) return rc;
     BiomeMap biome;
-    const bool tinted = biome_map(r, &biome);
+    const bool tinted = !foggy && biome_map(r, &biome);
     if (tinted) {  // the kernels that tint by position (launch_plan.hpp plan_biome), or a refusal that says why: never an untinted image
         RenderPlan asked = plan;
         asked.status = PlanStatus::ok;  // (a block shard's pixel list is made below; what a launch cannot carry is refused there)
@@ -481,7 +489,7 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
         }
         if (int rc = r->clock.open(r->ctx->stream)) return rc;
         HIP_TRY(launch_render_fold(r->kernel_variant, S, r->cam, r->opts, r->shard, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream, &r->last_choice,
-                                   (float*)r->staging.p, seeds_dev, StagedFold{}, tinted ? &biome : nullptr));
+                                   (float*)r->staging.p, seeds_dev, StagedFold{}, tinted ? &biome : nullptr, foggy ? &fog : nullptr));
         return r->clock.close(r->ctx->stream);
     });
 }
@@ -544,6 +552,15 @@ extern "C" int chunky_render_kernel_info(chunky_render* r, int32_t out8[8]) {
                 const bool pool = b.plan.family == KernelFamily::pool;
                 out8[0] = b.plan.tree, out8[1] = pool ? 1 : 0, out8[2] = b.plan.bvh ? 1 : 0, out8[4] = pool ? b.plan.park : -1, out8[5] = kChoiceBiome;
             }
+        }
+    }
+    if (r->last_choice.blocks == 0 && r->have_camera && fog_params_of(r, nullptr)) {
+        // before the first launch of a target with a fog layer: the fog instantiation its next launch will run
+        SceneView S;
+        if (scene_view(r->scene, &S, false) == CHUNKY_OK) {
+            const FogPlan f = fog_plan(r, S);
+            if (f.plan.status == PlanStatus::ok && f.refusal == FogRefusal::none)
+                out8[0] = f.plan.tree, out8[1] = 1, out8[2] = f.plan.bvh ? 1 : 0, out8[4] = f.plan.park, out8[5] = kChoiceFog;
         }
     }
     if (r->launch_cap > 0) {

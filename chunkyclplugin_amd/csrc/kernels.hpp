@@ -17,6 +17,7 @@ namespace chunky {
 struct SceneView;
 struct CameraView;
 struct BiomeMap;  // rt_device.hpp
+struct FogParams;
 
 constexpr int kMaxTraces = 10;        // 5 path segments x (main + shadow trace)
 
@@ -39,10 +40,11 @@ struct KernelChoice {
     int bvh;     // entity-BVH phases compiled in
     int blocks;  // workgroups launched
     int pool;    // render_pool: paths parked per wave beside the 64 in its lanes; -1 = another kernel
-    int ext;     // 1: the extended integrator (CHUNKY_OPT_SUN_SAMPLING / _EMITTERS / _BSDF / _EMITTER_NEE at non-default values); kChoiceBiome: a biome-tint instantiation
+    int ext;     // 1: the extended integrator (CHUNKY_OPT_SUN_SAMPLING / _EMITTERS / _BSDF / _EMITTER_NEE at non-default values); kChoiceBiome: a biome-tint instantiation; kChoiceFog: a ground-fog instantiation (of the extended integrator)
     int sorted;  // render_pool: full cubes and model blocks tested in phases of their own
 };
 constexpr int kChoiceBiome = 2;  // KernelChoice::ext, and bit 1 of AovChoice::bvh: the launch ran a kernel compiled with CHUNKY_BIOME_TINT
+constexpr int kChoiceFog = 3;    // KernelChoice::ext: the launch ran a kernel compiled with CHUNKY_FOG (render_pool_fog.hip, render_pool_fog_bvh.hip)
 
 // compute units of the CURRENT device (cached per device index: members of a group and threads of a host may sit on different GPUs)
 inline hipError_t current_device_cus(int* n_cu) {
@@ -96,9 +98,12 @@ struct StagedFold {
 // With a biome map (tints by block position) the launch runs what plan_biome (launch_plan.hpp) makes of
 // plan_render's plan, on the kernels compiled with CHUNKY_BIOME_TINT (render_pool_biome.hip, render_pool_biome_bvh.hip,
 // render_biome.hip); hipErrorNotSupported for what plan_biome refuses, and for a map with a fold other than `none`.
+// With `fog` (the ground-fog layer) the launch runs plan_fog's plan on the kernels compiled with CHUNKY_FOG;
+// hipErrorNotSupported for what plan_fog refuses — a biome map among it — and for a fold other than `none`.
 hipError_t launch_render_fold(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
-                              float* staging, const int* seeds_dev, const StagedFold& fold, const BiomeMap* biome = nullptr);
+                              float* staging, const int* seeds_dev, const StagedFold& fold, const BiomeMap* biome = nullptr,
+                              const FogParams* fog = nullptr);
 // the kernels behind render_pool (render_fallback.hip): render_waves, render_lanes, as `plan` names them
 hipError_t launch_fallback(const RenderPlan& plan, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                            const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen);

@@ -22,8 +22,9 @@ int stack_entries(const SceneFacts& F) {
 size_t stack_lds_bytes(const SceneFacts& F, int block) { return (size_t)stack_entries(F) * block * sizeof(int); }
 
 // render_pool runs: always without entity BVHs; with them when they could be re-laid out (rt_device.hpp bvh_rec / tri_rec)
-static NotPool why_not_pool(int variant, const SceneFacts& F, const RenderOpts& O, bool have_queue_and_staging) {
-    const bool bvh = has_bvh(F), ext = opts_extended(O);
+// (force_ext: plan_fog's launches run the extended family with every option at its default)
+static NotPool why_not_pool(int variant, const SceneFacts& F, const RenderOpts& O, bool have_queue_and_staging, bool force_ext) {
+    const bool bvh = has_bvh(F), ext = force_ext || opts_extended(O);
     if (variant & 2) return NotPool::lanes_forced;
     if (variant & 8) return NotPool::waves_forced;
     if (!have_queue_and_staging) return NotPool::no_queue;
@@ -43,8 +44,8 @@ static NotPool why_not_pool(int variant, const SceneFacts& F, const RenderOpts& 
 }
 
 // the extended light-transport options exist in render_pool's default instantiations only
-static ExtRefusal ext_refusal(int variant, const SceneFacts& F, const RenderOpts& O, NotPool why) {
-    if (!opts_extended(O)) return ExtRefusal::none;
+static ExtRefusal ext_refusal(int variant, const SceneFacts& F, const RenderOpts& O, NotPool why, bool force_ext) {
+    if (!force_ext && !opts_extended(O)) return ExtRefusal::none;
     if ((variant & (1 | 2 | 4 | 8)) || (has_bvh(F) && !F.bvh_records)) return ExtRefusal::default_kernel;
     if (!F.wide) return ExtRefusal::wide_tree;  // their instantiations walk the re-laid-out tree only (an octree deeper than 15 levels has none)
     // the fallback kernels never read these options: a set render_pool refuses (max depth 255) would render the reference's transport
@@ -148,11 +149,11 @@ static void plan_fallback(RenderPlan& p, int variant, const SceneFacts& F, int n
     if (group > 1) p.lds += (size_t)(kLaunchBlock / group) * (2 * ring_size(group) * 16 + 64);
 }
 
-RenderPlan plan_render(int variant, const SceneFacts& F, const RenderOpts& O, int projector_type, const ShardView& T, int n_passes,
-                       bool have_queue_and_staging, bool have_seeds_dev, bool want_staged_fold) {
+static RenderPlan plan_render_as(int variant, const SceneFacts& F, const RenderOpts& O, int projector_type, const ShardView& T, int n_passes,
+                                 bool have_queue_and_staging, bool have_seeds_dev, bool want_staged_fold, bool force_ext) {
     RenderPlan p{};
-    p.why = why_not_pool(variant, F, O, have_queue_and_staging);
-    p.ext_refusal = ext_refusal(variant, F, O, p.why);
+    p.why = why_not_pool(variant, F, O, have_queue_and_staging, force_ext);
+    p.ext_refusal = ext_refusal(variant, F, O, p.why, force_ext);
     const bool pool = p.why == NotPool::none;
     p.family = pool ? KernelFamily::pool : (((variant & 2) || !have_queue_and_staging) ? KernelFamily::lanes : KernelFamily::waves);
     // render_pool takes up to kMaxPoolPasses per launch, the other kernels what the kernel-argument segment holds
@@ -173,13 +174,18 @@ RenderPlan plan_render(int variant, const SceneFacts& F, const RenderOpts& O, in
     if (p.status != PlanStatus::ok) return p;  // refused: no kernel is named
     p.bvh = has_bvh(F);
     p.depth = stack_entries(F);
-    p.ext = opts_extended(O);
+    p.ext = force_ext || opts_extended(O);
     p.proj = pool && projector_type > 0;  // a projected camera: proj::render_pool, same template arguments
     if (pool)
         plan_pool(p, variant, F);
     else
         plan_fallback(p, variant, F, p.needs_list ? T.n_list : T.n_local, n_passes, have_queue_and_staging);
     return p;
+}
+
+RenderPlan plan_render(int variant, const SceneFacts& F, const RenderOpts& O, int projector_type, const ShardView& T, int n_passes,
+                       bool have_queue_and_staging, bool have_seeds_dev, bool want_staged_fold) {
+    return plan_render_as(variant, F, O, projector_type, T, n_passes, have_queue_and_staging, have_seeds_dev, want_staged_fold, false);
 }
 
 FirstHitPlan plan_first_hit(int variant, const SceneFacts& F) {
@@ -216,6 +222,38 @@ BiomePlan plan_biome(const RenderPlan& in) {
     p.group = 0;
     p.lds = (size_t)p.depth * kLaunchBlock * sizeof(int);
     return b;
+}
+
+// Ground fog: the extended family, forced, on the kernels compiled with CHUNKY_FOG (launch_plan.hpp has the table)
+FogPlan plan_fog(int variant, const SceneFacts& F, const RenderOpts& O, int projector_type, const ShardView& T, int n_passes,
+                 bool have_queue_and_staging, bool have_seeds_dev, bool biome_tinted) {
+    FogPlan f{plan_render_as(variant, F, O, projector_type, T, n_passes, have_queue_and_staging, have_seeds_dev, false, true), FogRefusal::none};
+    const RenderPlan& p = f.plan;
+    if (biome_tinted) f.refusal = FogRefusal::biome;
+    else if (variant & 4) f.refusal = FogRefusal::stats;
+    else if (variant & (1 | 2 | 8)) f.refusal = FogRefusal::rig_bits;
+    else if (projector_type > 0) f.refusal = FogRefusal::projected;
+    else if (O.max_depth > 254) f.refusal = FogRefusal::max_depth;
+    else if (!F.wide) f.refusal = FogRefusal::wide_tree;
+    else if (has_bvh(F) && !F.bvh_records) f.refusal = FogRefusal::bvh_records;
+    else if (p.why != NotPool::none || p.ext_refusal != ExtRefusal::none) f.refusal = FogRefusal::not_pool;  // (no work counter, arrays beyond 32-bit offsets)
+    // (what is left is a render_pool plan of the extended family — plan_pool: trees 17 / 18 / -1, 32 parked paths, 16 with entity BVHs —
+    // or one plan_render refused by its status: a launch too long for its seeds)
+    return f;
+}
+
+const char* fog_refusal_text(FogRefusal r) {
+    switch (r) {
+        case FogRefusal::biome: return "fog: not with a biome map on the scene (chunky_scene_set_biome_tints); set CHUNKY_OPT_BIOME_TINT to 0, remove the map or turn fog off";
+        case FogRefusal::stats: return "fog: the phase-statistics kernels (CHUNKY_OPT_KERNEL bit 2) have no fog; clear the bit or turn fog off";
+        case FogRefusal::rig_bits: return "fog: needs the default kernel (CHUNKY_OPT_KERNEL bits 0, 1 and 3 clear): the fallback kernels and the reference-layout walk have no fog";
+        case FogRefusal::projected: return "fog: projected cameras have no fog kernel; pass pre-generated rays (chunky_render_set_rays) or turn fog off";
+        case FogRefusal::max_depth: return "fog: needs max depth <= 254 (CHUNKY_OPT_MAX_DEPTH)";
+        case FogRefusal::wide_tree: return "fog: needs an octree the wide re-layout takes (depth <= 15)";
+        case FogRefusal::bvh_records: return "fog: the scene's entity BVHs could not be re-laid out; the fallback kernels have no fog";
+        case FogRefusal::not_pool: return "fog: the scene or the target sends this launch to the fallback kernels, which have no fog";
+        default: return "";
+    }
 }
 
 const char* biome_refusal_text(BiomeRefusal r) {

@@ -168,6 +168,23 @@ struct BiomePlan {
 BiomePlan plan_biome(const RenderPlan& p);
 const char* biome_refusal_text(BiomeRefusal r);
 
+// Ground fog: a target with a fog layer (chunky_render_set_fog) runs the EXTENDED family whatever its options say —
+// with every light-transport option at its default too — on the kernels compiled with CHUNKY_FOG (rt_device.hpp): render_pool for the
+// pinhole and pre-generated cameras, tree forms 17, 18 and -1, 32 parked paths without entity BVHs and 16 with them
+// (CHUNKY_POOL_FOG_INSTANCES, CHUNKY_POOL_FOG_BVH_INSTANCES).  plan_fog is plan_render with that family forced.  Everything else is
+// refused — FogPlan::refusal says why, the C API answers CHUNKY_E_STATE with fog_refusal_text — and never rendered without fog: a scene
+// whose biome map the target applies, phase statistics, the rig bits that pick another walk or kernel, projected cameras (pre-generated
+// rays serve every projection), max depth above 254, a scene without a wide tree or whose entity BVHs could not be re-laid out, and
+// whatever else sends a launch to the fallback kernels.  A plan plan_render refused (status != ok) comes back with that status.
+enum class FogRefusal : int { none = 0, biome, stats, rig_bits, projected, max_depth, wide_tree, bvh_records, not_pool };
+struct FogPlan {
+    RenderPlan plan;
+    FogRefusal refusal;
+};
+FogPlan plan_fog(int variant, const SceneFacts& F, const RenderOpts& O, int projector_type, const ShardView& T, int n_passes,
+                 bool have_queue_and_staging, bool have_seeds_dev, bool biome_tinted);
+const char* fog_refusal_text(FogRefusal r);
+
 }  // namespace chunky
 
 // ---------------------------------------------------------------------------------------------
@@ -239,6 +256,12 @@ const char* biome_refusal_text(BiomeRefusal r);
 #define CHUNKY_POOL_BIOME_BVH_INSTANCES(X)                                                                                             \
     X(17, 32, false, true, false, false) X(-1, 32, false, true, false, false)                                                          \
     X(17, 16, false, true, false, false) X(-1, 16, false, true, false, false)
+// X(TREE, K, STATS, BVH, EXT, SORT) of render_pool compiled with CHUNKY_FOG (render_pool_fog.hip, render_pool_fog_bvh.hip): what plan_fog
+// names — the extended instantiations of the plain lists, once more
+#define CHUNKY_POOL_FOG_INSTANCES(X)                                                                                                   \
+    X(17, 32, false, false, true, false) X(18, 32, false, false, true, false) X(-1, 32, false, false, true, false)
+#define CHUNKY_POOL_FOG_BVH_INSTANCES(X)                                                                                               \
+    X(17, 16, false, true, true, false) X(18, 16, false, true, true, false) X(-1, 16, false, true, true, false)
 // X(TREE, BVH) of the first-hit kernels (first_hit_pass.hpp first_hit_kernel, occlusion.hip occlusion_kernel, lights.hip light_kernel)
 #define CHUNKY_FIRST_HIT_INSTANCES(X)                                                                                                  \
     X(0, true) X(17, true) X(18, true) X(-1, true)                                                                                     \

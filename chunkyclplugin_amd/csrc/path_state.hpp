@@ -331,6 +331,9 @@ struct LaneState {
     // emitter shadow ray — the light that ray brings if it is free, and whether the vertex before sampled the emitters
     unsigned tkind : 2;
     unsigned after_nee : 1;
+#if CHUNKY_FOG
+    unsigned medium : 1;  // the vertex whose shadow ray is being traced is a medium vertex: bit 27 of a parked record's flag word
+#endif
     f3 pend;
     // main record
     Hit h;

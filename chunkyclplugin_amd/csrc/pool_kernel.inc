@@ -45,6 +45,9 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
     L.pid = lane;
     L.tkind = 0;
     L.after_nee = false;
+#if CHUNKY_FOG
+    L.medium = false;
+#endif
     L.pend = mk3(0, 0, 0);
     L.h.spec = 0;
     L.mean = mk3(0, 0, 0);

@@ -21,6 +21,9 @@
 
 #include "path_state.hpp"
 #include "pool_walk.hpp"
+#if CHUNKY_FOG
+#include "fog_spec.h"
+#endif
 
 #ifndef CHUNKY_STAGING_STORE
 #define CHUNKY_STAGING_STORE 0  // how finished samples reach the staging array: 0 = non-temporal (measured best), 1-3: see the deposit site
@@ -43,6 +46,43 @@ DEV int shade_phase_ext(const SceneView& S, const RenderOpts& O, LaneState& L) {
     const int kind = L.tkind;
     const f3 n = L.h.normal;
     int next = 0;  // 1 sun sampling, 2 emitter sampling, 3 diffuse bounce, 4 specular bounce (ray already set)
+#if CHUNKY_FOG
+    // Ground fog (tests/fog_port.c trace_sample_fog operation for operation): free flight at the end of every main-ray
+    // trace, hit or miss, ahead of everything else; a medium vertex is a vertex of its own kind — L.medium says so across its shadow trace.
+    const FogParams F = fog_params();
+    bool medium = kind == 1 && L.medium;
+    if (kind == 0) {
+        float ta, tb, len;
+        if (fog_interval(L.o.y, L.d.x, L.d.y, L.d.z, hit ? L.h.distance : rt_inf(), F.y_min, F.y_max, &ta, &tb, &len)) {
+            const float s = fog_free_flight(rt_pcg_float(&L.rng), F.sigma);
+            if (s < (tb - ta) * len) {
+                medium = true;
+                L.o = L.o + L.d * (ta + s / len);
+                L.throughput = L.throughput * mk3(F.color[0], F.color[1], F.color[2]);
+                L.after_nee = false;
+                L.h.distance = rt_inf();  // (the shadow record keeps the record's distance: nothing clips the sun ray of a vertex in mid-air)
+            }
+        }
+    }
+    L.medium = false;
+    if (medium) {
+        if (kind == 0) {
+            const bool sun_on = O.sun_sampling < 0 ? (S.sun_flags & 1) != 0 : O.sun_sampling != 0;
+            if (sun_on) {
+                L.d = sun_sample(S, L.rng);
+                L.h.emittance = FOG_PHASE_WEIGHT * fog_segment_transmittance(F.sigma, F.y_min, F.y_max, L.o.y, L.d.x, L.d.y, L.d.z, rt_inf());
+                L.medium = true;
+                L.tkind = 1;
+                L.shadow = true;
+                return ST_SETUP;
+            }
+        } else if (!hit) {
+            L.radiance = L.radiance + sky_radiance(S, L.d, L.throughput, L.h.emittance);
+        }
+        const float x1 = rt_pcg_float(&L.rng), x2 = rt_pcg_float(&L.rng);
+        fog_sphere(x1, x2, &L.d.x, &L.d.y, &L.d.z);  // (no origin offset: there is no surface to leave)
+    } else
+#endif
     if (kind == 0) {
         if (!hit) {
             L.radiance = L.radiance + sky_radiance(S, L.d, L.throughput, 1.0f);
@@ -105,6 +145,10 @@ DEV int shade_phase_ext(const SceneView& S, const RenderOpts& O, LaneState& L) {
         if (sun_on) {
             L.d = sun_sample(S, L.rng);
             L.h.emittance = rt_fabs(dot(L.d, n));
+#if CHUNKY_FOG
+            // (to infinity, whatever distance the shadow record keeps)
+            L.h.emittance = L.h.emittance * fog_segment_transmittance(F.sigma, F.y_min, F.y_max, L.o.y, L.d.x, L.d.y, L.d.z, rt_inf());
+#endif
             L.tkind = 1;
             L.shadow = true;
             return ST_SETUP;
@@ -149,6 +193,9 @@ DEV int shade_phase_ext(const SceneView& S, const RenderOpts& O, LaneState& L) {
                     const f3 ce = mk3(er.color.x, er.color.y, er.color.z);
                     const f3 le = ce * (ce * (er.emittance * O.emitter_scale));
                     L.pend = L.throughput * (le * w);
+#if CHUNKY_FOG
+                    L.pend = L.pend * fog_segment_transmittance(F.sigma, F.y_min, F.y_max, L.o.y, dir.x, dir.y, dir.z, dist);
+#endif
                     L.d = dir;
                     L.h.distance = dist - 0.001f;  // anything nearer than the emitter's face hides it
                     L.tkind = 2;
@@ -212,7 +259,11 @@ DEV void pool_pack(const LaneState& L, uint4 (&v)[WORDS]) {
     constexpr int H = SHORT ? 5 : 6;  // first of the two words of the main record
     const unsigned misc = (unsigned)L.depth | ((unsigned)L.shadow << 8) | ((unsigned)L.oct_hit << 9) | ((unsigned)L.trace_hit << 10) |
                           ((unsigned)L.cand_level << 11) | ((unsigned)L.bvh_which << 15) |
-                          (SHORT ? (unsigned)L.steps << 16 : ((unsigned)L.pid << 16) | ((unsigned)L.tkind << 24) | ((unsigned)L.after_nee << 26));
+                          (SHORT ? (unsigned)L.steps << 16 : ((unsigned)L.pid << 16) | ((unsigned)L.tkind << 24) | ((unsigned)L.after_nee << 26))
+#if CHUNKY_FOG
+                          | ((unsigned)L.medium << 27)
+#endif
+        ;
     if (WORDS > 8) v[WORDS - 1] = make_uint4(__float_as_uint(L.pend.x), __float_as_uint(L.pend.y), __float_as_uint(L.pend.z), (unsigned)L.h.spec);
     v[0] = make_uint4((unsigned)L.sidx, L.rng, misc, SHORT ? (unsigned)L.cand_data : (unsigned)L.steps);
     v[1] = make_uint4(__float_as_uint(L.radiance.x), __float_as_uint(L.radiance.y), __float_as_uint(L.radiance.z), __float_as_uint(L.throughput.x));
@@ -250,6 +301,9 @@ DEV void pool_unpack(LaneState& L, const uint4 (&v)[WORDS]) {
         L.cand_data = (int)v[0].w;
     } else {
         L.pid = (int)((v[0].z >> 16) & 0xFFu); L.tkind = (v[0].z >> 24) & 3u; L.after_nee = (v[0].z >> 26) & 1u;
+#if CHUNKY_FOG
+        L.medium = (v[0].z >> 27) & 1u;
+#endif
         L.steps = (int)v[0].w;
         L.bvh_cur = (int)v[5].x; L.bvh_top = (int)v[5].y; L.bvh_dist = __uint_as_float(v[5].z);
         L.cand_data = (int)v[5].w;
@@ -529,7 +583,30 @@ typedef void (*PoolKernel)(WaveArgs);
 typedef void (*PoolBiomeKernel)(BiomeMap, WaveArgs);
 PoolBiomeKernel pool_kernel_biome(const RenderPlan& p);
 PoolBiomeKernel pool_kernel_biome_bvh(const RenderPlan& p);
-#if CHUNKY_BIOME_TINT
+// The instantiations with the ground-fog layer (CHUNKY_FOG, rt_device.hpp: the layer's parameters head their arguments; shade_phase_ext
+// above) are compiled in two more units again, render_pool_fog.hip and render_pool_fog_bvh.hip: the extended integrator, pinhole and
+// pre-generated cameras.
+typedef void (*PoolFogKernel)(FogParams, WaveArgs);
+PoolFogKernel pool_kernel_fog(const RenderPlan& p);
+PoolFogKernel pool_kernel_fog_bvh(const RenderPlan& p);
+#if CHUNKY_FOG
+#define CHUNKY_POOL_FOG_CASE(TREE, K, STATS, BVH, EXT, SORT)                                                                     \
+    if (p.tree == (TREE) && p.park == (K) && p.stats == (STATS) && p.bvh == (BVH) && p.ext == (EXT) && p.sorted == (SORT) && !p.proj) \
+        return render_pool<TREE, K, STATS, BVH, EXT, SORT>;
+#ifdef CHUNKY_POOL_BVH_TU
+PoolFogKernel pool_kernel_fog_bvh(const RenderPlan& p) {
+    CHUNKY_POOL_FOG_BVH_INSTANCES(CHUNKY_POOL_FOG_CASE)
+    return nullptr;
+}
+#else
+PoolFogKernel pool_kernel_fog(const RenderPlan& p) {
+    if (p.bvh) return pool_kernel_fog_bvh(p);
+    CHUNKY_POOL_FOG_INSTANCES(CHUNKY_POOL_FOG_CASE)
+    return nullptr;
+}
+#endif
+}  // namespace chunky
+#elif CHUNKY_BIOME_TINT
 #define CHUNKY_POOL_BIOME_CASE(TREE, K, STATS, BVH, EXT, SORT)                                                                   \
     if (p.tree == (TREE) && p.park == (K) && p.stats == (STATS) && p.bvh == (BVH) && p.ext == (EXT) && p.sorted == (SORT) && !p.proj) \
         return render_pool<TREE, K, STATS, BVH, EXT, SORT>;
@@ -624,20 +701,24 @@ __global__ void __launch_bounds__(256) clear_foreign_kernel(ShardView T, int wid
 // render_pool + fold_kernel, as planned: look the kernel up, size the persistent grid, fill the arguments, launch, fold.
 static hipError_t launch_pool(const RenderPlan& plan, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
-                              float* staging, const int* seeds_dev, const StagedFold& fold = StagedFold{}, const BiomeMap* biome = nullptr) {
-    // (biome: a plan of plan_biome's, run by the instantiation that takes the map ahead of the same arguments)
-    const PoolKernel k = biome ? nullptr : pool_kernel(plan);
-    const PoolBiomeKernel kb = biome ? pool_kernel_biome(plan) : nullptr;
-    if (!k && !kb) return hipErrorInvalidDeviceFunction;  // a plan outside the list: an error, never another kernel
+                              float* staging, const int* seeds_dev, const StagedFold& fold = StagedFold{}, const BiomeMap* biome = nullptr,
+                              const FogParams* fog = nullptr) {
+    // (biome: a plan of plan_biome's, run by the instantiation that takes the map ahead of the same arguments; fog: a plan of plan_fog's, likewise)
+    const PoolKernel k = biome || fog ? nullptr : pool_kernel(plan);
+    const PoolBiomeKernel kb = biome && !fog ? pool_kernel_biome(plan) : nullptr;
+    const PoolFogKernel kf = fog && !biome ? pool_kernel_fog(plan) : nullptr;
+    if (!k && !kb && !kf) return hipErrorInvalidDeviceFunction;  // a plan outside the list: an error, never another kernel
     const int block = kLaunchBlock, park = plan.park;
     const long long n_tiles = pool_tiles(T, C.width, C.height);
     const long long n_samples = n_tiles * kSampleTile * P.n;  // tiles at the image's edges are padded
     // a wave keeps 64 + park paths in flight: no more workgroups than the samples can feed
     const long long want = (n_samples + (long long)(block / 64) * (64 + park) - 1) / ((long long)(block / 64) * (64 + park));
     int grid = 0;  // (for an empty share or no passes `want`, and so the grid, is <= 0: nothing is launched, below)
-    if (hipError_t e = kb ? persistent_grid(kb, block, plan.lds, want, &grid) : persistent_grid(k, block, plan.lds, want, &grid)) return e;
+    if (hipError_t e = kf ? persistent_grid(kf, block, plan.lds, want, &grid)
+                          : (kb ? persistent_grid(kb, block, plan.lds, want, &grid) : persistent_grid(k, block, plan.lds, want, &grid)))
+        return e;
     if (T.n_local <= 0 || P.n <= 0) return hipSuccess;  // (behind the device queries: a call on a broken device fails whatever it renders)
-    if (chosen) *chosen = KernelChoice{plan.tree, 1, plan.bvh ? 1 : 0, grid, park, kb ? kChoiceBiome : (plan.ext ? 1 : 0), plan.sorted ? 1 : 0};
+    if (chosen) *chosen = KernelChoice{plan.tree, 1, plan.bvh ? 1 : 0, grid, park, kf ? kChoiceFog : (kb ? kChoiceBiome : (plan.ext ? 1 : 0)), plan.sorted ? 1 : 0};
     hipError_t e = hipMemsetAsync(work_counter, 0, sizeof(int), stream);
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(work_counter + kXcdCounters, 0, kXcdRanges * sizeof(int), stream);  // the per-XCD sample ranges (xcd_claim)
@@ -645,7 +726,9 @@ static hipError_t launch_pool(const RenderPlan& plan, const SceneView& S, const 
     const WaveArgs A = make_wave_args(S, C, O, T, P, work_counter, res, (unsigned long long*)(work_counter + 2), (unsigned)plan.depth, staging, (unsigned)n_samples,
                                       (unsigned)((n_tiles + kXcdRanges - 1) / kXcdRanges * kSampleTile * P.n), fast_div((unsigned)P.n * (unsigned)kSubBlock),
                                       fast_div((unsigned)((C.width + kTileEdge - 1) >> kTileLog)), seeds_dev);
-    if (kb)
+    if (kf)
+        hipLaunchKernelGGL(kf, dim3(grid), dim3(block), plan.lds, stream, *fog, A);
+    else if (kb)
         hipLaunchKernelGGL(kb, dim3(grid), dim3(block), plan.lds, stream, *biome, A);
     else
         hipLaunchKernelGGL(k, dim3(grid), dim3(block), plan.lds, stream, A);
@@ -669,8 +752,15 @@ hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, c
 }
 hipError_t launch_render_fold(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
-                              float* staging, const int* seeds_dev, const StagedFold& fold, const BiomeMap* biome) {
+                              float* staging, const int* seeds_dev, const StagedFold& fold, const BiomeMap* biome, const FogParams* fog) {
     if (biome && fold.kind != StagedFold::none) return hipErrorNotSupported;  // the folds run on the kernels that do not tint by position
+    if (fog) {  // ground fog: plan_fog's plan on the fog instantiations, or nothing (the C API has refused the rest with the reason)
+        if (fold.kind != StagedFold::none) return hipErrorNotSupported;
+        const FogPlan f = plan_fog(variant, scene_facts(S), O, C.projector_type, T, P.n, work_counter && staging, seeds_dev != nullptr, biome != nullptr);
+        if (f.plan.status == PlanStatus::invalid_value) return hipErrorInvalidValue;
+        if (f.plan.status != PlanStatus::ok || f.refusal != FogRefusal::none) return hipErrorNotSupported;
+        return launch_pool(f.plan, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr, fold, nullptr, fog);
+    }
     RenderPlan plan = plan_render(variant, scene_facts(S), O, C.projector_type, T, P.n, work_counter && staging, seeds_dev != nullptr, fold.kind != StagedFold::none);
     switch (plan.status) {
         case PlanStatus::invalid_value: return hipErrorInvalidValue;

@@ -163,10 +163,27 @@ static_assert(sizeof(BiomeMap) == 64, "the biome kernels' other arguments start 
 #ifndef CHUNKY_BIOME_TINT
 #define CHUNKY_BIOME_TINT 0
 #endif
+// Ground fog (chunky_render_set_fog; the arithmetic: fog_spec.h): the layer's parameters head the arguments of the
+// kernels compiled with CHUNKY_FOG, exactly as the biome map heads those of the units compiled with CHUNKY_BIOME_TINT — one 64-byte line,
+// every other argument follows it unchanged — and of no other kernel.  A unit is compiled with at most one of the two.
+struct alignas(64) FogParams {
+    float sigma;         // density per block of path length, > 0
+    float y_min, y_max;  // the slab, octree coordinates
+    float color[3];      // single-scattering colour
+};
+static_assert(sizeof(FogParams) == 64, "the fog kernels' other arguments start 64 bytes into the argument segment");
+#ifndef CHUNKY_FOG
+#define CHUNKY_FOG 0
+#endif
+static_assert(!(CHUNKY_FOG && CHUNKY_BIOME_TINT), "one struct heads a kernel's arguments: fog or the biome map");
 #if CHUNKY_BIOME_TINT
 #define CHUNKY_KERNEL_ARGS_HEAD BiomeMap biome_unused_by_name,
 #define CHUNKY_LAUNCH_ARGS_HEAD(biome) (biome),
 constexpr int kKernelArgsOffset = (int)sizeof(BiomeMap);  // where the arguments behind the map start (path_state.hpp opaque_args)
+#elif CHUNKY_FOG
+#define CHUNKY_KERNEL_ARGS_HEAD FogParams fog_unused_by_name,
+#define CHUNKY_LAUNCH_ARGS_HEAD(fog) (fog),
+constexpr int kKernelArgsOffset = (int)sizeof(FogParams);
 #else
 #define CHUNKY_KERNEL_ARGS_HEAD
 #define CHUNKY_LAUNCH_ARGS_HEAD(biome)
@@ -190,6 +207,18 @@ DEV unsigned biome_tint_word(int cell, unsigned tt) {
 #else
     (void)cell, (void)tt;
     return 0u;
+#endif
+}
+#endif
+
+#if CHUNKY_FOG
+// The layer's parameters: scalar loads off the head of the argument segment, made where SHADE uses them — nothing of them lives in
+// registers outside it.
+DEV FogParams fog_params() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *(const FogParams __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+#else
+    return FogParams{};
 #endif
 }
 #endif

@@ -18,9 +18,9 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("CHUNKY_HIP_LIB") or os.path.join(PKG_DIR, "libchunky_hip.so")  # override: tuning builds (tools/variants.sh)
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
-SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_pool_biome.hip", "render_pool_biome_bvh.hip", "render_biome.hip", "aov_biome.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "lights.hip", "lights_groups.hip", "matte.hip", "denoise.hip", "adaptive.hip", "robust.hip",
-           "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_occlusion.hip", "capi_lights.hip", "capi_matte.hip", "capi_adaptive.hip", "capi_denoise.hip", "capi_robust.hip",
-           "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "canvas_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp", "lights_host.cpp", "robust_host.cpp",
+SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_pool_biome.hip", "render_pool_biome_bvh.hip", "render_pool_fog.hip", "render_pool_fog_bvh.hip", "render_biome.hip", "aov_biome.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "lights.hip", "lights_groups.hip", "matte.hip", "denoise.hip", "adaptive.hip", "robust.hip",
+           "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_occlusion.hip", "capi_lights.hip", "capi_matte.hip", "capi_adaptive.hip", "capi_denoise.hip", "capi_robust.hip", "capi_fog.hip",
+           "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "canvas_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp", "lights_host.cpp", "robust_host.cpp", "fog_host.cpp",
            "scene_records.cpp", "widetree.cpp", "launch_plan.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
 
@@ -33,6 +33,7 @@ BVH_WORLD, BVH_ACTOR = 0, 1
 OPT_DRAW_DEPTH, OPT_MAX_DEPTH, OPT_EMITTER_SCALE, OPT_KERNEL, OPT_SUN_SAMPLING, OPT_EMITTERS, OPT_BSDF, OPT_EMITTER_NEE, OPT_BVH_CULL_BEHIND, OPT_BIOME_TINT = range(10)
 BIOME_MAX_CELLS = 1 << 26  # CHUNKY_BIOME_MAX_CELLS: the most cells chunky_scene_set_biome_tints takes
 KERNEL_BIOME = 2  # word 5 of chunky_render_kernel_info and bit 1 of word 1 of chunky_render_aov_kernel_info: a biome-tint instantiation
+KERNEL_FOG = 3  # word 5 of chunky_render_kernel_info: a ground-fog instantiation
 PEER_LOCAL, PEER_DIRECT, PEER_STAGED = 0, 1, 2
 TRANSPORT_PEER_COPY, TRANSPORT_RCCL_SENDRECV, TRANSPORT_RCCL_REDUCE = 0, 1, 2
 E_INVALID, E_NO_DEVICE, E_HIP, E_STATE, E_ABORTED = -1, -2, -3, -4, -5
@@ -171,6 +172,11 @@ class AdaptiveState(C.Structure):
     """chunky_adaptive_state (include/chunky_hip.h): the header of a run's state; the arrays travel beside it."""
     _fields_ = [("size", C.c_size_t), ("width", C.c_int32), ("height", C.c_int32), ("passes", C.c_int32), ("last_check", C.c_int32),
                 ("active", C.c_int32), ("reserved", C.c_int32), ("params", AdaptiveParams), ("summary", AdaptiveSummary)]
+
+
+class Fog(C.Structure):
+    """chunky_fog (include/chunky_hip.h)."""
+    _fields_ = [("size", C.c_size_t), ("density", C.c_float), ("y_min", C.c_float), ("y_max", C.c_float), ("color", C.c_float * 3)]
 
 
 ROUND_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32)
@@ -316,6 +322,10 @@ def lib() -> C.CDLL:
             "chunky_camera_rays_window": [C.c_int, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32, f32, f32, vp],
             "chunky_render_set_canvas": [vp, C.c_int, C.c_int, C.c_int, C.c_int],
             "chunky_render_canvas": [vp, vp],
+            "chunky_render_set_fog": [vp, C.POINTER(Fog)],
+            "chunky_render_fog": [vp, C.POINTER(Fog)],
+            "chunky_fog_check": [C.POINTER(Fog)],
+            "chunky_selftest_plan_fog": [vp, i64, vp, vp],
             "chunky_canvas_check": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
             "chunky_selftest_canvas_pixel": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32, vp],
             "chunky_filter_frame": [vp, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int],
@@ -439,6 +449,36 @@ def plan_biome(plans16):
     out, why = np.zeros_like(p), np.zeros(len(p), np.int32)
     check(lib().chunky_selftest_plan_biome(ptr(p), len(p), ptr(out), ptr(why)))
     return out, why
+
+
+# the instantiations of the kernels with the ground-fog layer (csrc/launch_plan.hpp CHUNKY_POOL_FOG_INSTANCES, _FOG_BVH_INSTANCES)
+FOG_POOL_FORMS, FOG_POOL_PARK, FOG_POOL_BVH_PARK = (17, 18, -1), 32, 16
+FOG_REFUSALS = ("none", "biome", "stats", "rig_bits", "projected", "max_depth", "wide_tree", "bvh_records", "not_pool")  # csrc/launch_plan.hpp FogRefusal
+
+
+def fog_struct(density: float, y_min: float, y_max: float, color=(1.0, 1.0, 1.0)) -> Fog:
+    """A chunky_fog with this library's size."""
+    f = Fog()
+    f.size = C.sizeof(Fog)
+    f.density, f.y_min, f.y_max = float(density), float(y_min), float(y_max)
+    for k in range(3):
+        f.color[k] = float(color[k])
+    return f
+
+
+def fog_check(fog: Optional[Fog]) -> int:
+    """chunky_fog_check: chunky_render_set_fog's own test of a layer, without a target or a device; the status code (0 = accepted)."""
+    return int(lib().chunky_fog_check(None if fog is None else C.byref(fog)))
+
+
+def plan_fog(rows8):
+    """chunky_selftest_plan_fog: rows of 8 ints {kernel word, projector type, max depth, wide tree, entity BVHs, BVH records, biome map
+    applied, wide levels} -> (out (n, 8) int32 {status, refusal, tree, park, bvh, ext, family, 0}, the refusals' texts).  No device needed."""
+    p = np.ascontiguousarray(rows8, np.int32).reshape(-1, 8)
+    out = np.zeros_like(p)
+    text = C.create_string_buffer(256 * max(len(p), 1))
+    check(lib().chunky_selftest_plan_fog(ptr(p), len(p), ptr(out), text))
+    return out, [text.raw[256 * i:256 * (i + 1)].split(b"\0", 1)[0].decode() for i in range(len(p))]
 
 
 ADDR32_ATLAS, ADDR32_SKY, ADDR32_RECORDS = 1, 2, 4  # chunky_addr32_word / chunky_scene_addr32 (csrc/addr32.h)

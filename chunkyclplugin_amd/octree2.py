@@ -408,6 +408,22 @@ def biome_tint_option(js: dict) -> int:
     return 1 if bool(js.get("biomeColors", True)) else 0
 
 
+FOG_EXTINCTION_FACTOR = 0.04  # Chunky's Scene.EXTINCTION_FACTOR as remembered: an UNPINNED upstream fact
+
+
+def fog_settings(js: dict, depth: int) -> dict:
+    """The ground-fog layer (HipPathTracingRenderer.set_fog) of a scene JSON in a world of octree depth `depth`: density =
+    `fogDensity` x FOG_EXTINCTION_FACTOR per block, colour = `fogColor`, and — a stated deviation: Chunky's fog is unbounded and blends
+    the sky separately (`skyFogDensity`, not used) — the slab is the world's own height range [0, 2^depth].  density 0 means off."""
+    col = js.get("fogColor", {})
+    if isinstance(col, dict):
+        rgb = (col.get("red", 1.0), col.get("green", 1.0), col.get("blue", 1.0))
+    else:
+        rgb = tuple(col)[:3]
+    density = max(float(js.get("fogDensity", 0.0)), 0.0) * FOG_EXTINCTION_FACTOR
+    return {"density": density, "y_min": 0.0, "y_max": float(1 << int(depth)), "color": tuple(min(max(float(c), 0.0), 1.0) for c in rgb)}
+
+
 def load_scene(octree2_path: str, json_path: str = None, width: int = 1920, height: int = 1080,
                emitters: bool = False) -> scenes.PackedScene:
     """`.octree2` (+ scene JSON for camera / sun) -> PackedScene through the procedural asset pack (`asset_pack`: model classes

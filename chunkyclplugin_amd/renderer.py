@@ -288,6 +288,22 @@ class HipPathTracingRenderer:
         check(native.lib().chunky_render_canvas(self._h, ptr(out)))
         return tuple(int(v) for v in out)
 
+    def set_fog(self, density: float, y_min: float = 0.0, y_max: float = 1.0, color=(1.0, 1.0, 1.0)) -> None:
+        """chunky_render_set_fog: a homogeneous, isotropically scattering fog layer of `density` per block between the heights y_min
+        and y_max (octree coordinates) with single-scattering colour `color`, path traced by render_passes.  density 0 turns it off.
+        It touches no image: reset() before rendering with another layer."""
+        if float(density) == 0.0:
+            check(native.lib().chunky_render_set_fog(self._h, None))
+        else:
+            check(native.lib().chunky_render_set_fog(self._h, C.byref(native.fog_struct(density, y_min, y_max, color))))
+
+    def fog(self) -> dict:
+        """chunky_render_fog: the target's fog layer (density 0: none)."""
+        f = native.Fog()
+        f.size = C.sizeof(native.Fog)
+        check(native.lib().chunky_render_fog(self._h, C.byref(f)))
+        return {"density": float(f.density), "y_min": float(f.y_min), "y_max": float(f.y_max), "color": tuple(float(c) for c in f.color)}
+
     def camera_rays(self, seed: int) -> np.ndarray:
         """Self test of a projected camera (types 1-5, 7, 8, with its lens if one is set): the rays the render kernels compute for the pass of `seed`, every pixel,
         width*height*6 floats as camera_rays() lays them out."""
@@ -346,7 +362,8 @@ class HipPathTracingRenderer:
         out = np.zeros(8, np.int32)
         check(native.lib().chunky_render_kernel_info(self._h, ptr(out)))
         return {"tree": int(out[0]), "group": int(out[1]), "bvh": bool(out[2]), "blocks": int(out[3]), "pool": int(out[4]),
-                "ext": int(out[5]) == 1, "biome": int(out[5]) == native.KERNEL_BIOME, "passes_per_launch": int(out[6]), "sorted": bool(out[7])}
+                "ext": int(out[5]) == 1, "biome": int(out[5]) == native.KERNEL_BIOME, "fog": int(out[5]) == native.KERNEL_FOG,
+                "passes_per_launch": int(out[6]), "sorted": bool(out[7])}
 
     def phase_stats(self, reset: bool = True) -> dict:
         out = np.zeros(24, np.uint64)

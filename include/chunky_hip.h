@@ -311,6 +311,53 @@ int chunky_camera_rays_window(int projector_type, const float* settings, int64_t
                               int canvas_width, int canvas_height, int x0, int y0, int32_t seed,
                               float aperture, float focus, float* out);
 
+/* Ground fog (no reference counterpart; arithmetic: csrc/fog_spec.h; specification: tests/fog_port.c).
+ *
+ * A render target may carry one homogeneous, isotropically scattering fog layer: density sigma per block of path length inside the slab
+ * y_min <= y < y_max (octree coordinates), single-scattering colour `color`.  It is path traced — multiple scattering, lit by sun and
+ * sky, dimming the sun on what lies under it — by chunky_render_passes, on kernels of their own (the extended integrator with a
+ * medium vertex); with fog off (the default, density 0) every call runs the kernels it ran before and writes the same bits.
+ *
+ * The model.  At the end of every trace of a path's own ray, hit or miss, the part of the ray inside the slab is found (up to the hit,
+ * or to infinity).  If there is one, one random number u gives a free-flight distance s = -ln(1 - u) / sigma; if s is shorter than the
+ * part, the path has a MEDIUM VERTEX there: throughput *= color, the sun is sampled (where sun sampling is on) with weight 1/4 x the
+ * slab's transmittance towards the sun, and the path goes on in a direction uniform on the sphere; its depth counts as a bounce.
+ * Otherwise the surface, or the sky, is seen at full weight.  At a surface vertex the sun ray's weight is multiplied by the slab's
+ * transmittance towards the sun (to infinity), an emitter sample's by the transmittance up to the emitter.
+ *
+ * chunky_render_set_fog: `fog` NULL, or density 0, turns fog off; else every member is checked and the layer replaces the target's.
+ * fog->size is the caller's sizeof(chunky_fog): a smaller struct than this header's that still holds `color` is taken (members added
+ * later default to 0), a larger one is taken when its extra bytes are all 0.  It touches no image and reaches every member of a group;
+ * like a change of options it ends an adaptive run that could have been resumed.  CHUNKY_E_INVALID, nothing changed: a non-finite
+ * member, density < 0, y_min >= y_max, a colour component outside [0, 1], a size that fits neither rule.
+ * chunky_render_fog reports the layer (density 0: off); out->size is set to this header's sizeof.  chunky_fog_check is set_fog's test
+ * without a target or a device.
+ *
+ * While fog is on:
+ *   chunky_render_passes            runs the fog kernels, or answers CHUNKY_E_STATE with the reason, before anything is launched or
+ *                                   written, and never renders without fog: a projected camera (types 1-8; pre-generated rays, type -1,
+ *                                   serve every projection), CHUNKY_OPT_KERNEL bits 0-3, CHUNKY_OPT_MAX_DEPTH above 254, a scene whose
+ *                                   octree has no wide re-layout (deeper than 15 levels) or whose entity BVHs could not be re-laid
+ *                                   out, a scene with a biome map while CHUNKY_OPT_BIOME_TINT is 1.  The light-transport options
+ *                                   (CHUNKY_OPT_SUN_SAMPLING .. _EMITTER_NEE) all apply.  Shards, groups, canvas windows and external
+ *                                   device buffers work unchanged.
+ *   chunky_render_light_passes, chunky_render_adaptive*, chunky_render_robust_*   CHUNKY_E_STATE: not supported under fog.
+ *   the first-hit passes (AOV, matte, occlusion), the preview and trace records   ignore fog: they see the world in clear air.
+ * chunky_render_kernel_info's sixth word is 3 for a fog instantiation.  The Java binding does not reach these calls. */
+typedef struct chunky_fog {
+    size_t size;     /* sizeof(chunky_fog) of the caller */
+    float density;   /* sigma >= 0 per block; 0 = off */
+    float y_min, y_max;
+    float color[3];  /* each in [0, 1] */
+} chunky_fog;
+int chunky_render_set_fog(chunky_render* r, const chunky_fog* fog);
+int chunky_render_fog(chunky_render* r, chunky_fog* out);
+int chunky_fog_check(const chunky_fog* fog);
+/* self test (no device): plan_fog (csrc/launch_plan.hpp) for n rows of 8 ints {CHUNKY_OPT_KERNEL word, projector type, max depth, wide
+ * tree (0 / 1), entity BVHs (0 / 1), BVH records (0 / 1), biome map applied (0 / 1), wide levels}; out8 per row {status, refusal, tree,
+ * park, bvh, ext, family, 0}, and the refusal's text (NUL-terminated, at most 255 characters) in text256 per row when it is not NULL */
+int chunky_selftest_plan_fog(const int32_t* rows8, int64_t n, int32_t* out8, char* text256);
+
 typedef enum chunky_option {
     CHUNKY_OPT_DRAW_DEPTH = 0,      /* int, default 256  (K/rayTracer.cl:94) */
     CHUNKY_OPT_MAX_DEPTH = 1,       /* int >= 1, default 5 (K/rayTracer.cl:107); above 254 the fallback kernels run (render_pool marks a
@@ -400,7 +447,8 @@ int chunky_render_kernel_time(chunky_render* r, float* total_ms, int* launches);
  * launch of this target carries (256, fewer when the staged samples of a launch would not fit: chunky_render_passes cuts longer
  * requests into launches of that many); 1 when the launch tested full cubes and model blocks in phases of their own}.  On a group:
  * member 0's launch.  The sixth word is 2 for a biome-tint instantiation (chunky_scene_set_biome_tints), before the target's first launch
- * too: the first five words then name the instantiation its next launch will run (workgroups 0). */
+ * too: the first five words then name the instantiation its next launch will run (workgroups 0).  It is 3 for a ground-fog
+ * instantiation (chunky_render_set_fog), likewise. */
 int chunky_render_kernel_info(chunky_render* r, int32_t out8[8]);
 
 /* Profile of the wave-scheduled kernel, filled only while CHUNKY_OPT_KERNEL has bit 2 set: for each of
@@ -452,7 +500,8 @@ int chunky_render_trace_records(chunky_render* r, int32_t seed, const int32_t* g
 #define CHUNKY_AOV_ALBEDO 0
 #define CHUNKY_AOV_NORMAL 1
 /* Enqueue n AOV passes (asynchronous, like chunky_render_passes; longer requests are cut into launches of at most 256 passes,
- * which changes no bit).  CHUNKY_E_STATE before chunky_render_set_camera. */
+ * which changes no bit).  CHUNKY_E_STATE before chunky_render_set_camera.  A ground-fog layer (chunky_render_set_fog) is ignored:
+ * the images are of the world in clear air. */
 int chunky_render_aov_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp);
 /* Blocking read-back of one image (which = CHUNKY_AOV_ALBEDO or CHUNKY_AOV_NORMAL), 3*width*height floats, like
  * chunky_render_read.  CHUNKY_E_STATE before any AOV pass. */
@@ -504,7 +553,7 @@ int chunky_render_aov_kernel_info(chunky_render* r, int32_t out4[4]);
 #define CHUNKY_AOV_EMITTANCE 5
 #define CHUNKY_AOV_BLOCK 6
 /* Enqueue n passes over all seven images (asynchronous; cut into launches of at most 256 passes, which changes no bit).
- * CHUNKY_E_STATE before chunky_render_set_camera. */
+ * CHUNKY_E_STATE before chunky_render_set_camera.  A ground-fog layer (chunky_render_set_fog) is ignored. */
 int chunky_render_aov_passes_ex(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp);
 /* Blocking read-back of one image, which = CHUNKY_AOV_ALBEDO .. CHUNKY_AOV_BLOCK; n_words = width*height times the words per pixel
  * of the image (3 for albedo, normal and position, else 1; floats, int32 for CHUNKY_AOV_BLOCK).  CHUNKY_E_STATE before the first
@@ -545,7 +594,8 @@ int chunky_render_aov_read_ex(chunky_render* r, int which, void* out, int64_t n_
 #define CHUNKY_AOV_AO 7
 #define CHUNKY_AOV_SUN 8
 /* Enqueue n passes over both images (asynchronous; cut into launches of at most 256 passes, which changes no bit; n = 0 is legal).
- * CHUNKY_E_STATE before chunky_render_set_camera; CHUNKY_E_INVALID for ao_distance zero, negative or NaN. */
+ * CHUNKY_E_STATE before chunky_render_set_camera; CHUNKY_E_INVALID for ao_distance zero, negative or NaN.  A ground-fog layer
+ * (chunky_render_set_fog) is ignored: both images are of the world in clear air. */
 int chunky_render_occlusion_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp, float ao_distance);
 /* Blocking read-back of one image (which = CHUNKY_AOV_AO or CHUNKY_AOV_SUN), width*height floats.  CHUNKY_E_STATE before the first
  * chunky_render_occlusion_passes; CHUNKY_E_INVALID for an unknown image or a wrong count. */
@@ -591,7 +641,8 @@ int chunky_render_occlusion_kernel_info(chunky_render* r, int32_t out4[4]);
 #define CHUNKY_LIGHT_EMITTERS 2
 #define CHUNKY_LIGHT_ALL 3
 /* Enqueue n passes over the four images (asynchronous; cut into launches of at most 256 passes, which changes no bit; n = 0 is
- * legal).  CHUNKY_E_STATE before chunky_render_set_camera and with an experimental light-transport option set. */
+ * legal).  CHUNKY_E_STATE before chunky_render_set_camera, with an experimental light-transport option set, and while the target
+ * has a ground-fog layer (chunky_render_set_fog). */
 int chunky_render_light_passes(chunky_render* r, const int32_t* seeds, int n, int first_buffer_spp);
 /* Blocking read-back of one image (which = CHUNKY_LIGHT_SKY .. CHUNKY_LIGHT_ALL), 3*width*height floats.  CHUNKY_E_STATE before the
  * first chunky_render_light_passes; CHUNKY_E_INVALID for an unknown image or a wrong count. */
@@ -683,7 +734,7 @@ int chunky_render_light_mix_groups(chunky_render* r, float w_sky, float w_sun, c
 #define CHUNKY_MATTE_EMPTY INT32_MIN
 /* Enqueue n matte passes (asynchronous, like chunky_render_aov_passes; cut into launches of at most 256 passes, which changes no
  * word).  CHUNKY_E_STATE before chunky_render_set_camera; CHUNKY_E_INVALID, before any launch, when the target's passes would
- * exceed 2^31 - 1. */
+ * exceed 2^31 - 1.  A ground-fog layer (chunky_render_set_fog) is ignored. */
 int chunky_render_matte_passes(chunky_render* r, const int32_t* seeds, int n);
 /* Empty every slot and set the pass count to 0. */
 int chunky_render_matte_reset(chunky_render* r);
