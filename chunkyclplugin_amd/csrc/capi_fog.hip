@@ -13,6 +13,8 @@ extern "C" int chunky_render_set_fog(chunky_render* r, const chunky_fog* fog) {
     LOCK_RENDER(r);
     FogSettings s;
     if (int rc = check_fog("set_fog", fog, &s)) return rc;
+    if (s.on())  // (a layer, not "off": the glass kernels have no medium)
+        if (int rc = refuse_glass("set_fog", r)) return rc;
     r->fog = s;  // (the layer travels by value in the kernel arguments: launches already queued keep the one they had)
     r->ad_resumable = false;  // what a pass renders changes: an adaptive run cannot continue across it
     return CHUNKY_OK;

@@ -22,6 +22,7 @@
 #include "canvas_host.hpp"
 #include "capi_host.hpp"
 #include "fog_host.hpp"
+#include "glass_host.hpp"
 #include "kernels.hpp"
 #include "lights_host.hpp"
 #include "rccl_dyn.hpp"
@@ -173,6 +174,7 @@ struct chunky_render {
     int kernel_variant = 0;
     int biome_tint = 1;  // CHUNKY_OPT_BIOME_TINT: 0 = this target ignores the scene's biome map
     FogSettings fog;     // chunky_render_set_fog: the ground-fog layer of chunky_render_passes; density 0 (default) = none
+    GlassSettings glass; // chunky_render_set_translucency: translucent blocks in chunky_render_passes; off by default
     ShardView shard{0, 1, 256, 0};
     DevBuf own_fb, work_counter;
     DevBuf staging;  // render_pool: one launch's samples, [tile of 256 slots][pass][slot][3] floats
@@ -344,6 +346,10 @@ bool fog_params_of(const chunky_render* r, FogParams* F);  // r has a fog layer 
 int refuse_fog(const char* who, const chunky_render* r);  // CHUNKY_E_STATE for a call that has no fog kernels while r has a layer
 // what plan_fog decides for r's passes over S, as render_plan does for a target without fog
 FogPlan fog_plan(const chunky_render* r, const SceneView& S);
+bool glass_params_of(const chunky_render* r, GlassParams* G);  // r has translucency on (then *G holds it as the glass kernels take it)   // capi_glass.hip
+int refuse_glass(const char* who, const chunky_render* r);  // CHUNKY_E_STATE for a call that has no glass kernels while r has translucency on
+// what plan_glass decides for r's passes over S
+GlassPlan glass_plan(const chunky_render* r, const SceneView& S);
 int read_floats(const char* who, chunky_render* r, const void* src, void* out, int64_t n, int64_t need);
 int first_hit_kernel_time(chunky_render* r, FirstHitPass chunky_render::*pass, float* total_ms, int* launches);  // capi_aov.hip
 int first_hit_kernel_info(const char* who, chunky_render* r, FirstHitPass chunky_render::*pass, int32_t out4[4]);

@@ -35,6 +35,7 @@ static int light_passes(chunky_render* r, ShardView T, const int32_t* seeds, int
         return fail(CHUNKY_E_STATE, "light_passes: not with CHUNKY_OPT_SUN_SAMPLING, _EMITTERS, _BSDF or _EMITTER_NEE away from their defaults");
     if (int rc = refuse_biome("light_passes", r)) return rc;  // (before anything is allocated)
     if (int rc = refuse_fog("light_passes", r)) return rc;
+    if (int rc = refuse_glass("light_passes", r)) return rc;
     const bool groups = r->light_table.n_groups > 0;
     if (groups && !std::isfinite(r->opts.emitter_scale))  // 0 * inf: the specification of a group would be NaN wherever another group is hit
         return fail(CHUNKY_E_STATE, "light_passes: emitter groups are set and CHUNKY_OPT_EMITTER_SCALE is not finite");

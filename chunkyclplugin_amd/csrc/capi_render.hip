@@ -360,6 +360,7 @@ int needs_render_pool(const char* who, const chunky_render* r, SceneView* S) {
     if (!r->have_camera) return fail(CHUNKY_E_STATE, "%s before set_camera", who);
     if (int rc = refuse_biome(who, r)) return rc;  // the folds run on the kernels that do not tint by position
     if (int rc = refuse_fog(who, r)) return rc;    // ... and that have no medium
+    if (int rc = refuse_glass(who, r)) return rc;  // ... and that let nothing through a translucent block
     if (int rc = target_scene_view(r, S, r->opts.nee != 0)) return rc;
     const RenderPlan plan = render_plan(r, *S);
     if (int rc = check_extended_opts(who, plan)) return rc;
@@ -437,9 +438,16 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
         if (f.refusal != FogRefusal::none) return fail(CHUNKY_E_STATE, "render_passes: %s", fog_refusal_text(f.refusal));
         plan = f.plan;  // (render_pool: no pixel list, launches of up to kMaxPoolPasses)
     }
+    GlassParams glass;
+    const bool glassy = glass_params_of(r, &glass);
+    if (glassy) {  // the glass kernels (launch_plan.hpp plan_glass), or a refusal that says why: never an image with opaque glass
+        const GlassPlan g = glass_plan(r, S);
+        if (g.refusal != GlassRefusal::none) return fail(CHUNKY_E_STATE, "render_passes: %s", glass_refusal_text(g.refusal));
+        plan = g.plan;
+    }
     if (int rc = check_extended_opts("render_passes", plan)) return rc;
     BiomeMap biome;
-    const bool tinted = !foggy && biome_map(r, &biome);
+    const bool tinted = !foggy && !glassy && biome_map(r, &biome);
     if (tinted) {  // the kernels that tint by position (launch_plan.hpp plan_biome), or a refusal that says why: never an untinted image
         RenderPlan asked = plan;
         asked.status = PlanStatus::ok;  // (a block shard's pixel list is made below; what a launch cannot carry is refused there)
@@ -489,7 +497,8 @@ extern "C" int chunky_render_passes(chunky_render* r, const int32_t* seeds, int 
         }
         if (int rc = r->clock.open(r->ctx->stream)) return rc;
         HIP_TRY(launch_render_fold(r->kernel_variant, S, r->cam, r->opts, r->shard, ps, r->fb, (int*)r->work_counter.p, r->ctx->stream, &r->last_choice,
-                                   (float*)r->staging.p, seeds_dev, StagedFold{}, tinted ? &biome : nullptr, foggy ? &fog : nullptr));
+                                   (float*)r->staging.p, seeds_dev, StagedFold{}, tinted ? &biome : nullptr, foggy ? &fog : nullptr,
+                                   glassy ? &glass : nullptr));
         return r->clock.close(r->ctx->stream);
     });
 }
@@ -561,6 +570,15 @@ extern "C" int chunky_render_kernel_info(chunky_render* r, int32_t out8[8]) {
             const FogPlan f = fog_plan(r, S);
             if (f.plan.status == PlanStatus::ok && f.refusal == FogRefusal::none)
                 out8[0] = f.plan.tree, out8[1] = 1, out8[2] = f.plan.bvh ? 1 : 0, out8[4] = f.plan.park, out8[5] = kChoiceFog;
+        }
+    }
+    if (r->last_choice.blocks == 0 && r->have_camera && glass_params_of(r, nullptr)) {
+        // before the first launch of a target with translucency on: the glass instantiation its next launch will run
+        SceneView S;
+        if (scene_view(r->scene, &S, false) == CHUNKY_OK) {
+            const GlassPlan g = glass_plan(r, S);
+            if (g.plan.status == PlanStatus::ok && g.refusal == GlassRefusal::none)
+                out8[0] = g.plan.tree, out8[1] = 1, out8[2] = g.plan.bvh ? 1 : 0, out8[4] = g.plan.park, out8[5] = kChoiceGlass;
         }
     }
     if (r->launch_cap > 0) {

@@ -18,6 +18,7 @@ struct SceneView;
 struct CameraView;
 struct BiomeMap;  // rt_device.hpp
 struct FogParams;
+struct GlassParams;
 
 constexpr int kMaxTraces = 10;        // 5 path segments x (main + shadow trace)
 
@@ -44,6 +45,7 @@ struct KernelChoice {
     int sorted;  // render_pool: full cubes and model blocks tested in phases of their own
 };
 constexpr int kChoiceBiome = 2;  // KernelChoice::ext, and bit 1 of AovChoice::bvh: the launch ran a kernel compiled with CHUNKY_BIOME_TINT
+constexpr int kChoiceGlass = 4;  // KernelChoice::ext: the launch ran a kernel compiled with CHUNKY_GLASS (render_pool_glass.hip, render_pool_glass_bvh.hip)
 constexpr int kChoiceFog = 3;    // KernelChoice::ext: the launch ran a kernel compiled with CHUNKY_FOG (render_pool_fog.hip, render_pool_fog_bvh.hip)
 
 // compute units of the CURRENT device (cached per device index: members of a group and threads of a host may sit on different GPUs)
@@ -100,10 +102,12 @@ struct StagedFold {
 // render_biome.hip); hipErrorNotSupported for what plan_biome refuses, and for a map with a fold other than `none`.
 // With `fog` (the ground-fog layer) the launch runs plan_fog's plan on the kernels compiled with CHUNKY_FOG;
 // hipErrorNotSupported for what plan_fog refuses — a biome map among it — and for a fold other than `none`.
+// With `glass` (translucent blocks) the launch runs plan_glass's plan on the kernels compiled with CHUNKY_GLASS, likewise;
+// fog among what plan_glass refuses.
 hipError_t launch_render_fold(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
                               float* staging, const int* seeds_dev, const StagedFold& fold, const BiomeMap* biome = nullptr,
-                              const FogParams* fog = nullptr);
+                              const FogParams* fog = nullptr, const GlassParams* glass = nullptr);
 // the kernels behind render_pool (render_fallback.hip): render_waves, render_lanes, as `plan` names them
 hipError_t launch_fallback(const RenderPlan& plan, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                            const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen);

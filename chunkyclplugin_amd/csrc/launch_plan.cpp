@@ -256,6 +256,43 @@ const char* fog_refusal_text(FogRefusal r) {
     }
 }
 
+// Translucent blocks: the extended family, forced, on the kernels compiled with CHUNKY_GLASS and their wider parked record
+GlassPlan plan_glass(int variant, const SceneFacts& F, const RenderOpts& O, int projector_type, const ShardView& T, int n_passes,
+                     bool have_queue_and_staging, bool have_seeds_dev, bool biome_tinted, bool foggy) {
+    GlassPlan g{plan_render_as(variant, F, O, projector_type, T, n_passes, have_queue_and_staging, have_seeds_dev, false, true), GlassRefusal::none};
+    RenderPlan& p = g.plan;
+    if (foggy) g.refusal = GlassRefusal::fog;
+    else if (biome_tinted) g.refusal = GlassRefusal::biome;
+    else if (variant & 4) g.refusal = GlassRefusal::stats;
+    else if (variant & (1 | 2 | 8)) g.refusal = GlassRefusal::rig_bits;
+    else if (projector_type > 0) g.refusal = GlassRefusal::projected;
+    else if (O.max_depth > 254) g.refusal = GlassRefusal::max_depth;
+    else if (!F.wide) g.refusal = GlassRefusal::wide_tree;
+    else if (has_bvh(F) && !F.bvh_records) g.refusal = GlassRefusal::bvh_records;
+    else if (p.why != NotPool::none || p.ext_refusal != ExtRefusal::none) g.refusal = GlassRefusal::not_pool;
+    if (g.refusal == GlassRefusal::none && p.status == PlanStatus::ok && p.family == KernelFamily::pool) {
+        // the glass units' parked record: the launch sizes the LDS with what the kernel carves it with (pool_kernel.inc)
+        p.words = kPoolGlassWords;
+        p.lds = (size_t)(kLaunchBlock / 64) * pool_wave_lds_bytes(p.park, p.words, (unsigned)p.depth);
+    }
+    return g;
+}
+
+const char* glass_refusal_text(GlassRefusal r) {
+    switch (r) {
+        case GlassRefusal::fog: return "translucency: not with a fog layer on the target (chunky_render_set_fog); turn fog off (density 0) or translucency off";
+        case GlassRefusal::biome: return "translucency: not with a biome map on the scene (chunky_scene_set_biome_tints); set CHUNKY_OPT_BIOME_TINT to 0, remove the map or turn translucency off";
+        case GlassRefusal::stats: return "translucency: the phase-statistics kernels (CHUNKY_OPT_KERNEL bit 2) have no translucency; clear the bit or turn translucency off";
+        case GlassRefusal::rig_bits: return "translucency: needs the default kernel (CHUNKY_OPT_KERNEL bits 0, 1 and 3 clear): the fallback kernels and the reference-layout walk have no translucency";
+        case GlassRefusal::projected: return "translucency: projected cameras have no translucency kernel; pass pre-generated rays (chunky_render_set_rays) or turn translucency off";
+        case GlassRefusal::max_depth: return "translucency: needs max depth <= 254 (CHUNKY_OPT_MAX_DEPTH)";
+        case GlassRefusal::wide_tree: return "translucency: needs an octree the wide re-layout takes (depth <= 15)";
+        case GlassRefusal::bvh_records: return "translucency: the scene's entity BVHs could not be re-laid out; the fallback kernels have no translucency";
+        case GlassRefusal::not_pool: return "translucency: the scene or the target sends this launch to the fallback kernels, which have no translucency";
+        default: return "";
+    }
+}
+
 const char* biome_refusal_text(BiomeRefusal r) {
     switch (r) {
         case BiomeRefusal::stats: return "biome tints: the phase-statistics kernels (CHUNKY_OPT_KERNEL bit 2) do not tint by position; set CHUNKY_OPT_BIOME_TINT to 0 or remove the map";

@@ -185,6 +185,22 @@ FogPlan plan_fog(int variant, const SceneFacts& F, const RenderOpts& O, int proj
                  bool have_queue_and_staging, bool have_seeds_dev, bool biome_tinted);
 const char* fog_refusal_text(FogRefusal r);
 
+// Translucent blocks: a target with translucency on (chunky_render_set_translucency) runs the EXTENDED family whatever
+// its options say, on the kernels compiled with CHUNKY_GLASS (rt_device.hpp): plan_fog's instantiations once more — render_pool for the
+// pinhole and pre-generated cameras, tree forms 17, 18 and -1, 32 parked paths without entity BVHs and 16 with them
+// (CHUNKY_POOL_GLASS_INSTANCES, CHUNKY_POOL_GLASS_BVH_INSTANCES) — with a parked record of kPoolGlassWords 16-byte words: the extended
+// integrator's nine, and three for the hit's alpha, the runs, a shadow ray's clip distance and filter and its vertex's normal.
+// plan_glass is plan_fog's shape: the same refusals for the same reasons, and one more, a target with a fog layer.
+constexpr int kPoolGlassWords = 12;
+enum class GlassRefusal : int { none = 0, fog, biome, stats, rig_bits, projected, max_depth, wide_tree, bvh_records, not_pool };
+struct GlassPlan {
+    RenderPlan plan;
+    GlassRefusal refusal;
+};
+GlassPlan plan_glass(int variant, const SceneFacts& F, const RenderOpts& O, int projector_type, const ShardView& T, int n_passes,
+                     bool have_queue_and_staging, bool have_seeds_dev, bool biome_tinted, bool foggy);
+const char* glass_refusal_text(GlassRefusal r);
+
 }  // namespace chunky
 
 // ---------------------------------------------------------------------------------------------
@@ -261,6 +277,12 @@ const char* fog_refusal_text(FogRefusal r);
 #define CHUNKY_POOL_FOG_INSTANCES(X)                                                                                                   \
     X(17, 32, false, false, true, false) X(18, 32, false, false, true, false) X(-1, 32, false, false, true, false)
 #define CHUNKY_POOL_FOG_BVH_INSTANCES(X)                                                                                               \
+    X(17, 16, false, true, true, false) X(18, 16, false, true, true, false) X(-1, 16, false, true, true, false)
+// X(TREE, K, STATS, BVH, EXT, SORT) of render_pool compiled with CHUNKY_GLASS (render_pool_glass.hip, render_pool_glass_bvh.hip): what
+// plan_glass names
+#define CHUNKY_POOL_GLASS_INSTANCES(X)                                                                                                 \
+    X(17, 32, false, false, true, false) X(18, 32, false, false, true, false) X(-1, 32, false, false, true, false)
+#define CHUNKY_POOL_GLASS_BVH_INSTANCES(X)                                                                                             \
     X(17, 16, false, true, true, false) X(18, 16, false, true, true, false) X(-1, 16, false, true, true, false)
 // X(TREE, BVH) of the first-hit kernels (first_hit_pass.hpp first_hit_kernel, occlusion.hip occlusion_kernel, lights.hip light_kernel)
 #define CHUNKY_FIRST_HIT_INSTANCES(X)                                                                                                  \

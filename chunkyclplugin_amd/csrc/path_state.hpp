@@ -334,6 +334,15 @@ struct LaneState {
 #if CHUNKY_FOG
     unsigned medium : 1;  // the vertex whose shadow ray is being traced is a medium vertex: bit 27 of a parked record's flag word
 #endif
+#if CHUNKY_GLASS
+    // translucent blocks: three more 16-byte words of a parked record, and bits 27-31 of its flag word
+    unsigned crossings : 5;  // translucent hits the ray in flight has crossed
+    int rm;                  // block of the run the ray in flight is inside (the reference's ray->material, put to use); 0: none
+    int rm_vertex;           // ... and the one the path's last vertex was reached with: its shadow rays and its bounce start with it
+    float clip;              // a shadow ray's clip distance (its record's distance is the nearest hit's, as a main ray's)
+    f3 n_vertex, o_vertex;   // the vertex's normal and point while a shadow ray is traced (the trace writes the record's normal, a crossing moves the ray's origin)
+    // (a shadow ray's colour filter is L.pend: (1, 1, 1) at the start of a sun ray, where pend is dead; an emitter ray's light itself)
+#endif
     f3 pend;
     // main record
     Hit h;
@@ -442,7 +451,15 @@ DEV void march_step(const SceneView& S, const RenderOpts& O, LaneState& L, LaneM
     const LaneMask live = marching & __ballot(L.steps < O.draw_depth) & __ballot(!(L.dist_march > L.h.distance)) & __ballot(inside);
     int kind;
     leaf_lookup<TREE>(S, bx, by, bz, data, level, kind, inside, entry);
+#if CHUNKY_GLASS
+    // Runs: a leaf that can be hit and holds the block of the run the ray is inside (L.rm) is stepped through
+    // like air, and a leaf that cannot be hit ends the run.  For the lanes of `live` only: every other lane computes on stale values.
+    const LaneMask can_hit = __ballot(kind < 2);
+    const LaneMask hittable = can_hit & ~__ballot(data == L.rm);
+    L.rm = in_mask(live & ~can_hit) ? 0 : L.rm;
+#else
     const LaneMask hittable = __ballot(kind < 2);
+#endif
     const LaneMask cand = live & hittable, go = live & ~hittable;
     // render_pool passes the three lane masks "inv > 0" (scalar registers, set when the loop is entered) instead of L.far
     const f3 far = far_masks ? mk3(in_mask(far_masks[0]) ? 1.0f : 0.0f, in_mask(far_masks[1]) ? 1.0f : 0.0f, in_mask(far_masks[2]) ? 1.0f : 0.0f)

@@ -6,7 +6,7 @@
 // plan_render (launch_plan.cpp) picks it for scenes with many model blocks
 template <int TREE, int K, bool STATS, bool BVH = false, bool EXT = false, bool SORT = false>
 __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_BVH_WAVES : CHUNKY_POOL_WAVES))) render_pool(CHUNKY_KERNEL_ARGS_HEAD WaveArgs unused_by_name) {
-    constexpr int WORDS = pool_words(EXT, BVH);  // 16-byte words of a parked path (pool_pack; launch_plan.hpp: the launch sizes the LDS with the same two functions)
+    constexpr int WORDS = CHUNKY_GLASS ? kPoolGlassWords : pool_words(EXT, BVH);  // 16-byte words of a parked path (pool_pack; launch_plan.hpp: the launch sizes the LDS with the same two functions)
     constexpr int END = BVH ? ST_TRACED : ST_SHADE;  // where a lane goes when the octree part of a trace ends
     // candidates sorted into full cubes (ST_BLOCK) and model blocks (ST_MODEL); not instantiated with entity BVHs or the extended
     // integrator (their pools are small: measured -4 % / -2 %)
@@ -47,6 +47,12 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
     L.after_nee = false;
 #if CHUNKY_FOG
     L.medium = false;
+#endif
+#if CHUNKY_GLASS
+    L.crossings = 0;
+    L.rm = L.rm_vertex = 0;
+    L.clip = 0;
+    L.n_vertex = L.o_vertex = mk3(0, 0, 0);
 #endif
     L.pend = mk3(0, 0, 0);
     L.h.spec = 0;
@@ -334,6 +340,10 @@ __global__ void __launch_bounds__(256, ((STATS || EXT) ? 4 : (BVH ? CHUNKY_POOL_
                         L.shadow = false;
                         L.tkind = 0;
                         L.after_nee = false;
+#if CHUNKY_GLASS
+                        L.crossings = 0;  // at the camera: inside no run
+                        L.rm = L.rm_vertex = 0;
+#endif
                         L.h.distance = rt_inf();
                         st = ST_SETUP;
                         fresh = false;

@@ -24,6 +24,9 @@
 #if CHUNKY_FOG
 #include "fog_spec.h"
 #endif
+#if CHUNKY_GLASS
+#include "glass_spec.h"
+#endif
 
 #ifndef CHUNKY_STAGING_STORE
 #define CHUNKY_STAGING_STORE 0  // how finished samples reach the staging array: 0 = non-temporal (measured best), 1-3: see the deposit site
@@ -44,7 +47,37 @@ template <int TREE, bool BVH>
 DEV int shade_phase_ext(const SceneView& S, const RenderOpts& O, LaneState& L) {
     const bool hit = BVH ? L.trace_hit : L.oct_hit;
     const int kind = L.tkind;
+#if CHUNKY_GLASS
+    // Translucent blocks (tests/glass_port.c trace_sample_glass operation for operation).  In these units a shadow
+    // ray is traced as a main ray is — L.shadow stays false: the nearest hit, written to the record — so that it can be crossed in order;
+    // what the vertex still needs of its record, the normal, waits in L.n_vertex, and the ray's clip distance in L.clip.
+    const f3 n = kind == 0 ? L.h.normal : L.n_vertex;
+    constexpr bool kShadowFlag = false;
+    const GlassParams G = glass_params();
+    if (hit && glass_translucent(L.h.color.w, G.opaque_alpha, (int)L.crossings, G.max_crossings)) {
+        const float a = L.h.color.w;
+        // a main ray draws: below a the hit is a surface vertex as ever; a shadow ray draws nothing and always crosses
+        const bool crosses = kind == 0 ? !(rt_pcg_float(&L.rng) < a) : true;
+        if (crosses) {
+            if (kind == 0) {
+                L.throughput = L.throughput * mk3(glass_tc(a, L.h.color.x), glass_tc(a, L.h.color.y), glass_tc(a, L.h.color.z));
+            } else {
+                L.pend = L.pend * mk3(glass_fs(a, L.h.color.x), glass_fs(a, L.h.color.y), glass_fs(a, L.h.color.z));
+                L.clip = L.clip - L.h.distance;
+            }
+            // the ray is inside the hit's run from here on, if the octree part of the trace won (an entity triangle leaves the run alone)
+            if (L.oct_hit && (!BVH || L.h.distance == L.bvh_dist)) L.rm = L.cand_data;
+            glass_restart(L.o.x, L.o.y, L.o.z, L.d.x, L.d.y, L.d.z, L.h.distance, L.h.normal.x, L.h.normal.y, L.h.normal.z, &L.o.x, &L.o.y, &L.o.z);
+            L.crossings += 1;
+            L.h.distance = kind == 0 ? rt_inf() : L.clip;
+            return ST_SETUP;  // the same direction, the same kind of trace, the same depth
+        }
+    }
+    if (kind != 0) L.o = L.o_vertex;  // a shadow ray has ended: back at the vertex (a crossing moved the origin)
+#else
     const f3 n = L.h.normal;
+    constexpr bool kShadowFlag = true;
+#endif
     int next = 0;  // 1 sun sampling, 2 emitter sampling, 3 diffuse bounce, 4 specular bounce (ray already set)
 #if CHUNKY_FOG
     // Ground fog (tests/fog_port.c trace_sample_fog operation for operation): free flight at the end of every main-ray
@@ -89,7 +122,14 @@ DEV int shade_phase_ext(const SceneView& S, const RenderOpts& O, LaneState& L) {
             return ST_NEXT;
         }
         const f3 d_in = L.d;
+#if CHUNKY_GLASS
+        L.n_vertex = n;      // a surface vertex: its shadow rays and its bounce start inside the run it was reached through
+        L.rm_vertex = L.rm;
+#endif
         L.o = L.o + L.d * (L.h.distance - kOffset);  // rec.point
+#if CHUNKY_GLASS
+        L.o_vertex = L.o;
+#endif
         const f3 base = L.throughput;
         const f3 c = mk3(L.h.color.x, L.h.color.y, L.h.color.z);
         const f3 thr_d = base * c;
@@ -134,10 +174,15 @@ DEV int shade_phase_ext(const SceneView& S, const RenderOpts& O, LaneState& L) {
             next = 1;
         }
     } else if (kind == 1) {
+#if CHUNKY_GLASS
+        // (the record's emittance is a crossed hit's by now: |dot(d, n)| again, from the operands it was made from)
+        if (!hit) L.radiance = L.radiance + sky_radiance(S, L.d, L.throughput, rt_fabs(dot(L.d, n))) * L.pend;
+#else
         if (!hit) L.radiance = L.radiance + sky_radiance(S, L.d, L.throughput, L.h.emittance);
+#endif
         next = 2;
     } else {
-        if (!hit) L.radiance = L.radiance + L.pend;
+        if (!hit) L.radiance = L.radiance + L.pend;  // (with translucent blocks: through the filter, crossing by crossing)
         next = 3;
     }
     if (next == 1) {  // Sun_sampleDirection + shadow ray (K/sky.h:68-93, K/rayTracer.cl:101-106): the record keeps its distance
@@ -150,7 +195,13 @@ DEV int shade_phase_ext(const SceneView& S, const RenderOpts& O, LaneState& L) {
             L.h.emittance = L.h.emittance * fog_segment_transmittance(F.sigma, F.y_min, F.y_max, L.o.y, L.d.x, L.d.y, L.d.z, rt_inf());
 #endif
             L.tkind = 1;
-            L.shadow = true;
+            L.shadow = kShadowFlag;
+#if CHUNKY_GLASS
+            L.clip = L.h.distance;  // the record's distance, kept (K/rayTracer.cl:101-106)
+            L.pend = mk3(1, 1, 1);  // the sun ray's filter
+            L.crossings = 0;
+            L.rm = L.rm_vertex;
+#endif
             return ST_SETUP;
         }
         next = 2;
@@ -199,7 +250,12 @@ DEV int shade_phase_ext(const SceneView& S, const RenderOpts& O, LaneState& L) {
                     L.d = dir;
                     L.h.distance = dist - 0.001f;  // anything nearer than the emitter's face hides it
                     L.tkind = 2;
-                    L.shadow = true;
+                    L.shadow = kShadowFlag;
+#if CHUNKY_GLASS
+                    L.clip = L.h.distance;
+                    L.crossings = 0;
+                    L.rm = L.rm_vertex;
+#endif
                     return ST_SETUP;
                 }
             }
@@ -214,6 +270,10 @@ DEV int shade_phase_ext(const SceneView& S, const RenderOpts& O, LaneState& L) {
     L.h.distance = rt_inf();
     L.tkind = 0;
     L.shadow = false;
+#if CHUNKY_GLASS
+    L.crossings = 0;
+    L.rm = L.rm_vertex;  // (whatever a shadow ray did to it is discarded)
+#endif
     return (int)L.depth < O.max_depth ? ST_SETUP : ST_NEXT;
 }
 // ---------------------------------------------------------------------------------------------
@@ -263,7 +323,16 @@ DEV void pool_pack(const LaneState& L, uint4 (&v)[WORDS]) {
 #if CHUNKY_FOG
                           | ((unsigned)L.medium << 27)
 #endif
+#if CHUNKY_GLASS
+                          | ((unsigned)L.crossings << 27)
+#endif
         ;
+#if CHUNKY_GLASS
+    static_assert(WORDS == kPoolGlassWords, "the glass units park the twelve-word record only");
+    v[8] = make_uint4(__float_as_uint(L.h.color.w), (unsigned)L.rm, (unsigned)L.rm_vertex, __float_as_uint(L.clip));
+    v[9] = make_uint4(__float_as_uint(L.n_vertex.x), __float_as_uint(L.n_vertex.y), __float_as_uint(L.n_vertex.z), __float_as_uint(L.o_vertex.x));
+    v[10] = make_uint4(__float_as_uint(L.o_vertex.y), __float_as_uint(L.o_vertex.z), 0u, 0u);
+#endif
     if (WORDS > 8) v[WORDS - 1] = make_uint4(__float_as_uint(L.pend.x), __float_as_uint(L.pend.y), __float_as_uint(L.pend.z), (unsigned)L.h.spec);
     v[0] = make_uint4((unsigned)L.sidx, L.rng, misc, SHORT ? (unsigned)L.cand_data : (unsigned)L.steps);
     v[1] = make_uint4(__float_as_uint(L.radiance.x), __float_as_uint(L.radiance.y), __float_as_uint(L.radiance.z), __float_as_uint(L.throughput.x));
@@ -304,6 +373,12 @@ DEV void pool_unpack(LaneState& L, const uint4 (&v)[WORDS]) {
 #if CHUNKY_FOG
         L.medium = (v[0].z >> 27) & 1u;
 #endif
+#if CHUNKY_GLASS
+        L.crossings = (v[0].z >> 27) & 31u;
+        L.rm = (int)v[8].y; L.rm_vertex = (int)v[8].z; L.clip = __uint_as_float(v[8].w);
+        L.n_vertex = mk3(__uint_as_float(v[9].x), __uint_as_float(v[9].y), __uint_as_float(v[9].z));
+        L.o_vertex = mk3(__uint_as_float(v[9].w), __uint_as_float(v[10].x), __uint_as_float(v[10].y));
+#endif
         L.steps = (int)v[0].w;
         L.bvh_cur = (int)v[5].x; L.bvh_top = (int)v[5].y; L.bvh_dist = __uint_as_float(v[5].z);
         L.cand_data = (int)v[5].w;
@@ -321,7 +396,11 @@ DEV void pool_unpack(LaneState& L, const uint4 (&v)[WORDS]) {
     }
     L.h.distance = __uint_as_float(v[H].x);
     L.h.normal = mk3(__uint_as_float(v[H].y), __uint_as_float(v[H].z), __uint_as_float(v[H].w));
+#if CHUNKY_GLASS
+    L.h.color = f4{__uint_as_float(v[H + 1].x), __uint_as_float(v[H + 1].y), __uint_as_float(v[H + 1].z), __uint_as_float(v[8].x)};  // the hit's alpha survives parking
+#else
     L.h.color = f4{__uint_as_float(v[H + 1].x), __uint_as_float(v[H + 1].y), __uint_as_float(v[H + 1].z), 0.0f};
+#endif
     L.h.emittance = __uint_as_float(v[H + 1].w);
 }
 
@@ -350,7 +429,7 @@ DEV void wave_lds_fence() {
 // 16-byte groups in one burst and writes its own over them.
 template <int K, int WORDS = 8>
 DEV int pool_swap(PoolLds P, LaneState& L, int& st, int& ptag, int X, int lane) {
-    constexpr bool BVH = WORDS == 8 || WORDS == 9;  // (the extended integrator's 9-word record carries the walk's fields too; 6 / 7 words: no entity BVHs)
+    constexpr bool BVH = WORDS >= 8;  // (the extended integrator's 9-word record, and the glass units' 12-word one, carry the walk's fields too; 6 / 7 words: no entity BVHs)
     // who trades, as lane masks in scalar registers (mask algebra on the scalar unit; the vector unit only compares)
     constexpr LaneMask kSlots = K >= 64 ? ~0ull : ((1ull << K) - 1ull);            // lane j < K speaks for parked slot j
     const LaneMask m_done = __ballot(st == ST_DONE);
@@ -589,8 +668,31 @@ PoolBiomeKernel pool_kernel_biome_bvh(const RenderPlan& p);
 typedef void (*PoolFogKernel)(FogParams, WaveArgs);
 PoolFogKernel pool_kernel_fog(const RenderPlan& p);
 PoolFogKernel pool_kernel_fog_bvh(const RenderPlan& p);
-#if CHUNKY_FOG
-#define CHUNKY_POOL_FOG_CASE(TREE, K, STATS, BVH, EXT, SORT)                                                                     \
+// The instantiations with translucent blocks (CHUNKY_GLASS, rt_device.hpp: the two parameters head their arguments; shade_phase_ext above and
+// the march's run rule, path_state.hpp march_step) are compiled in two more units, render_pool_glass.hip and render_pool_glass_bvh.hip:
+// the extended integrator, pinhole and pre-generated cameras, the twelve-word parked record.
+typedef void (*PoolGlassKernel)(GlassParams, WaveArgs);
+PoolGlassKernel pool_kernel_glass(const RenderPlan& p);
+PoolGlassKernel pool_kernel_glass_bvh(const RenderPlan& p);
+#if CHUNKY_GLASS
+#define CHUNKY_POOL_GLASS_CASE(TREE, K, STATS, BVH, EXT, SORT)                                                                   \
+    if (p.tree == (TREE) && p.park == (K) && p.stats == (STATS) && p.bvh == (BVH) && p.ext == (EXT) && p.sorted == (SORT) && !p.proj) \
+        return render_pool<TREE, K, STATS, BVH, EXT, SORT>;
+#ifdef CHUNKY_POOL_BVH_TU
+PoolGlassKernel pool_kernel_glass_bvh(const RenderPlan& p) {
+    CHUNKY_POOL_GLASS_BVH_INSTANCES(CHUNKY_POOL_GLASS_CASE)
+    return nullptr;
+}
+#else
+PoolGlassKernel pool_kernel_glass(const RenderPlan& p) {
+    if (p.bvh) return pool_kernel_glass_bvh(p);
+    CHUNKY_POOL_GLASS_INSTANCES(CHUNKY_POOL_GLASS_CASE)
+    return nullptr;
+}
+#endif
+}  // namespace chunky
+#elif CHUNKY_FOG
+#define CHUNKY_POOL_FOG_CASE(TREE, K, STATS, BVH, EXT, SORT)                                                                    \
     if (p.tree == (TREE) && p.park == (K) && p.stats == (STATS) && p.bvh == (BVH) && p.ext == (EXT) && p.sorted == (SORT) && !p.proj) \
         return render_pool<TREE, K, STATS, BVH, EXT, SORT>;
 #ifdef CHUNKY_POOL_BVH_TU
@@ -702,23 +804,26 @@ __global__ void __launch_bounds__(256) clear_foreign_kernel(ShardView T, int wid
 static hipError_t launch_pool(const RenderPlan& plan, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
                               float* staging, const int* seeds_dev, const StagedFold& fold = StagedFold{}, const BiomeMap* biome = nullptr,
-                              const FogParams* fog = nullptr) {
-    // (biome: a plan of plan_biome's, run by the instantiation that takes the map ahead of the same arguments; fog: a plan of plan_fog's, likewise)
-    const PoolKernel k = biome || fog ? nullptr : pool_kernel(plan);
-    const PoolBiomeKernel kb = biome && !fog ? pool_kernel_biome(plan) : nullptr;
-    const PoolFogKernel kf = fog && !biome ? pool_kernel_fog(plan) : nullptr;
-    if (!k && !kb && !kf) return hipErrorInvalidDeviceFunction;  // a plan outside the list: an error, never another kernel
+                              const FogParams* fog = nullptr, const GlassParams* glass = nullptr) {
+    // (biome: a plan of plan_biome's, run by the instantiation that takes the map ahead of the same arguments; fog: a plan of plan_fog's,
+    // glass: a plan of plan_glass's, likewise)
+    const PoolKernel k = biome || fog || glass ? nullptr : pool_kernel(plan);
+    const PoolBiomeKernel kb = biome && !fog && !glass ? pool_kernel_biome(plan) : nullptr;
+    const PoolFogKernel kf = fog && !biome && !glass ? pool_kernel_fog(plan) : nullptr;
+    const PoolGlassKernel kg = glass && !biome && !fog ? pool_kernel_glass(plan) : nullptr;
+    if (!k && !kb && !kf && !kg) return hipErrorInvalidDeviceFunction;  // a plan outside the list: an error, never another kernel
     const int block = kLaunchBlock, park = plan.park;
     const long long n_tiles = pool_tiles(T, C.width, C.height);
     const long long n_samples = n_tiles * kSampleTile * P.n;  // tiles at the image's edges are padded
     // a wave keeps 64 + park paths in flight: no more workgroups than the samples can feed
     const long long want = (n_samples + (long long)(block / 64) * (64 + park) - 1) / ((long long)(block / 64) * (64 + park));
     int grid = 0;  // (for an empty share or no passes `want`, and so the grid, is <= 0: nothing is launched, below)
-    if (hipError_t e = kf ? persistent_grid(kf, block, plan.lds, want, &grid)
-                          : (kb ? persistent_grid(kb, block, plan.lds, want, &grid) : persistent_grid(k, block, plan.lds, want, &grid)))
+    if (hipError_t e = kg ? persistent_grid(kg, block, plan.lds, want, &grid)
+                          : (kf ? persistent_grid(kf, block, plan.lds, want, &grid)
+                                : (kb ? persistent_grid(kb, block, plan.lds, want, &grid) : persistent_grid(k, block, plan.lds, want, &grid))))
         return e;
     if (T.n_local <= 0 || P.n <= 0) return hipSuccess;  // (behind the device queries: a call on a broken device fails whatever it renders)
-    if (chosen) *chosen = KernelChoice{plan.tree, 1, plan.bvh ? 1 : 0, grid, park, kf ? kChoiceFog : (kb ? kChoiceBiome : (plan.ext ? 1 : 0)), plan.sorted ? 1 : 0};
+    if (chosen) *chosen = KernelChoice{plan.tree, 1, plan.bvh ? 1 : 0, grid, park, kg ? kChoiceGlass : (kf ? kChoiceFog : (kb ? kChoiceBiome : (plan.ext ? 1 : 0))), plan.sorted ? 1 : 0};
     hipError_t e = hipMemsetAsync(work_counter, 0, sizeof(int), stream);
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(work_counter + kXcdCounters, 0, kXcdRanges * sizeof(int), stream);  // the per-XCD sample ranges (xcd_claim)
@@ -726,7 +831,9 @@ static hipError_t launch_pool(const RenderPlan& plan, const SceneView& S, const 
     const WaveArgs A = make_wave_args(S, C, O, T, P, work_counter, res, (unsigned long long*)(work_counter + 2), (unsigned)plan.depth, staging, (unsigned)n_samples,
                                       (unsigned)((n_tiles + kXcdRanges - 1) / kXcdRanges * kSampleTile * P.n), fast_div((unsigned)P.n * (unsigned)kSubBlock),
                                       fast_div((unsigned)((C.width + kTileEdge - 1) >> kTileLog)), seeds_dev);
-    if (kf)
+    if (kg)
+        hipLaunchKernelGGL(kg, dim3(grid), dim3(block), plan.lds, stream, *glass, A);
+    else if (kf)
         hipLaunchKernelGGL(kf, dim3(grid), dim3(block), plan.lds, stream, *fog, A);
     else if (kb)
         hipLaunchKernelGGL(kb, dim3(grid), dim3(block), plan.lds, stream, *biome, A);
@@ -752,8 +859,16 @@ hipError_t launch_render(int variant, const SceneView& S, const CameraView& C, c
 }
 hipError_t launch_render_fold(int variant, const SceneView& S, const CameraView& C, const RenderOpts& O, const ShardView& T,
                               const PassSeeds& P, float* res, int* work_counter, hipStream_t stream, KernelChoice* chosen,
-                              float* staging, const int* seeds_dev, const StagedFold& fold, const BiomeMap* biome, const FogParams* fog) {
+                              float* staging, const int* seeds_dev, const StagedFold& fold, const BiomeMap* biome, const FogParams* fog,
+                              const GlassParams* glass) {
     if (biome && fold.kind != StagedFold::none) return hipErrorNotSupported;  // the folds run on the kernels that do not tint by position
+    if (glass) {  // translucent blocks: plan_glass's plan on the glass instantiations, or nothing (the C API has refused the rest with the reason)
+        if (fold.kind != StagedFold::none) return hipErrorNotSupported;
+        const GlassPlan g = plan_glass(variant, scene_facts(S), O, C.projector_type, T, P.n, work_counter && staging, seeds_dev != nullptr, biome != nullptr, fog != nullptr);
+        if (g.plan.status == PlanStatus::invalid_value) return hipErrorInvalidValue;
+        if (g.plan.status != PlanStatus::ok || g.refusal != GlassRefusal::none) return hipErrorNotSupported;
+        return launch_pool(g.plan, S, C, O, T, P, res, work_counter, stream, chosen, staging, P.n > kMaxPassesPerLaunch ? seeds_dev : nullptr, fold, nullptr, nullptr, glass);
+    }
     if (fog) {  // ground fog: plan_fog's plan on the fog instantiations, or nothing (the C API has refused the rest with the reason)
         if (fold.kind != StagedFold::none) return hipErrorNotSupported;
         const FogPlan f = plan_fog(variant, scene_facts(S), O, C.projector_type, T, P.n, work_counter && staging, seeds_dev != nullptr, biome != nullptr);

@@ -176,6 +176,18 @@ static_assert(sizeof(FogParams) == 64, "the fog kernels' other arguments start 6
 #define CHUNKY_FOG 0
 #endif
 static_assert(!(CHUNKY_FOG && CHUNKY_BIOME_TINT), "one struct heads a kernel's arguments: fog or the biome map");
+// Translucent blocks (chunky_render_set_translucency; the arithmetic: glass_spec.h): the two parameters head the
+// arguments of the kernels compiled with CHUNKY_GLASS, as FogParams heads those of the fog units — and of no other kernel.  A unit has
+// one head only: the biome map, fog or this.
+struct alignas(64) GlassParams {
+    float opaque_alpha;  // a hit whose alpha is below this is translucent, in (0, 1]
+    int max_crossings;   // ... while its ray has crossed fewer translucent hits than this, in [1, 31]
+};
+static_assert(sizeof(GlassParams) == 64, "the glass kernels' other arguments start 64 bytes into the argument segment");
+#ifndef CHUNKY_GLASS
+#define CHUNKY_GLASS 0
+#endif
+static_assert(!(CHUNKY_GLASS && (CHUNKY_FOG || CHUNKY_BIOME_TINT)), "one struct heads a kernel's arguments: the biome map, fog or translucency");
 #if CHUNKY_BIOME_TINT
 #define CHUNKY_KERNEL_ARGS_HEAD BiomeMap biome_unused_by_name,
 #define CHUNKY_LAUNCH_ARGS_HEAD(biome) (biome),
@@ -184,6 +196,10 @@ constexpr int kKernelArgsOffset = (int)sizeof(BiomeMap);  // where the arguments
 #define CHUNKY_KERNEL_ARGS_HEAD FogParams fog_unused_by_name,
 #define CHUNKY_LAUNCH_ARGS_HEAD(fog) (fog),
 constexpr int kKernelArgsOffset = (int)sizeof(FogParams);
+#elif CHUNKY_GLASS
+#define CHUNKY_KERNEL_ARGS_HEAD GlassParams glass_unused_by_name,
+#define CHUNKY_LAUNCH_ARGS_HEAD(glass) (glass),
+constexpr int kKernelArgsOffset = (int)sizeof(GlassParams);
 #else
 #define CHUNKY_KERNEL_ARGS_HEAD
 #define CHUNKY_LAUNCH_ARGS_HEAD(biome)
@@ -219,6 +235,17 @@ DEV FogParams fog_params() {
     return *(const FogParams __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
 #else
     return FogParams{};
+#endif
+}
+#endif
+
+#if CHUNKY_GLASS
+// The two parameters: scalar loads off the head of the argument segment, made where SHADE uses them.
+DEV GlassParams glass_params() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *(const GlassParams __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+#else
+    return GlassParams{};
 #endif
 }
 #endif

@@ -18,9 +18,9 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("CHUNKY_HIP_LIB") or os.path.join(PKG_DIR, "libchunky_hip.so")  # override: tuning builds (tools/variants.sh)
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "chunky_hip.h")
-SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_pool_biome.hip", "render_pool_biome_bvh.hip", "render_pool_fog.hip", "render_pool_fog_bvh.hip", "render_biome.hip", "aov_biome.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "lights.hip", "lights_groups.hip", "matte.hip", "denoise.hip", "adaptive.hip", "robust.hip",
-           "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_occlusion.hip", "capi_lights.hip", "capi_matte.hip", "capi_adaptive.hip", "capi_denoise.hip", "capi_robust.hip", "capi_fog.hip",
-           "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "canvas_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp", "lights_host.cpp", "robust_host.cpp", "fog_host.cpp",
+SOURCES = ["render_pool.hip", "render_pool_bvh.hip", "render_pool_biome.hip", "render_pool_biome_bvh.hip", "render_pool_fog.hip", "render_pool_fog_bvh.hip", "render_pool_glass.hip", "render_pool_glass_bvh.hip", "render_biome.hip", "aov_biome.hip", "render_fallback.hip", "aux_kernels.hip", "filter.hip", "aov.hip", "occlusion.hip", "lights.hip", "lights_groups.hip", "matte.hip", "denoise.hip", "adaptive.hip", "robust.hip",
+           "capi_context.hip", "capi_group.hip", "capi_scene.hip", "capi_render.hip", "capi_aov.hip", "capi_occlusion.hip", "capi_lights.hip", "capi_matte.hip", "capi_adaptive.hip", "capi_denoise.hip", "capi_robust.hip", "capi_fog.hip", "capi_glass.hip",
+           "capi_run.hip", "capi_filter.hip", "capi_selftest.hip", "capi_error.cpp", "capi_host.cpp", "canvas_host.cpp", "adaptive_host.cpp", "denoise_host.cpp", "matte_host.cpp", "lights_host.cpp", "robust_host.cpp", "fog_host.cpp", "glass_host.cpp",
            "scene_records.cpp", "widetree.cpp", "launch_plan.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared"]
 
@@ -34,6 +34,7 @@ OPT_DRAW_DEPTH, OPT_MAX_DEPTH, OPT_EMITTER_SCALE, OPT_KERNEL, OPT_SUN_SAMPLING, 
 BIOME_MAX_CELLS = 1 << 26  # CHUNKY_BIOME_MAX_CELLS: the most cells chunky_scene_set_biome_tints takes
 KERNEL_BIOME = 2  # word 5 of chunky_render_kernel_info and bit 1 of word 1 of chunky_render_aov_kernel_info: a biome-tint instantiation
 KERNEL_FOG = 3  # word 5 of chunky_render_kernel_info: a ground-fog instantiation
+KERNEL_GLASS = 4  # word 5 of chunky_render_kernel_info: a translucent-blocks instantiation
 PEER_LOCAL, PEER_DIRECT, PEER_STAGED = 0, 1, 2
 TRANSPORT_PEER_COPY, TRANSPORT_RCCL_SENDRECV, TRANSPORT_RCCL_REDUCE = 0, 1, 2
 E_INVALID, E_NO_DEVICE, E_HIP, E_STATE, E_ABORTED = -1, -2, -3, -4, -5
@@ -177,6 +178,11 @@ class AdaptiveState(C.Structure):
 class Fog(C.Structure):
     """chunky_fog (include/chunky_hip.h)."""
     _fields_ = [("size", C.c_size_t), ("density", C.c_float), ("y_min", C.c_float), ("y_max", C.c_float), ("color", C.c_float * 3)]
+
+
+class Translucency(C.Structure):
+    """chunky_translucency (include/chunky_hip.h)."""
+    _fields_ = [("size", C.c_size_t), ("opaque_alpha", C.c_float), ("max_crossings", C.c_int32)]
 
 
 ROUND_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32)
@@ -326,6 +332,10 @@ def lib() -> C.CDLL:
             "chunky_render_fog": [vp, C.POINTER(Fog)],
             "chunky_fog_check": [C.POINTER(Fog)],
             "chunky_selftest_plan_fog": [vp, i64, vp, vp],
+            "chunky_render_set_translucency": [vp, C.POINTER(Translucency)],
+            "chunky_render_translucency": [vp, C.POINTER(Translucency), C.POINTER(C.c_int)],
+            "chunky_translucency_check": [C.POINTER(Translucency)],
+            "chunky_selftest_plan_glass": [vp, i64, vp, vp],
             "chunky_canvas_check": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
             "chunky_selftest_canvas_pixel": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32, vp],
             "chunky_filter_frame": [vp, C.c_int, C.c_int, C.c_double, vp, vp, C.c_int],
@@ -478,6 +488,35 @@ def plan_fog(rows8):
     out = np.zeros_like(p)
     text = C.create_string_buffer(256 * max(len(p), 1))
     check(lib().chunky_selftest_plan_fog(ptr(p), len(p), ptr(out), text))
+    return out, [text.raw[256 * i:256 * (i + 1)].split(b"\0", 1)[0].decode() for i in range(len(p))]
+
+
+# the instantiations of the kernels with translucent blocks (csrc/launch_plan.hpp CHUNKY_POOL_GLASS_INSTANCES, _GLASS_BVH_INSTANCES)
+GLASS_POOL_FORMS, GLASS_POOL_PARK, GLASS_POOL_BVH_PARK, GLASS_POOL_WORDS = (17, 18, -1), 32, 16, 12
+GLASS_REFUSALS = ("none", "fog", "biome", "stats", "rig_bits", "projected", "max_depth", "wide_tree", "bvh_records", "not_pool")  # csrc/launch_plan.hpp GlassRefusal
+
+
+def translucency_struct(opaque_alpha: float = 0.99, max_crossings: int = 8) -> Translucency:
+    """A chunky_translucency with this library's size."""
+    t = Translucency()
+    t.size = C.sizeof(Translucency)
+    t.opaque_alpha, t.max_crossings = float(opaque_alpha), int(max_crossings)
+    return t
+
+
+def translucency_check(t: Optional[Translucency]) -> int:
+    """chunky_translucency_check: chunky_render_set_translucency's own test, without a target or a device; the status code (0 = accepted)."""
+    return int(lib().chunky_translucency_check(None if t is None else C.byref(t)))
+
+
+def plan_glass(rows9):
+    """chunky_selftest_plan_glass: rows of 9 ints {kernel word, projector type, max depth, wide tree, entity BVHs, BVH records, biome map
+    applied, wide levels, fog layer} -> (out (n, 8) int32 {status, refusal, tree, park, bvh, ext, family, words}, the refusals' texts).
+    No device needed."""
+    p = np.ascontiguousarray(rows9, np.int32).reshape(-1, 9)
+    out = np.zeros((len(p), 8), np.int32)
+    text = C.create_string_buffer(256 * max(len(p), 1))
+    check(lib().chunky_selftest_plan_glass(ptr(p), len(p), ptr(out), text))
     return out, [text.raw[256 * i:256 * (i + 1)].split(b"\0", 1)[0].decode() for i in range(len(p))]
 
 

@@ -304,6 +304,23 @@ class HipPathTracingRenderer:
         check(native.lib().chunky_render_fog(self._h, C.byref(f)))
         return {"density": float(f.density), "y_min": float(f.y_min), "y_max": float(f.y_max), "color": tuple(float(c) for c in f.color)}
 
+    def set_translucency(self, opaque_alpha: Optional[float] = 0.99, max_crossings: int = 8) -> None:
+        """chunky_render_set_translucency: hits whose alpha (after the tint) is below `opaque_alpha` let light through — a path's ray
+        crosses with probability 1 - alpha, a shadow ray is filtered — at most `max_crossings` times per ray.
+        opaque_alpha None turns the feature off.  It touches no image: reset() before rendering with another setting."""
+        if opaque_alpha is None:
+            check(native.lib().chunky_render_set_translucency(self._h, None))
+        else:
+            check(native.lib().chunky_render_set_translucency(self._h, C.byref(native.translucency_struct(opaque_alpha, max_crossings))))
+
+    def translucency(self) -> dict:
+        """chunky_render_translucency: the target's setting."""
+        t = native.Translucency()
+        t.size = C.sizeof(native.Translucency)
+        on = C.c_int(0)
+        check(native.lib().chunky_render_translucency(self._h, C.byref(t), C.byref(on)))
+        return {"enabled": bool(on.value), "opaque_alpha": float(t.opaque_alpha), "max_crossings": int(t.max_crossings)}
+
     def camera_rays(self, seed: int) -> np.ndarray:
         """Self test of a projected camera (types 1-5, 7, 8, with its lens if one is set): the rays the render kernels compute for the pass of `seed`, every pixel,
         width*height*6 floats as camera_rays() lays them out."""
@@ -362,7 +379,7 @@ class HipPathTracingRenderer:
         out = np.zeros(8, np.int32)
         check(native.lib().chunky_render_kernel_info(self._h, ptr(out)))
         return {"tree": int(out[0]), "group": int(out[1]), "bvh": bool(out[2]), "blocks": int(out[3]), "pool": int(out[4]),
-                "ext": int(out[5]) == 1, "biome": int(out[5]) == native.KERNEL_BIOME, "fog": int(out[5]) == native.KERNEL_FOG,
+                "ext": int(out[5]) == 1, "biome": int(out[5]) == native.KERNEL_BIOME, "fog": int(out[5]) == native.KERNEL_FOG, "glass": int(out[5]) == native.KERNEL_GLASS,
                 "passes_per_launch": int(out[6]), "sorted": bool(out[7])}
 
     def phase_stats(self, reset: bool = True) -> dict:

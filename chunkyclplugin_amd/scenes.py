@@ -455,7 +455,7 @@ def outdoor_world(chunks: int = 32, height: int = 256, seed: int = 20260101,
                   width: int = 1920, img_height: int = 1080, sun_flag: bool = True,
                   aabb_frac: float = 0.02, quad_frac: float = 0.01, trees: bool = True,
                   emitters: float = 0.0, octree_order: str = "bfs", atlas_tiles: Tuple[int, int] = (8, 8),
-                  water: bool = False) -> PackedScene:
+                  water: bool = False, water_alpha: int = 255) -> PackedScene:
     """BASELINE.json config 3: chunks x chunks Minecraft chunks (16 columns each), `height` tall,
     seeded value-noise terrain with bedrock/stone/dirt/grass layers, ANY_TYPE hidden interior,
     ~`aabb_frac` slab (AABB-model) and ~`quad_frac` plant (quad-model) blocks on the surface,
@@ -465,7 +465,8 @@ def outdoor_world(chunks: int = 32, height: int = 256, seed: int = 20260101,
 
     `atlas_tiles` bounds the atlas layers (in 16-px tiles): (2, 2) pushes the thirteen textures over four layers, with
     tiles at y = 1 whose location bit 13 runs into the kernel's 19-bit layer mask (K/textureAtlas.h:13, quirk B#7).
-    `water` floods the low ground with a cube whose material carries the biome-water tint (type 3, K/material.h:61-72)."""
+    `water` floods the low ground with a cube whose material carries the biome-water tint (type 3, K/material.h:61-72);
+    `water_alpha` is the alpha byte of its texels (255, the default: opaque water, the bytes of before)."""
     rng = np.random.default_rng(seed)
     n = chunks * 16
     S = max(n, height)
@@ -489,7 +490,10 @@ def outdoor_world(chunks: int = 32, height: int = 256, seed: int = 20260101,
         "sun": ab.add(noise_texture(rng, (255, 250, 230), 4, size=32)),
     }
     if water:
-        tex["water"] = ab.add(noise_texture(rng, (200, 200, 200), 12))
+        water_tile = noise_texture(rng, (200, 200, 200), 12)
+        if water_alpha != 255:
+            water_tile[..., 3] = int(water_alpha)
+        tex["water"] = ab.add(water_tile)
     atlas, recs = ab.build()
     pal = Palettes()
     m = {k: pal.material(texture=recs[v]) for k, v in tex.items() if k not in ("grass", "leaves", "plant", "glow", "sun", "water")}
@@ -642,13 +646,86 @@ def indoor_room(size: int = 64, seed: int = 7, width: int = 1920, img_height: in
                        width=width, height=img_height, name=f"indoor{size}")
 
 
+def alpha_texture(rng: np.random.Generator, base_rgb: Sequence[int], alphas: Sequence[int] = (0, 64, 128, 255), spread: int = 16) -> np.ndarray:
+    """A 16 x 16 RGBA8 tile whose texel alphas are drawn from `alphas`: cut-out, translucent and opaque texels side by side."""
+    t = noise_texture(rng, base_rgb, spread)
+    t[..., 3] = np.asarray(alphas, np.uint8)[rng.integers(0, len(alphas), size=(16, 16))]
+    return t
+
+
+def greenhouse(room: int = 20, seed: int = 5, width: int = 96, img_height: int = 64) -> PackedScene:
+    """The exhibit world of translucent blocks: a closed room of `room`^3 cells (room + 2 <= 24 with its walls)
+    in a depth-5 octree, sun on, whose only openings are glazed —
+      an east window of stained-glass cubes in three block ids (solid ARGB, alpha bytes 0x40 / 0x80 / 0xC0; columns of one id side by
+        side and columns of different ids), the 0xC0 glass with a non-zero specular byte;
+      a roof light of thin-box pane model blocks whose 16 x 16 texture has texel alphas in {0, 64, 128, 255};
+      a south window of crossed-quad model blocks with such a texture;
+      lamps (emittance 1) set into the west wall behind panes of the 0x80 glass;
+    and a pool two cells deep in the three-cell floor: water cubes (alpha 0xB0, biome-water tint type 3) over stone."""
+    assert 12 <= room <= 22
+    rng = np.random.default_rng(seed)
+    depth, S = 5, 32
+    ab = AtlasBuilder(4, 4)
+    t_wall = ab.add(noise_texture(rng, (205, 200, 190), 10))
+    t_stone = ab.add(noise_texture(rng, (125, 125, 125), 14))
+    t_lamp = ab.add(noise_texture(rng, (255, 235, 190), 3))
+    t_pane = ab.add(alpha_texture(rng, (170, 215, 235)))
+    t_vine = ab.add(alpha_texture(rng, (110, 190, 120)))
+    t_sun = ab.add(noise_texture(rng, (255, 250, 230), 4, size=32))
+    atlas, recs = ab.build()
+    pal = Palettes()
+    m_wall, m_stone = pal.material(texture=recs[t_wall]), pal.material(texture=recs[t_stone])
+    m_lamp = pal.material(texture=recs[t_lamp], emittance=1.0)
+    m_pane, m_vine = pal.material(texture=recs[t_pane]), pal.material(texture=recs[t_vine])
+    m_g40 = pal.material(argb=0x40E03030)
+    m_g80 = pal.material(argb=0x8030D040)
+    m_gc0 = pal.material(argb=0xC03050E0, spec=0x40)  # (word 5: specular byte 0x40)
+    m_water = pal.material(argb=0xB0FFFFFF, tint=3 << 24)
+    air = pal.block_invisible()
+    wall, stone, lamp, g40, g80, gc0, water = (pal.block_cube(x) for x in (m_wall, m_stone, m_lamp, m_g40, m_g80, m_gc0, m_water))
+    pane = pal.block_aabbs([((0, 1, 0.4375, 0.5625, 0, 1), 0, (m_pane,) * 6)])
+
+    def quad(o, xv, yv):
+        return (o, xv, yv, (0.0, 1.0, 0.0, 1.0), m_vine, 1)
+    vine = pal.block_quads([quad((0.1, 0, 0.1), (0.8, 0, 0.8), (0, 1, 0)), quad((0.9, 0, 0.9), (-0.8, 0, -0.8), (0, 1, 0)),
+                            quad((0.1, 0, 0.9), (0.8, 0, -0.8), (0, 1, 0)), quad((0.9, 0, 0.1), (-0.8, 0, 0.8), (0, 1, 0))])
+    t = np.zeros((S, S, S), np.int32)  # [x, y, z]
+    a, b, f = 0, room + 1, 2           # the shell's first and last cell, the floor's top cell
+    t[a:b + 1, a:b + 1, a:b + 1] = wall
+    t[a:b + 1, a:f + 1, a:b + 1] = stone
+    t[a + 1:b, f + 1:b, a + 1:b] = air
+    # the east window: columns of one glass side by side, then another
+    for k, g in enumerate((g40, g40, g80, gc0, gc0, g80)):
+        t[b, f + 3:f + 9, a + 4 + k] = g
+    t[a + 6:a + 13, b, a + 6:a + 13] = pane           # the roof light
+    t[a + 5:a + 11, f + 3:f + 9, b] = vine            # the south window
+    t[a, f + 4:f + 6, a + 6:a + 8] = lamp             # lamps in the west wall ...
+    t[a + 1, f + 4:f + 6, a + 6:a + 8] = g80          # ... behind glass
+    t[a + 3:a + 9, f - 1:f + 1, a + 11:a + 17] = water  # the pool: two cells of water, stone beneath
+    opaque = np.zeros(len(pal.blocks) // 2, bool)       # (the translucent cubes are not: what lies behind them is seen)
+    opaque[[wall, stone, lamp]] = True
+    t = hide_interior(t, opaque)
+    octree = build_octree(t, depth, "bfs")
+    blocks, mats, aabbs, quads = pal.arrays()
+    alt, azi, inten = 0.9, 0.3, 1.25
+    sky = bake_sky(128, sun_direction(alt, azi))
+    sun = pack_sun(alt, azi, inten, True, recs[t_sun])
+    cam = look_at_camera((a + 3.5, f + room * 0.55, a + 3.5), (b - 2.0, f + 2.5, a + room * 0.7), 85.0)
+    return PackedScene(octree=octree, octree_depth=depth, block_palette=blocks,
+                       material_palette=mats, aabb_models=aabbs, quad_models=quads,
+                       world_bvh=empty_bvh(), actor_bvh=empty_bvh(), bvh_trigs=np.zeros(1, np.int32),
+                       atlas=atlas, sky=sky, sky_intensity=inten, sun=sun, camera=cam,
+                       width=width, height=img_height, name=f"greenhouse{room}")
+
+
 def add_entities(scene: PackedScene, n_tris: int, seed: int = 11, actor_tris: int = 0,
                  region: Optional[Tuple[Sequence[float], Sequence[float]]] = None,
-                 leaf_size: int = 4) -> PackedScene:
+                 leaf_size: int = 4, material: Optional[int] = None) -> PackedScene:
     """BASELINE.json config 5: seeded instanced meshes (small textured tetrahedra/boxes) scattered
     in `region` (default: upper half of the world cube), packed into the world BVH (and
     optionally an actor BVH) that share one triangle array, as `AbstractSceneLoader.java:118-127`
-    does."""
+    does.  `material`: a material-palette pointer every triangle gets (a translucent one, say) in place of a drawn one; the
+    geometry is the same either way."""
     rng = np.random.default_rng(seed)
     S = float(1 << scene.octree_depth)
     lo, hi = region if region is not None else ((0.1 * S, 0.3 * S, 0.1 * S), (0.6 * S, 0.7 * S, 0.6 * S))
@@ -664,6 +741,8 @@ def add_entities(scene: PackedScene, n_tris: int, seed: int = 11, actor_tris: in
             R = np.linalg.qr(rng.normal(size=(3, 3)))[0]
             v = (np.array([[1, 1, 1], [1, -1, -1], [-1, 1, -1], [-1, -1, 1]], float) * s) @ R.T + c
             mat = 6 * int(rng.integers(0, nmat))
+            if material is not None:
+                mat = int(material)
             ds = bool(rng.random() < 0.3)
             for (i, j, l) in ((0, 1, 2), (0, 3, 1), (0, 2, 3), (1, 3, 2)):
                 out.append(pack_triangle(v[i], v[j], v[l], (0, 0), (1, 0), (0, 1), mat, ds))

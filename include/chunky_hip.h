@@ -358,6 +358,50 @@ int chunky_fog_check(const chunky_fog* fog);
  * park, bvh, ext, family, 0}, and the refusal's text (NUL-terminated, at most 255 characters) in text256 per row when it is not NULL */
 int chunky_selftest_plan_fog(const int32_t* rows8, int64_t n, int32_t* out8, char* text256);
 
+/* Translucent blocks (no reference counterpart: K/material.h:50-54 tests a hit's alpha and drops it; arithmetic:
+ * csrc/glass_spec.h; specification: tests/glass_port.c).
+ *
+ * Off by default: every hit whose alpha passes the reference's test is opaque.  With translucency on, a hit of colour c and alpha a
+ * (after the tint multiply) with a < opaque_alpha is TRANSLUCENT for a ray that has crossed fewer than max_crossings such hits:
+ *   the path's own ray draws one random number u: u < a, and the hit is a surface vertex as ever; otherwise the ray crosses — throughput
+ *     *= (1 - a) + a c per channel, no emission, the depth unchanged — and is traced on in its direction from the far side;
+ *   a shadow ray (towards the sun, or an emitter sample) draws nothing: its light is multiplied by (1 - a) ((1 - a) + a c) per channel
+ *     and it goes on, clipped at what is left of its distance; an opaque hit, or a translucent one at the cap, blocks it as ever.
+ * A ray that has crossed into a block of the octree is inside that block's RUN: it steps through every leaf of the same block without
+ * a test — a lake or a glass wall is one interface, met on the way in — until it meets a leaf that cannot be hit (air).  A bounce and
+ * the shadow rays of a vertex start inside the run the vertex was reached through.  No refraction, no absorption by path length.
+ * With nothing translucent in view the image is the extended integrator's, bit for bit.
+ *
+ * chunky_render_set_translucency: `t` NULL turns the feature off; else t->size is the caller's sizeof(chunky_translucency) (a smaller
+ * struct that still holds max_crossings is taken; a larger one when its extra bytes are all 0), opaque_alpha must lie in (0, 1]
+ * (default 0.99: an alpha byte of 0xFF arrives as 255/256, or (255/256)^2 through a tint, and stays opaque) and max_crossings in
+ * [1, 31] (default 8).  CHUNKY_E_INVALID, nothing changed, otherwise.  It touches no image and reaches every member of a group; like a
+ * change of options it ends an adaptive run that could have been resumed.
+ * chunky_render_translucency reports the parameters (out->size is set to this header's sizeof) and, in *enabled when not NULL, whether the
+ * feature is on.  chunky_translucency_check is set_translucency's test without a target or a device.
+ *
+ * While translucency is on:
+ *   chunky_render_passes            runs the glass kernels (the extended integrator whatever the light-transport options say, which all
+ *                                   apply), or answers CHUNKY_E_STATE with the reason, before anything is launched or written: a fog
+ *                                   layer on the target, and everything chunky_render_set_fog lists for fog.  Shards, groups, canvas
+ *                                   windows and external device buffers work unchanged.
+ *   chunky_render_light_passes, chunky_render_adaptive*, chunky_render_robust_*, chunky_render_set_fog with a density
+ *                                   CHUNKY_E_STATE: not supported with translucent blocks.
+ *   the first-hit passes (AOV, matte, occlusion), the preview and trace records   ignore it: every hit is opaque to them.
+ * chunky_render_kernel_info's sixth word is 4 for a glass instantiation.  The Java binding does not reach these calls. */
+typedef struct chunky_translucency {
+    size_t size;           /* sizeof(chunky_translucency) of the caller */
+    float opaque_alpha;    /* in (0, 1] */
+    int32_t max_crossings; /* in [1, 31] */
+} chunky_translucency;
+int chunky_render_set_translucency(chunky_render* r, const chunky_translucency* t);
+int chunky_render_translucency(chunky_render* r, chunky_translucency* out, int* enabled);
+int chunky_translucency_check(const chunky_translucency* t);
+/* self test (no device): plan_glass (csrc/launch_plan.hpp) for n rows of 9 ints {CHUNKY_OPT_KERNEL word, projector type, max depth, wide
+ * tree (0 / 1), entity BVHs (0 / 1), BVH records (0 / 1), biome map applied (0 / 1), wide levels, fog layer (0 / 1)}; out8 per row
+ * {status, refusal, tree, park, bvh, ext, family, words of a parked path}, and the refusal's text in text256 per row when it is not NULL */
+int chunky_selftest_plan_glass(const int32_t* rows9, int64_t n, int32_t* out8, char* text256);
+
 typedef enum chunky_option {
     CHUNKY_OPT_DRAW_DEPTH = 0,      /* int, default 256  (K/rayTracer.cl:94) */
     CHUNKY_OPT_MAX_DEPTH = 1,       /* int >= 1, default 5 (K/rayTracer.cl:107); above 254 the fallback kernels run (render_pool marks a
@@ -448,7 +492,7 @@ int chunky_render_kernel_time(chunky_render* r, float* total_ms, int* launches);
  * requests into launches of that many); 1 when the launch tested full cubes and model blocks in phases of their own}.  On a group:
  * member 0's launch.  The sixth word is 2 for a biome-tint instantiation (chunky_scene_set_biome_tints), before the target's first launch
  * too: the first five words then name the instantiation its next launch will run (workgroups 0).  It is 3 for a ground-fog
- * instantiation (chunky_render_set_fog), likewise. */
+ * instantiation (chunky_render_set_fog), likewise, and 4 for a translucent-blocks instantiation (chunky_render_set_translucency). */
 int chunky_render_kernel_info(chunky_render* r, int32_t out8[8]);
 
 /* Profile of the wave-scheduled kernel, filled only while CHUNKY_OPT_KERNEL has bit 2 set: for each of
